@@ -2,12 +2,19 @@
 """bench.py -- whole-job throughput of the raster hydrology hot path on MI355X.
 
 Metric (BASELINE.json): Mcells/s for fill -> D8 -> accumulation -> bluespot label (-> watershed, pour points) with the
-inputs resident in HBM when the timed region starts, plus the achieved fraction of the HBM roofline per stage (the D8
-stencil is the metric's second headline).  A "step" is one pass of the whole chain over the DEM:
+inputs resident in HBM when the timed region starts, plus (--full) the achieved fraction of the HBM roofline per stage (the
+D8 stencil is the metric's second headline).  A "step" is one pass of the whole chain over the DEM:
     fill (+depths) -> minimum_safe_short_and_diag + no-flats fill -> D8 -> accumulation ->
     connected components + label_stats -> (keep all) -> watersheds + label_count -> pour points (argmax accum)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--beta 2.0] [--bands B] [--config 2|3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--beta 2.0] [--bands B] [--config 2|3] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, ms_per_step, the chain's
+configuration and engines).  --full adds what takes work of its own: the per-stage times of about eight timed steps, the
+roofline of the dominant stage and of the D8 stencil timed alone, the measured copy / read bandwidth of the device and the
+single-thread CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64): the
+rasters at a fixed seeded sample of cells and the per-label records at a fixed seeded sample of labels (write_outputs).
 
 Workloads (BASELINE.json `configs`):
   N = 1 (default)    configs[2]: one 16384^2 fBm DEM on one GPU, one device context -- the configuration the metric is quoted on.
@@ -26,8 +33,8 @@ N > 1 is launched by torch.distributed.run (one process per GPU).  torch is used
 ncclUniqueId to the ranks); the product package is torch-free.  If the band path fails on any rank the run exits non-zero:
 there is no fall-back to independent replicas.
 
-Only the `cpu_baseline` leg touches oracle/ (the single-thread C restatement of the reference path), on a bounded sample,
-on rank 0 at N = 1.
+Only the `cpu_baseline` leg (--full) touches oracle/ (the single-thread C restatement of the reference path), on a bounded
+sample, on rank 0 at N = 1.
 """
 import argparse
 import json
@@ -220,6 +227,40 @@ def cpu_baseline(dem, sample):
             "sample": "%dx%d crop of the benchmark DEM, full chain, %.1f s, 1 thread (the reference path is single-threaded)" % (sample, sample, dt)}
 
 
+CELL_SAMPLE, LABEL_SAMPLE = 1 << 19, 1 << 17      # at most 8 x 4 MiB of rasters + 9 x 1 MiB of label records, all float64
+
+
+def write_outputs(pipe, rasters, labelled, outdir):
+    """What a caller of the timed path receives after its last step, as float64 .npy files under `outdir`: every raster at the
+    same fixed, seeded sample of cells (`cells`: flat row-major indices, sorted) and, when the chain labels bluespots, `nlabels`
+    and the records of label_stats / label_count / pour points at a fixed, seeded sample of labels (`label_ids`, 0 = background);
+    `short_diag` are the no-flats increments.  The samples depend only on the raster shape and the label count."""
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    out = {}
+    total = pipe.shape[0] * pipe.shape[1]
+    rng = np.random.default_rng(1)
+    cells = np.arange(total) if total <= CELL_SAMPLE else np.unique(rng.integers(0, total, size=CELL_SAMPLE))
+    out["cells"] = cells
+    for name in rasters:
+        out[name] = pipe.download(name).reshape(-1)[cells]
+    out["short_diag"] = np.array([pipe.get_float("short"), pipe.get_float("diag")])
+    if labelled:
+        n = pipe.get_int("nlabels")
+        ids = np.arange(n + 1) if n + 1 <= LABEL_SAMPLE else np.unique(rng.integers(0, n + 1, size=LABEL_SAMPLE))
+        stats, counts, pour = pipe.stats(), pipe.watershed_counts(), pipe.pourpoints()
+        out.update({"nlabels": np.array([n]), "label_ids": ids, "watershed_counts": counts[ids]})
+        out.update({"stats_" + f: stats[f][ids] for f in ("min", "max", "sum", "count")})
+        out.update({"pour_" + f: pour[f][ids] for f in ("value", "row", "col")})
+    nbytes = 0
+    for name, a in out.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        nbytes += a.nbytes
+        np.save(outdir / (name + ".npy"), a)
+    assert nbytes <= 64 << 20, nbytes
+    return sorted(out)
+
+
 class BandWorker(threading.Thread):
     """One band of the row-banded DEM: owns a BandPipeline, runs one chain per step on request."""
 
@@ -267,12 +308,18 @@ def main():
     ap.add_argument("--beta", type=float, default=2.0)
     ap.add_argument("--bands", type=int, default=0, help="row bands in total (default: as many as the int32 cell domain needs, >= N)")
     ap.add_argument("--config", type=int, default=3, choices=(2, 3), help="2: 4096^2, fill + D8 only (BASELINE configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-stage times, the rooflines (D8 stencil timed alone, device copy / read bandwidth) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float64, seeded samples)")
     ap.add_argument("--cpu-sample", type=int, default=8192)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--check", action="store_true",
                     help="band runs: after the timed steps compare every band's rasters (sha256 of its owned rows) and the label count with ONE "
                          "undivided context on rank 0 (the DEM must fit one context: < 2**31 cells); exit code 6 on a difference")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -297,6 +344,8 @@ def main():
     nbands = -(-nbands // world) * world
     band_mode = (world > 1 or nbands > 1) and not config2
     stage_names = ["fill", "noflat", "flowdir"] if config2 else STAGES
+    if args.dump_outputs and band_mode:
+        ap.error("--dump-outputs writes the outputs of one device context: not with row bands (--gpus > 1, --bands > 1 or --size > 32768)")
 
     t_gen = time.perf_counter()
     src = DemSource(n, args.beta)
@@ -429,7 +478,7 @@ def main():
     t0 = time.perf_counter()
     stride = max(1, args.steps // 8)
     for i in range(args.steps):
-        step(True, i % stride == 0)
+        step(True, args.full and i % stride == 0)
     barrier()
     elapsed = time.perf_counter() - t0
     if dist is not None:
@@ -463,6 +512,10 @@ def main():
         if rank == 0:
             print("bench.py: the band chain failed (or fell back to a slow engine) on at least one rank; no metric is reported", file=sys.stderr)
         shutdown(4)
+
+    if args.dump_outputs:
+        write_outputs(pipe, ("filled", "noflat", "flowdir") if config2 else ("filled", "depths", "noflat", "flowdir", "accum", "labels", "watersheds"),
+                      not config2, args.dump_outputs)
 
     check_note = None
     if args.check and band_mode:
@@ -512,7 +565,7 @@ def main():
     # from the surface it holds in registers and the `flowdir` stage is an empty interval, so the kernel is timed as a request of
     # its own on the resident surface, after the timed steps (HIP events on its stream, like every stage).
     d8_alone_ms = d8_single_ms = None
-    if pipe is not None:
+    if pipe is not None and args.full:
         # steady-state stencil throughput: 16 launches back to back between ONE pair of HIP events on the kernel's stream
         # (mhip_ctx_kernel_ms "d8_steady"), best-of-3 is NOT taken: the mean of three such batches
         acc = 0.0
@@ -565,66 +618,8 @@ def main():
         if info["noflat_algorithm"] not in (2, 3):
             info["noflat_reject"] = {k: pipe.get_int("noflat_reject" + k) for k in ("", "_irregular", "_unreached", "_mismatch")}
     if rank == 0:
-        stages = {}
-        for s in stage_names:
-            gbs = ALG_BYTES[s] * cells / (stage_ms[s] * 1e-3) / 1e9 if stage_ms[s] > 0 else 0.0
-            stages[s] = {"ms": round(stage_ms[s], 3), "alg_bytes_per_cell": ALG_BYTES[s], "achieved_GBs": round(gbs, 1),
-                         "frac_of_hbm_peak": round(gbs / (HBM_PEAK_GBS * world), 4)}
-        # The chain runs fill -> no-flats fill -> D8 alone on the GPU, then {accumulation} next to {labelling -> watersheds} and the
-        # pour points: the event times of those tail stages include the time they waited for CUs the other branch held (alone:
-        # accumulation 5.6, labelling 5.5, watersheds 3.6 ms at 16384^2).  The dominant stage is taken among the stages
-        # that had the GPU to themselves, whose time means the same thing in the chain and alone.
-        overlapped = () if (band_mode or config2 or serial_streams) else ("accum", "label", "watershed", "pourpoints")
-        for s in overlapped:
-            stages[s]["overlapped"] = True
-        dominant = max((s for s in stage_names if s not in overlapped), key=lambda s: stage_ms[s])
-        d8 = dict(stages["flowdir"])
-        if d8_alone_ms:
-            if stage_ms["flowdir"] < 0.5 * d8_alone_ms:
-                stages["flowdir"].update({"achieved_GBs": None, "frac_of_hbm_peak": None,
-                                          "fused_into": "noflat (ng_finish_kernel writes the directions; d8_roofline times the stencil on its own)"})
-            gbs = ALG_BYTES["flowdir"] * cells / (d8_alone_ms * 1e-3) / 1e9
-            d8 = {"ms": round(d8_alone_ms, 4), "achieved_GBs": round(gbs, 1), "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4)}
-        if "pourpoints" in stages and info.get("pour_algorithm") == 1:
-            # the 12 B/cell pass over accumulation + labels does not run: the keys come out of the accumulation's final pass and the
-            # stage is pour_finish_kernel over one key per label
-            stages["pourpoints"].update({"achieved_GBs": None, "frac_of_hbm_peak": None, "alg_bytes_per_cell": None,
-                                         "fused_into": "accum (accum_final_walk_kernel writes one key per label; this stage turns keys into records)"})
-        copy_gbs = read_gbs = None
-        try:
-            copy_gbs = round(pipe.copy_bandwidth(), 1) if pipe is not None else None
-            read_gbs = round(pipe.read_bandwidth(), 1) if pipe is not None else None
-        except Exception:
-            copy_gbs = read_gbs = None
         chain = "fill -> no-flats fill -> D8" if config2 else ("fill+depths -> no-flats fill -> D8 -> accumulation -> CCL+label_stats -> "
                                                                "watersheds+label_count -> pour points")
-        launches_key = {"fill": "fill_launches" if "fill_launches" in info else "fill_rounds", "noflat": "noflat_rounds"}.get(dominant, "")
-
-        def kernel_detail(stage):
-            """the dominant KERNEL of the dominant stage: its own device time (HIP events around its launches, live in this run) and
-            its own HBM bytes (the committed PMC table of the same command), next to the stage figure"""
-            if band_mode or stage not in hot_ms or hot_ms[stage] <= 0.0:
-                return None
-            kms = hot_ms[stage] / max(nsampled[0], 1)
-            out_ = {"name": KERNEL_OF_STAGE[stage], "launches_per_step": hot_launches[stage], "ms_per_step": round(kms, 3),
-                    "avg_launch_us": round(1e3 * kms / max(hot_launches[stage], 1), 1), "timed_by": "HIP events around the launches, on their stream"}
-            rows, meta, path = pmc_table(n)
-            fp = lib_fingerprint()
-            if rows is not None and fp and meta.get("library_sources_sha256_16") == fp:
-                # counter-based figures (HBM bytes the kernel MOVED / its time), only when the table was collected with this very
-                # library: they are traffic, not the algorithmic fraction the `frac` keys of this line carry
-                for row in rows:
-                    if row["kernel"].startswith(KERNEL_OF_STAGE[stage]):
-                        own = (2.0 * row["fetch_size_kb"] + row["write_size_kb"]) * 1024.0 / max(int(meta.get("steps", 1)), 1)
-                        out_.update({"traffic_bytes_per_step": round(own), "traffic_bytes_per_cell": round(own / cells, 2),
-                                     "traffic_GBs": round(own / (kms * 1e-3) / 1e9, 1),
-                                     "traffic_frac_of_hbm_peak": round(own / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                     "traffic_source": "profiles/" + path.name, "fetch_correction": FETCH_NOTE})
-                        break
-            elif rows is not None:
-                out_["traffic_note"] = "profiles/%s was collected with another build of the library (%s != %s): no counter figures" % (
-                    path.name, meta.get("library_sources_sha256_16"), fp)
-            return out_
         out = {
             "metric": ("Mcells/s fill->D8 on %d^2 f32 DEM" if config2 else "Mcells/s fill->D8->accum->label on %d^2 f32 DEM") % n,
             "value": round(value, 2), "unit": "Mcells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -635,25 +630,86 @@ def main():
                        "parallelism": parallelism, "dem_generation_s": round(t_gen, 1),
                        **({"streams": "serial (MHIP_SERIAL=1: every stage alone on the GPU, the pour points as a pass of their own)"} if serial_streams else {}),
                        **info},
-            "roofline": {"bound": "hbm", "kernel": KERNEL_OF_STAGE.get(dominant, dominant), "stage": dominant,
-                         "kernel_detail": kernel_detail(dominant),
-                         "launches_per_step": info.get(launches_key, 1),
-                         "achieved": stages[dominant]["achieved_GBs"], "peak": HBM_PEAK_GBS * world,
-                         "unit": "GB/s", "frac": stages[dominant]["frac_of_hbm_peak"], "traffic": pmc_traffic(dominant, n) if not band_mode else None,
-                         "measured_copy_peak_GBs": copy_gbs, "measured_read_peak_GBs": read_gbs,
-                         "note": "dominant stage by %s; algorithmic bytes of the whole stage / stage time" % (
-                             "host wall clock of the slowest band (rank 0)" if band_mode else "device time (HIP events on the stage's stream)")},
-            "d8_roofline": {"bound": "hbm", "kernel": "d8s_kernel", "ms": d8["ms"],
-                            "timed_by": "16 launches back to back between one pair of HIP events on the kernel's stream, mean of 3 batches",
-                            "ms_single_request": round(d8_single_ms, 4) if d8_single_ms else None,
-                            "achieved": d8["achieved_GBs"], "peak": HBM_PEAK_GBS * world,
-                            "unit": "GB/s", "frac": d8["frac_of_hbm_peak"], "frac_of_measured_copy_peak": round(d8["achieved_GBs"] / copy_gbs, 4) if copy_gbs else None,
-                            "frac_of_measured_read_peak": round(d8["achieved_GBs"] / read_gbs, 4) if read_gbs else None,
-                            "traffic": pmc_traffic("flowdir", n) if not band_mode else None},
-            "stages": stages, "stage_times_sampled_steps": nsampled[0] if not band_mode else None,
         }
-        if world == 1 and not band_mode and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(src.full, min(args.cpu_sample, n))
+        if args.full:
+            stages = {}
+            for s in stage_names:
+                gbs = ALG_BYTES[s] * cells / (stage_ms[s] * 1e-3) / 1e9 if stage_ms[s] > 0 else 0.0
+                stages[s] = {"ms": round(stage_ms[s], 3), "alg_bytes_per_cell": ALG_BYTES[s], "achieved_GBs": round(gbs, 1),
+                             "frac_of_hbm_peak": round(gbs / (HBM_PEAK_GBS * world), 4)}
+            # The chain runs fill -> no-flats fill -> D8 alone on the GPU, then {accumulation} next to {labelling -> watersheds} and the
+            # pour points: the event times of those tail stages include the time they waited for CUs the other branch held (alone:
+            # accumulation 5.6, labelling 5.5, watersheds 3.6 ms at 16384^2).  The dominant stage is taken among the stages
+            # that had the GPU to themselves, whose time means the same thing in the chain and alone.
+            overlapped = () if (band_mode or config2 or serial_streams) else ("accum", "label", "watershed", "pourpoints")
+            for s in overlapped:
+                stages[s]["overlapped"] = True
+            dominant = max((s for s in stage_names if s not in overlapped), key=lambda s: stage_ms[s])
+            d8 = dict(stages["flowdir"])
+            if d8_alone_ms:
+                if stage_ms["flowdir"] < 0.5 * d8_alone_ms:
+                    stages["flowdir"].update({"achieved_GBs": None, "frac_of_hbm_peak": None,
+                                              "fused_into": "noflat (ng_finish_kernel writes the directions; d8_roofline times the stencil on its own)"})
+                gbs = ALG_BYTES["flowdir"] * cells / (d8_alone_ms * 1e-3) / 1e9
+                d8 = {"ms": round(d8_alone_ms, 4), "achieved_GBs": round(gbs, 1), "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4)}
+            if "pourpoints" in stages and info.get("pour_algorithm") == 1:
+                # the 12 B/cell pass over accumulation + labels does not run: the keys come out of the accumulation's final pass and the
+                # stage is pour_finish_kernel over one key per label
+                stages["pourpoints"].update({"achieved_GBs": None, "frac_of_hbm_peak": None, "alg_bytes_per_cell": None,
+                                             "fused_into": "accum (accum_final_walk_kernel writes one key per label; this stage turns keys into records)"})
+            copy_gbs = read_gbs = None
+            try:
+                copy_gbs = round(pipe.copy_bandwidth(), 1) if pipe is not None else None
+                read_gbs = round(pipe.read_bandwidth(), 1) if pipe is not None else None
+            except Exception:
+                copy_gbs = read_gbs = None
+            launches_key = {"fill": "fill_launches" if "fill_launches" in info else "fill_rounds", "noflat": "noflat_rounds"}.get(dominant, "")
+
+            def kernel_detail(stage):
+                """the dominant KERNEL of the dominant stage: its own device time (HIP events around its launches, live in this run) and
+                its own HBM bytes (the committed PMC table of the same command), next to the stage figure"""
+                if band_mode or stage not in hot_ms or hot_ms[stage] <= 0.0:
+                    return None
+                kms = hot_ms[stage] / max(nsampled[0], 1)
+                out_ = {"name": KERNEL_OF_STAGE[stage], "launches_per_step": hot_launches[stage], "ms_per_step": round(kms, 3),
+                        "avg_launch_us": round(1e3 * kms / max(hot_launches[stage], 1), 1), "timed_by": "HIP events around the launches, on their stream"}
+                rows, meta, path = pmc_table(n)
+                fp = lib_fingerprint()
+                if rows is not None and fp and meta.get("library_sources_sha256_16") == fp:
+                    # counter-based figures (HBM bytes the kernel MOVED / its time), only when the table was collected with this very
+                    # library: they are traffic, not the algorithmic fraction the `frac` keys of this line carry
+                    for row in rows:
+                        if row["kernel"].startswith(KERNEL_OF_STAGE[stage]):
+                            own = (2.0 * row["fetch_size_kb"] + row["write_size_kb"]) * 1024.0 / max(int(meta.get("steps", 1)), 1)
+                            out_.update({"traffic_bytes_per_step": round(own), "traffic_bytes_per_cell": round(own / cells, 2),
+                                         "traffic_GBs": round(own / (kms * 1e-3) / 1e9, 1),
+                                         "traffic_frac_of_hbm_peak": round(own / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                         "traffic_source": "profiles/" + path.name, "fetch_correction": FETCH_NOTE})
+                            break
+                elif rows is not None:
+                    out_["traffic_note"] = "profiles/%s was collected with another build of the library (%s != %s): no counter figures" % (
+                        path.name, meta.get("library_sources_sha256_16"), fp)
+                return out_
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": KERNEL_OF_STAGE.get(dominant, dominant), "stage": dominant,
+                             "kernel_detail": kernel_detail(dominant),
+                             "launches_per_step": info.get(launches_key, 1),
+                             "achieved": stages[dominant]["achieved_GBs"], "peak": HBM_PEAK_GBS * world,
+                             "unit": "GB/s", "frac": stages[dominant]["frac_of_hbm_peak"], "traffic": pmc_traffic(dominant, n) if not band_mode else None,
+                             "measured_copy_peak_GBs": copy_gbs, "measured_read_peak_GBs": read_gbs,
+                             "note": "dominant stage by %s; algorithmic bytes of the whole stage / stage time" % (
+                                 "host wall clock of the slowest band (rank 0)" if band_mode else "device time (HIP events on the stage's stream)")},
+                "d8_roofline": {"bound": "hbm", "kernel": "d8s_kernel", "ms": d8["ms"],
+                                "timed_by": "16 launches back to back between one pair of HIP events on the kernel's stream, mean of 3 batches",
+                                "ms_single_request": round(d8_single_ms, 4) if d8_single_ms else None,
+                                "achieved": d8["achieved_GBs"], "peak": HBM_PEAK_GBS * world,
+                                "unit": "GB/s", "frac": d8["frac_of_hbm_peak"], "frac_of_measured_copy_peak": round(d8["achieved_GBs"] / copy_gbs, 4) if copy_gbs else None,
+                                "frac_of_measured_read_peak": round(d8["achieved_GBs"] / read_gbs, 4) if read_gbs else None,
+                                "traffic": pmc_traffic("flowdir", n) if not band_mode else None},
+                "stages": stages, "stage_times_sampled_steps": nsampled[0] if not band_mode else None,
+            })
+            if world == 1 and not band_mode and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(src.full, min(args.cpu_sample, n))
         print(json.dumps(out), flush=True)
     shutdown(0)
 

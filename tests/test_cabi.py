@@ -79,25 +79,43 @@ def test_host_helpers_match_reference_semantics():
     assert f2.tolist() == [[7, 0, 1], [6, 8, 2], [5, 4, 3]]
 
 
-REFERENCE = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE + "/malstroem/algorithms"), reason="reference checkout not on this box")
-def test_enable_patches_the_real_reference_package(monkeypatch):
-    """hip.enable(target=malstroem.algorithms) on the reference's own (pure-Python) package: the 13 whole-stage functions
-    are rebound like speedups.enable() rebinds its 8 (speedups/__init__.py:37-77), with identical call signatures, and
-    disable() restores them.  Runs without a GPU (nothing is called); `available` is forced for the duration."""
+def _reference_algorithms_package():
+    """A stand-in for the reference's ``malstroem.algorithms`` package: modules fill / flow / label whose functions carry the
+    reference's recorded call signatures and module names (tests/golden/reference_signatures.json, made by
+    tests/golden/record_reference_signatures.py from the reference checkout).  Every function is a distinct object."""
     import inspect
-    import sys
+    import json
     import types
-    monkeypatch.setattr(sys, "dont_write_bytecode", True)       # never write into the read-only reference tree
-    monkeypatch.syspath_prepend(REFERENCE)
-    import malstroem.algorithms as ref_alg
-    from malstroem.algorithms import fill as rfill, flow as rflow, label as rlabel  # noqa: F401
+    recorded = json.loads((ROOT / "tests" / "golden" / "reference_signatures.json").read_text())
+    pkg = types.SimpleNamespace(fill=types.ModuleType("malstroem.algorithms.fill"), flow=types.ModuleType("malstroem.algorithms.flow"),
+                                label=types.ModuleType("malstroem.algorithms.label"))
+    for key, rec in recorded.items():
+        m, a = key.split(".")
+
+        def fn(*args, **kwargs):
+            raise AssertionError("the stand-in of a reference function was called")
+        fn.__name__ = fn.__qualname__ = a
+        fn.__module__ = rec["module"]
+        fn.__signature__ = inspect.Signature([inspect.Parameter(p["name"], getattr(inspect.Parameter, p["kind"]),
+                                                                default=p.get("default", inspect.Parameter.empty))
+                                              for p in rec["params"]])
+        setattr(getattr(pkg, m), a, fn)
+    return pkg
+
+
+def test_enable_patches_the_real_reference_package(monkeypatch):
+    """hip.enable(target=malstroem.algorithms) on the reference's package, as its recorded interface: the 13 whole-stage
+    functions are rebound like speedups.enable() rebinds its 8 (speedups/__init__.py:37-77), with identical call signatures,
+    and disable() restores them.  Runs without a GPU (nothing is called); `available` is forced for the duration."""
+    import inspect
+    import types
+    ref_alg = _reference_algorithms_package()
     import malstroem_amd.algorithms as alg
     hip = alg.hip
     originals = {(m, a): getattr(getattr(ref_alg, m), a) for (m, a) in hip._PATCH}
     assert len(originals) == 13
+    originals_unpatched = {name: getattr(ref_alg.flow, name)
+                           for name in ("trace_accumulated_flow", "assign_watersheds_upstream", "upstream_cells", "trace_downstream")}
     was_enabled = hip.enabled
     monkeypatch.setattr(hip, "available", True)
     hip.disable()
@@ -116,6 +134,7 @@ def test_enable_patches_the_real_reference_package(monkeypatch):
             assert all(p.default is not inspect.Parameter.empty for p in ours[len(theirs):]), (m, a)
         # functions the reference keeps un-patched stay its own, and exist in the mirror with the same signatures
         for name in ("trace_accumulated_flow", "assign_watersheds_upstream", "upstream_cells", "trace_downstream"):
+            assert getattr(ref_alg.flow, name) is originals_unpatched[name]
             assert getattr(ref_alg.flow, name).__module__ == "malstroem.algorithms.flow"
             assert (list(inspect.signature(getattr(alg.flow, name)).parameters) ==
                     list(inspect.signature(getattr(ref_alg.flow, name)).parameters)), name

@@ -1,8 +1,8 @@
 """Raster I/O boundary: malstroem_amd.io's windowed GeoTIFF reader / writer.
 
 CPU: round trips over every dtype / layout / size class, window reads against whole reads, nodata substitution with the
-reference's rule (io.py:69-71), and -- where the reference checkout is present -- its seven tests/data/*.tif files decoded by
-the product reader against the committed fixtures (decoded independently by tests/golden/decode_reference_fixtures.py).
+reference's rule (io.py:69-71), and the reference's seven tests/data/*.tif files (committed as tests/golden/reference_tifs/)
+decoded by the product reader against the committed fixtures (decoded independently by tests/golden/decode_reference_fixtures.py).
 GPU: DemTool driven by a windowed reader and windowed writers (one window on the host at a time) against the fixtures.
 """
 import os
@@ -10,10 +10,10 @@ import os
 import numpy as np
 import pytest
 
-from _cases import fixtures
+from _cases import GOLDEN, fixtures
 from malstroem_amd.io import RasterReader, RasterWriter
 
-REF_DATA = "/root/reference/tests/data"
+REF_DATA = str(GOLDEN / "reference_tifs")
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64, np.int32, np.uint8, np.uint16])
@@ -131,7 +131,6 @@ def test_nodata_substitution_follows_the_reference_rule(tmp_path):
     assert np.array_equal(RasterReader(p2, nodatasubst=-999).read(), a)      # nodata == 0 is falsy in io.py:69: not substituted
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference checkout not on this box")
 def test_reader_decodes_the_reference_fixtures():
     fx = fixtures()
     for name in ("dtm", "filled", "depths", "filled_no_flats", "flowdir_noflats", "labelled", "wsheds"):

@@ -2,9 +2,9 @@
 traffic table bench.py reads.  On the GPU box:
 
     cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_f -o f -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_w -o w -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
-    python3 tools/pmc_traffic.py gpurun_out/pmc_f/f_results.db gpurun_out/pmc_w/w_results.db 16384 > profiles/<round>_pmc_hbm_traffic.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d out/pmc_f -o f -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d out/pmc_w -o w -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+    python3 tools/pmc_traffic.py out/pmc_f/f_results.db out/pmc_w/w_results.db 16384 > profiles/<round>_pmc_hbm_traffic.json
 
 FETCH_SIZE / WRITE_SIZE are in KiB per dispatch.  Calibration (MI355X_MICROARCH.md, "HBM": FETCH_SIZE = TCC_EA0_RDREQ x 64 B
 while a coalesced streaming read is served in 128-byte requests): every kernel of this run whose compulsory reads are known
