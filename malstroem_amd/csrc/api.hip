@@ -357,6 +357,7 @@ int mhip_label_stats_f32(const float *data, const int32_t *labels, int64_t n, in
     MH_TRY(upload(d_l, labels, (size_t)n * 4, s));
     MH_TRY(d_r.alloc(sizeof(mhip_stat_record) * (size_t)(nlab + 1)));
     MH_TRY(label_stats_dev(d_d.as<float>(), d_l.as<int32_t>(), n, nlab, d_r.as<mhip_stat_record>(), s));
+    MH_TRY(label_stats_zero_sign_dev(d_d.as<float>(), d_l.as<int32_t>(), n, nlab, d_r.as<mhip_stat_record>(), s));
     return download(records, d_r, sizeof(mhip_stat_record) * (size_t)(nlab + 1), s);
 }
 
@@ -370,6 +371,7 @@ int mhip_label_stats_f64(const double *data, const int32_t *labels, int64_t n, i
     MH_TRY(upload(d_l, labels, (size_t)n * 4, s));
     MH_TRY(d_r.alloc(sizeof(mhip_stat_record) * (size_t)(nlab + 1)));
     MH_TRY(label_stats64_dev(d_d.as<double>(), d_l.as<int32_t>(), n, nlab, d_r.as<mhip_stat_record>(), s));
+    MH_TRY(label_stats_zero_sign_dev(d_d.as<double>(), d_l.as<int32_t>(), n, nlab, d_r.as<mhip_stat_record>(), s));
     return download(records, d_r, sizeof(mhip_stat_record) * (size_t)(nlab + 1), s);
 }
 

@@ -380,6 +380,10 @@ int keep_mask_dev(const int32_t *d_labels, const uint8_t *d_keep, int64_t nlab, 
 int label_stats_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec,
                     hipStream_t s, int64_t W = 0, bool components = false);
 int label_stats64_dev(const double *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec, hipStream_t s);
+// the reference keeps the FIRST of equal values: a record whose min / max is a zero gets the sign of its label's first zero cell
+// (the reductions above order -0.0 below +0.0); the standalone label_stats only, see DESIGN.md
+int label_stats_zero_sign_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec, hipStream_t s);
+int label_stats_zero_sign_dev(const double *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec, hipStream_t s);
 int label_arg_dev(const double *d_data, const int32_t *d_labels, int64_t H, int64_t W, int64_t nlab, bool is_max,
                   mhip_index_record *d_rec, hipStream_t s, bool components = false);
 int label_count_dev(const int32_t *d_labels, int64_t n, int64_t nlab, int64_t *d_counts, hipStream_t s, int64_t W = 0);

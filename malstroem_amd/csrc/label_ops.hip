@@ -950,6 +950,53 @@ int label_stats64_dev(const double *d_data, const int32_t *d_labels, int64_t n, 
     return check_bad(bad, s, "label_stats");
 }
 
+// ---- signed zeros of label_stats ------------------------------------------------------------------------------------
+// min / max reduce as ordered keys, which put -0.0 below +0.0; the reference (`val < min`, `val > max`) keeps the first of
+// equal values, so a label whose min (max) is a zero reports the sign of its first zero cell in raster order: that cell's
+// index by one atomicMin per zero cell of such a label, then its value into the record.
+template <typename T>
+__global__ __launch_bounds__(256) void zero_first_kernel(const T *__restrict__ data, const int32_t *__restrict__ lab, int64_t n, int64_t nlab,
+                                                        const mhip_stat_record *__restrict__ rec, unsigned long long *first)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || data[i] != (T)0) return;
+    const int32_t l = lab[i];
+    if (l < 0 || l > nlab) return;
+    if ((rec[l].min == 0.0 || rec[l].max == 0.0) && (unsigned long long)i < first[l]) atomicMin(&first[l], (unsigned long long)i);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void zero_sign_kernel(const T *__restrict__ data, const unsigned long long *__restrict__ first, int64_t nrec,
+                                                       mhip_stat_record *rec)
+{
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= nrec || first[l] == ~0ull) return;
+    const double z = (double)data[first[l]];
+    if (rec[l].min == 0.0) rec[l].min = z;
+    if (rec[l].max == 0.0) rec[l].max = z;
+}
+template <typename T>
+static int zero_sign_dev(const T *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec, hipStream_t s)
+{
+    const int64_t nrec = nlab + 1;
+    DevBuf first;
+    MH_TRY(first.alloc(8 * (size_t)nrec));
+    MH_HIP(hipMemsetAsync(first.p, 0xff, 8 * (size_t)nrec, s));
+    hipLaunchKernelGGL(zero_first_kernel<T>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, d_data, d_labels, n, nlab, (const mhip_stat_record *)d_rec,
+                       first.as<unsigned long long>());
+    hipLaunchKernelGGL(zero_sign_kernel<T>, dim3((unsigned)cdiv(nrec, 256)), dim3(256), 0, s, d_data, first.as<unsigned long long>(), nrec, d_rec);
+    MH_HIP(hipGetLastError());
+    MH_HIP(stream_sync(s));      // `first` goes back to the pool
+    return MHIP_OK;
+}
+int label_stats_zero_sign_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec, hipStream_t s)
+{
+    return zero_sign_dev(d_data, d_labels, n, nlab, d_rec, s);
+}
+int label_stats_zero_sign_dev(const double *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec, hipStream_t s)
+{
+    return zero_sign_dev(d_data, d_labels, n, nlab, d_rec, s);
+}
+
 int label_arg_dev(const double *d_data, const int32_t *d_labels, int64_t H, int64_t W, int64_t nlab, bool is_max,
                   mhip_index_record *d_rec, hipStream_t s, bool components)
 {

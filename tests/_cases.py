@@ -122,3 +122,24 @@ def zigzag_flowdir(h, w, seed):
     every few cells, bouncing back and forth between neighbouring bands."""
     rng = np.random.default_rng(seed)
     return rng.choice(np.array([1, 2, 3], np.uint8), size=(h, w), p=[0.4, 0.2, 0.4]).astype(np.uint8)
+
+
+def assert_same_bits(got, want, what=""):
+    """Bit-for-bit equality of two arrays (record arrays field by field): compares the unsigned-integer views, so -0.0 differs
+    from +0.0; any NaN equals any NaN (the payload is not part of the contract)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
+    if got.dtype.names:
+        for f in got.dtype.names:
+            assert_same_bits(got[f], want[f], "%s.%s" % (what, f) if what else f)
+        return
+    if got.dtype.kind == "f":
+        gn, wn = np.isnan(got), np.isnan(want)
+        bad = (gn != wn) | (~gn & ~wn & (got.view("u%d" % got.itemsize) != want.view("u%d" % want.itemsize)))
+    else:
+        bad = got != want
+    if bad.any():
+        idx = np.argwhere(bad)
+        first = tuple(idx[0])
+        raise AssertionError("%s: %d of %d elements differ, first at %s: got %r, want %r"
+                             % (what or "arrays", len(idx), got.size, first, got[first], want[first]))
