@@ -37,6 +37,10 @@ extern "C" {
 typedef struct { double min, max, sum; int64_t count; } mhip_stat_record;
 /* packed record of reference _label.pyx:26-28 == numpy [('value','<f8'),('row','<i8'),('col','<i8')] */
 typedef struct { double value; int64_t row, col; } mhip_index_record;
+/* final state of one bluespot for a given amount of water (no reference counterpart) == numpy
+ * [('drawdown','<f8'),('dmax_final','<f8'),('qmodel','<f8'),('wet_cells','<i8')]: water level below the spill level, largest
+ * final depth, the amount the hypsometry table holds at that level (cell-metres), cells left with water */
+typedef struct { double drawdown, dmax_final, qmodel; int64_t wet_cells; } mhip_final_record;
 
 /* ---- library / device ------------------------------------------------------------------------- */
 const char *mhip_last_error(void);
@@ -107,6 +111,26 @@ int mhip_label_argmax_f64(const double *data, const int32_t *labels, int64_t H, 
 int mhip_label_count(const int32_t *labels, int64_t n, int64_t nlab, int64_t *counts);
 /* max(labelled) helper (the reference computes nlabels = np.max(labelled) when not given). */
 int mhip_label_max(const int32_t *labels, int64_t n, int32_t *out_max);
+
+/* Hypsometry tables, water levels and final-state depths of labelled depths (no reference counterpart; semantics, the bound of
+ * the table's model volume and its proof: DESIGN.md 9).  Depths are >= 0 and not NaN; amounts q are cell-metres.
+ * layout: nbins[l] = floor(max(dmax[l], 0) / res) + 1 bins for label l >= 1 (none for label 0), offsets[0 .. nlab + 1] their
+ *   exclusive prefix sums; *total = offsets[nlab + 1].  More than 2**30 bins in all (12 bytes each on the device) or an infinite
+ *   dmax: MHIP_ELIMIT.
+ * hyps: cell d of label l >= 1 -> bin offsets[l] + clamp(floor(double(d) / res), 0, nbins[l] - 1); counts / sums [total] = cells
+ *   and sum of double(d) per bin.  W: the raster's width (0: a flat array).  *lds_spills (optional): runs of cells that found no
+ *   slot in their tile's on-chip table and went to the global atomics one by one.
+ * levels: per label the draw-down t whose model volume equals q[l] (0.0 when q[l] >= the full volume, dmax[l] when q[l] <= 0);
+ *   records[0 .. nlab] with wet_cells = 0.
+ * final_depths: out = float(max(0, double(d) - records[label].drawdown)) on labelled cells, 0 on background; counts
+ *   records[l].wet_cells = cells with out > 0. */
+int mhip_label_hyps_layout(const double *dmax, int64_t nlab, double res, int64_t *offsets, int64_t *total);
+int mhip_label_hyps_f32(const float *data, const int32_t *labels, int64_t n, int64_t W, int64_t nlab, double res, const int64_t *offsets,
+                        int64_t *counts, double *sums, int64_t *lds_spills);
+int mhip_hyps_levels(int64_t nlab, const int64_t *offsets, const int64_t *counts, const double *sums, const double *dmax, const double *q,
+                     mhip_final_record *records);
+int mhip_final_depths_f32(const float *data, const int32_t *labels, int64_t n, int64_t W, int64_t nlab, mhip_final_record *records,
+                          float *out);
 
 /* flow.watersheds_from_labels(flowdir, labelled, unassigned)  reference flow.py:398-412 ->
  * _flow.pyx:276-403. In place on labels. Terminates on flow cycles (reference does not). */
@@ -201,13 +225,17 @@ enum mhip_stage {
     MHIP_STAGE_LABEL = 1 << 4,       /* raw bluespot labels i32 + raw label_stats */
     MHIP_STAGE_WATERSHED = 1 << 5,   /* watersheds i32 from (filtered) labels + label_count */
     MHIP_STAGE_POURPOINTS = 1 << 6,  /* argmax(accum) or argmin(no-flats) per label */
-    MHIP_STAGE_ALL = 0x7f
+    MHIP_STAGE_ALL = 0x7f,
+    /* not stages of mhip_ctx_run: the timing slots (mhip_ctx_stage_ms) of mhip_ctx_hyps and mhip_ctx_final_depths */
+    MHIP_STAGE_HYPS = 1 << 7,
+    MHIP_STAGE_FINALDEPTHS = 1 << 8
 };
 
 enum mhip_raster {
     MHIP_R_DEM = 0, MHIP_R_FILLED, MHIP_R_DEPTHS, MHIP_R_NOFLAT, MHIP_R_FLOWDIR, MHIP_R_ACCUM,
     MHIP_R_LABELS, MHIP_R_WATERSHEDS,
     MHIP_R_NGDIST,   /* uint32: distances of the geodesic no-flats fill (row bands exchange its edge rows), see mhip_ctx_geo_begin */
+    MHIP_R_FINALDEPTHS,   /* float32: water depths of the last mhip_ctx_final_depths */
     MHIP_R_COUNT_
 };
 
@@ -364,7 +392,8 @@ int mhip_ctx_trace_downstream(mhip_ctx *ctx, const int64_t *cells_rc, int64_t n,
                               int32_t *out_label, int32_t *out_found, int64_t *out_len, const int64_t *offsets, int64_t *out_cells);
 /* after mhip_ctx_sync: milliseconds (HIP events on the ctx stream) of `stage` (single bit) in the last run */
 int mhip_ctx_stage_ms(mhip_ctx *ctx, int stage, float *ms);
-/* milliseconds / launch count of one named kernel family in the last run ("d8", "fill_round", "noflat_round");
+/* milliseconds / launch count of one named kernel family in the last run ("d8", "fill_round", "noflat_round"; "hyps_table" and
+ * "final_depths": the table kernel of the last mhip_ctx_hyps / the raster pass of the last mhip_ctx_final_depths alone);
  * "d8_steady" is a measurement of its own: it LAUNCHES the D8 stencil on the resident no-flats surface 16 times back to back
  * between one pair of events (steady-state throughput; an undivided context only) and returns their total */
 int mhip_ctx_kernel_ms(mhip_ctx *ctx, const char *kernel, float *ms_total, int32_t *launches);
@@ -382,6 +411,14 @@ int mhip_ctx_apply_keep(mhip_ctx *ctx, const uint8_t *keep);          /* NULL = 
 int mhip_ctx_stats(mhip_ctx *ctx, mhip_stat_record *records);         /* nlabels+1, after apply_keep */
 int mhip_ctx_watershed_counts(mhip_ctx *ctx, int64_t *counts);        /* nlabels+1 */
 int mhip_ctx_pourpoints(mhip_ctx *ctx, mhip_index_record *records);   /* nlabels+1 */
+/* Final state of the bluespots (see mhip_label_hyps_layout ... above; the same kernels) on the resident DEPTHS and LABELS of an
+ * undivided context, after mhip_ctx_apply_keep (or with uploaded labels).  hyps: layout from the resident label statistics and
+ * the table, kept on the device; *total = number of bins.  hyps_fetch: offsets [nlabels + 2], counts / sums [total].
+ * final_depths: q[nlabels + 1] cell-metres -> records[nlabels + 1] and the raster MHIP_R_FINALDEPTHS; any number of calls per
+ * table.  mhip_ctx_get_i64: "hyps_bins", "hyps_lds_spills". */
+int mhip_ctx_hyps(mhip_ctx *ctx, double res, int64_t *total);
+int mhip_ctx_hyps_fetch(mhip_ctx *ctx, int64_t *offsets, int64_t *counts, double *sums);
+int mhip_ctx_final_depths(mhip_ctx *ctx, const double *q, mhip_final_record *records);
 
 #ifdef __cplusplus
 }

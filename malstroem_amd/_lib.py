@@ -17,14 +17,17 @@ CSRC = _PKG / "csrc"
 
 STAT_DTYPE = np.dtype([("min", "<f8"), ("max", "<f8"), ("sum", "<f8"), ("count", "<i8")])   # _label.pyx:22-24
 INDEX_DTYPE = np.dtype([("value", "<f8"), ("row", "<i8"), ("col", "<i8")])                    # _label.pyx:26-28
+FINAL_DTYPE = np.dtype([("drawdown", "<f8"), ("dmax_final", "<f8"), ("qmodel", "<f8"), ("wet_cells", "<i8")])   # mhip_final_record
 
 OK, EINVAL, EHIP, ENODEV, ELIMIT, ENOTCONV, ECOMM = 0, -1, -2, -3, -4, -5, -6
 
 STAGE_FILL, STAGE_NOFLAT, STAGE_FLOWDIR, STAGE_ACCUM = 1, 2, 4, 8
 STAGE_LABEL, STAGE_WATERSHED, STAGE_POURPOINTS, STAGE_ALL = 16, 32, 64, 0x7F
-R_DEM, R_FILLED, R_DEPTHS, R_NOFLAT, R_FLOWDIR, R_ACCUM, R_LABELS, R_WATERSHEDS, R_NGDIST = range(9)
+STAGE_HYPS, STAGE_FINALDEPTHS = 128, 256     # timing slots of mhip_ctx_hyps / mhip_ctx_final_depths, not stages of mhip_ctx_run
+R_DEM, R_FILLED, R_DEPTHS, R_NOFLAT, R_FLOWDIR, R_ACCUM, R_LABELS, R_WATERSHEDS, R_NGDIST, R_FINALDEPTHS = range(10)
 RASTER_DTYPE = {R_DEM: np.float32, R_FILLED: np.float32, R_DEPTHS: np.float32, R_NOFLAT: np.float64,
-                R_FLOWDIR: np.uint8, R_ACCUM: np.float64, R_LABELS: np.int32, R_WATERSHEDS: np.int32, R_NGDIST: np.uint32}
+                R_FLOWDIR: np.uint8, R_ACCUM: np.float64, R_LABELS: np.int32, R_WATERSHEDS: np.int32, R_NGDIST: np.uint32,
+                R_FINALDEPTHS: np.float32}
 
 # every symbol include/malstroem_hip.h declares (checked by tests/test_cabi.py)
 SYMBOLS = [
@@ -46,6 +49,8 @@ SYMBOLS = [
     "mhip_ctx_band_foreign_counts", "mhip_ctx_side_begin", "mhip_ctx_side_end",
     "mhip_ctx_has_comm", "mhip_ctx_exchange_halo", "mhip_ctx_exchange_edge_rows", "mhip_ctx_comm_add_side", "mhip_band_union_find", "mhip_band_accum_pairs", "mhip_band_accum_solve", "mhip_band_label_pairs",
     "mhip_band_label_merge", "mhip_band_ws_publish", "mhip_band_ws_lut", "mhip_band_merge_records", "mhip_tg_create", "mhip_tg_destroy", "mhip_tg_barrier", "mhip_tg_allreduce_max", "mhip_tg_offer", "mhip_tg_take", "mhip_shm_barrier", "mhip_ctx_allreduce_max",
+    "mhip_label_hyps_layout", "mhip_label_hyps_f32", "mhip_hyps_levels", "mhip_final_depths_f32", "mhip_ctx_hyps", "mhip_ctx_hyps_fetch",
+    "mhip_ctx_final_depths",
 ]
 
 _lib = None

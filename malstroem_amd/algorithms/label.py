@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from .._lib import INDEX_DTYPE, STAT_DTYPE
+from .._lib import FINAL_DTYPE, INDEX_DTYPE, STAT_DTYPE
 from .dtypes import DTYPE_LABEL
 
 
@@ -114,3 +114,70 @@ def label_count(labelled):
     out = np.zeros(n + 1, dtype=np.int64)
     _lib.call("mhip_label_count", _lib.ptr(lab), _lib.i64(lab.size), _lib.i64(n), _lib.ptr(out))
     return out
+
+
+def _depths(data, labelled):
+    data = np.asarray(data)
+    if data.dtype != np.float32:
+        raise ValueError("dtype mismatch: float32 depths expected, got '%s'" % data.dtype)
+    data = np.ascontiguousarray(data)
+    lab = _labels(labelled)
+    if lab.shape != data.shape:
+        raise ValueError("shape mismatch")
+    if data.size == 0:
+        raise ValueError("empty raster")
+    width = data.shape[-1] if data.ndim == 2 else 0
+    return data, lab, width
+
+
+def label_hypsometry(data, labelled, resolution, nlabels=None):
+    """Hypsometry table of every label (no reference counterpart): ``(offsets, counts, sums)``.
+
+    Label ``l >= 1`` with largest depth ``dmax`` owns the bins ``[offsets[l], offsets[l + 1])``,
+    ``floor(dmax / resolution) + 1`` of them; a cell of depth ``d`` counts in bin ``min(floor(float64(d) / resolution), last)``
+    with ``counts`` (int64) and ``sums`` (float64 sum of the depths).  ``data``: float32 depths >= 0 without NaN."""
+    from ..finalstate import check_resolution
+    res = check_resolution(resolution)
+    data, lab, width = _depths(data, labelled)
+    nlabels = _nlabels(lab, nlabels)
+    stats = label_stats(data, lab, nlabels)
+    dmax = np.ascontiguousarray(stats["max"])
+    offsets = np.zeros(nlabels + 2, dtype=np.int64)
+    total = ctypes.c_int64(0)
+    _lib.call("mhip_label_hyps_layout", _lib.ptr(dmax), _lib.i64(nlabels), ctypes.c_double(res), _lib.ptr(offsets), ctypes.byref(total))
+    counts = np.zeros(total.value, dtype=np.int64)
+    sums = np.zeros(total.value, dtype=np.float64)
+    _lib.call("mhip_label_hyps_f32", _lib.ptr(data), _lib.ptr(lab), _lib.i64(lab.size), _lib.i64(width), _lib.i64(nlabels), ctypes.c_double(res),
+              _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(sums), None)
+    return offsets, counts, sums
+
+
+def final_depths(data, labelled, offsets, counts, sums, q, resolution):
+    """Final-state depths for ``q[l]`` cell-metres of water in label ``l``: ``(raster float32, records)``.
+
+    ``offsets, counts, sums``: the tables of ``label_hypsometry`` on the same rasters at the same ``resolution``; the level of a
+    label is the draw-down below its spill level at which the table holds ``q[l]``; ``raster = max(0, depth - drawdown[label])``.
+    ``records`` (``_lib.FINAL_DTYPE``): drawdown, dmax_final, qmodel, wet_cells per label."""
+    from ..finalstate import check_resolution, hyps_layout
+    res = check_resolution(resolution)
+    data, lab, width = _depths(data, labelled)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    nlabels = offsets.size - 2
+    if offsets.ndim != 1 or nlabels < 0:
+        raise ValueError("offsets must have nlabels + 2 entries")
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    if counts.shape != (int(offsets[-1]),) or sums.shape != counts.shape:
+        raise ValueError("counts and sums must have offsets[-1] entries")
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if q.shape != (nlabels + 1,):
+        raise ValueError("len(q) must be nlabels + 1 = %d" % (nlabels + 1))
+    stats = label_stats(data, lab, nlabels)      # (raises for a label above nlabels)
+    dmax = np.ascontiguousarray(stats["max"])
+    if not np.array_equal(hyps_layout(dmax, res)[1], offsets):
+        raise ValueError("offsets are not the hypsometry layout of these rasters at resolution %g" % res)
+    rec = np.zeros(nlabels + 1, dtype=FINAL_DTYPE)
+    _lib.call("mhip_hyps_levels", _lib.i64(nlabels), _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(sums), _lib.ptr(dmax), _lib.ptr(q), _lib.ptr(rec))
+    out = np.empty(data.shape, dtype=np.float32)
+    _lib.call("mhip_final_depths_f32", _lib.ptr(data), _lib.ptr(lab), _lib.i64(lab.size), _lib.i64(width), _lib.i64(nlabels), _lib.ptr(rec), _lib.ptr(out))
+    return out, rec

@@ -86,17 +86,26 @@ def parse_filter(filter):
     return filter_function
 
 
-def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None):
+def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
+                finalstate=False, hyps_resolution=0.05):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
 
     ``dem``: path of the DEM GeoTIFF (metres, square cells); ``outdir``: an existing empty directory; ``rain``: rain incidents
     in mm; ``accum``: also compute the accumulated flow (pour points then sit at its maximum, bluespots.py:195-200);
-    ``filter``: bluespot filter expression.  Returns a dict with the paths written and the counts the reference logs."""
+    ``filter``: bluespot filter expression.  Returns a dict with the paths written and the counts the reference logs.
+
+    ``finalstate``: also write, for every rain event, the raster of the water depths the event leaves behind
+    (``finaldepths_<mm:g>.tif``; ``finalstate.FinalStateTool`` on the pipeline the bluespots were computed on, hypsometry tables at
+    ``hyps_resolution`` metres) and the vector layer ``finalstate``: the events with water level, largest depth and wet area per
+    bluespot; the dict gains ``finalstate`` and ``finaldepths``.  Not on row bands yet."""
     if vector:
         raise NotImplementedError("vectorisation of bluespots / watersheds (GDAL polygonize) is outside malstroem_amd's hot path")
     if comm is not None and comm.size > 1:
+        if finalstate:
+            raise NotImplementedError("finalstate on row bands: the hypsometry tables of the bands add up (counts and sums of a global "
+                                      "label), which is not built yet; run it on one context")
         return _process_all_bands(dem, outdir, rain, accum, filter, comm, device, nodatasubst, backend_factory)
     if not os.path.isdir(outdir) or os.listdir(outdir):
         raise ValueError("outdir isn't an empty directory")
@@ -131,15 +140,30 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         nodes_writer = io.VectorWriter('GeoJSON', outvector, 'nodes', None, None, crs)
         streams_writer = io.VectorWriter('GeoJSON', outvector, 'streams', None, None, crs)
         StreamTool(pourpoints_reader, dem_reader, dem_reader, nodes_writer, streams_writer, pipeline=pipe).process()
+        if not finalstate:
+            pipe.close()
+        # Process rain events
+        nodes_reader = io.VectorReader(outvector, nodes_writer.layername)
+        events_writer = io.VectorWriter('GeoJSON', outvector, 'events', None, None, crs)
+        RainTool(nodes_reader, events_writer, rain).process()
+        res = dict(outdir=outdir, vector=outvector, nlabels=nlabels, events=events_writer.filepath,
+                   nodes=nodes_writer.filepath, streams=streams_writer.filepath, pourpoints=pourpoint_writer.filepath)
+        if finalstate:
+            # Final state of every event: the depths and the filtered labels are still on the device
+            from .finalstate import FinalStateTool
+            written = {}
+
+            def depths_writer_for(tag):
+                written[tag] = os.path.join(outdir, 'finaldepths_{}.tif'.format(tag))
+                return io.RasterWriter(written[tag], tr, crs)
+            final_writer = io.VectorWriter('GeoJSON', outvector, 'finalstate', None, None, crs)
+            FinalStateTool(dem_reader, dem_reader, io.VectorReader(outvector, events_writer.layername), depths_writer_for, hyps_resolution,
+                           pipeline=pipe, device=device, output_eventdata=final_writer).process()
+            res.update(finalstate=final_writer.filepath, finaldepths=written)
     finally:
         pipe.close()
         dem_reader.close()
-    # Process rain events
-    nodes_reader = io.VectorReader(outvector, nodes_writer.layername)
-    events_writer = io.VectorWriter('GeoJSON', outvector, 'events', None, None, crs)
-    RainTool(nodes_reader, events_writer, rain).process()
-    return dict(outdir=outdir, vector=outvector, nlabels=nlabels, events=events_writer.filepath,
-                nodes=nodes_writer.filepath, streams=streams_writer.filepath, pourpoints=pourpoint_writer.filepath)
+    return res
 
 
 def _process_all_bands(dem, outdir, rain, accum, filter, comm, device, nodatasubst, backend_factory):

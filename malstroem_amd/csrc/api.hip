@@ -423,6 +423,102 @@ int mhip_label_max(const int32_t *labels, int64_t n, int32_t *out_max)
     return label_max_dev(d_l.as<int32_t>(), n, out_max, s);
 }
 
+/* ---- hypsometry tables, water levels, final depths on host arrays (hyps.hip; the context entry points launch the same kernels) ---- */
+static bool hyps_res_ok(double res) { return res > 0.0 && res <= 1.7976931348623157e308; }   // (false for NaN)
+
+// offsets[0 .. nlab + 1] as mhip_label_hyps_layout makes them: 0, 0, then strictly increasing, at most HYPS_MAX_BINS in all
+static int hyps_check_offsets(const int64_t *offsets, int64_t nlab, int64_t *total)
+{
+    bool ok = offsets[0] == 0 && offsets[1] == 0;
+    for (int64_t l = 1; ok && l <= nlab; ++l) ok = offsets[l + 1] > offsets[l];
+    if (!ok || offsets[nlab + 1] > HYPS_MAX_BINS) {
+        set_error("offsets are no hypsometry layout of %lld labels (0, 0, then strictly increasing, at most 2**30 bins)", (long long)nlab);
+        return MHIP_EINVAL;
+    }
+    *total = offsets[nlab + 1];
+    return MHIP_OK;
+}
+
+int mhip_label_hyps_layout(const double *dmax, int64_t nlab, double res, int64_t *offsets, int64_t *total)
+{
+    MH_ARG(dmax && offsets && total && nlab >= 0 && hyps_res_ok(res), "label_hyps_layout(dmax, nlab>=0, 0 < res < inf, offsets, total)");
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    DevBuf d_m, d_o;
+    MH_TRY(upload(d_m, dmax, 8 * (size_t)(nlab + 1), s));
+    MH_TRY(d_o.alloc(8 * (size_t)(nlab + 2)));
+    MH_TRY(hyps_layout_dev(d_m.as<double>(), 1, nlab, res, d_o.as<int64_t>(), total, s));
+    return download(offsets, d_o, 8 * (size_t)(nlab + 2), s);
+}
+
+int mhip_label_hyps_f32(const float *data, const int32_t *labels, int64_t n, int64_t W, int64_t nlab, double res, const int64_t *offsets,
+                        int64_t *counts, double *sums, int64_t *lds_spills)
+{
+    MH_ARG(data && labels && offsets && counts && sums && n >= 1 && W >= 0 && nlab >= 0 && hyps_res_ok(res),
+           "label_hyps_f32(data, labels, n>=1, W>=0, nlab>=0, 0 < res < inf, offsets, counts, sums)");
+    int64_t total = 0;
+    MH_TRY(hyps_check_offsets(offsets, nlab, &total));
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    DevBuf d_d, d_l, d_o, d_c, d_s;
+    MH_TRY(upload(d_d, data, (size_t)n * 4, s));
+    MH_TRY(upload(d_l, labels, (size_t)n * 4, s));
+    MH_TRY(upload(d_o, offsets, 8 * (size_t)(nlab + 2), s));
+    MH_TRY(d_c.alloc(4 * (size_t)total));
+    MH_TRY(d_s.alloc(8 * (size_t)total));
+    MH_TRY(hyps_table_dev(d_d.as<float>(), d_l.as<int32_t>(), n, W, nlab, res, d_o.as<int64_t>(), total, d_c.as<uint32_t>(), d_s.as<double>(),
+                          lds_spills, s));
+    if (total == 0) return MHIP_OK;
+    std::vector<uint32_t> c32((size_t)total);
+    MH_HIP(hipMemcpyAsync(c32.data(), d_c.p, 4 * (size_t)total, hipMemcpyDeviceToHost, s));
+    MH_TRY(download(sums, d_s, 8 * (size_t)total, s));
+    for (int64_t k = 0; k < total; ++k) counts[k] = (int64_t)c32[(size_t)k];
+    return MHIP_OK;
+}
+
+int mhip_hyps_levels(int64_t nlab, const int64_t *offsets, const int64_t *counts, const double *sums, const double *dmax, const double *q,
+                     mhip_final_record *records)
+{
+    MH_ARG(offsets && counts && sums && dmax && q && records && nlab >= 0, "hyps_levels(nlab>=0, offsets, counts, sums, dmax, q, records)");
+    int64_t total = 0;
+    MH_TRY(hyps_check_offsets(offsets, nlab, &total));
+    std::vector<uint32_t> c32((size_t)total + 1);
+    for (int64_t k = 0; k < total; ++k) {
+        MH_ARG(counts[k] >= 0 && counts[k] < ((int64_t)1 << 31), "hyps_levels: a count outside [0, 2**31)");
+        c32[(size_t)k] = (uint32_t)counts[k];
+    }
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    DevBuf d_o, d_c, d_s, d_m, d_q, d_r;
+    MH_TRY(upload(d_o, offsets, 8 * (size_t)(nlab + 2), s));
+    MH_TRY(upload(d_c, c32.data(), 4 * ((size_t)total + 1), s));
+    MH_TRY(d_s.alloc(8 * (size_t)total));
+    if (total) MH_HIP(hipMemcpyAsync(d_s.p, sums, 8 * (size_t)total, hipMemcpyHostToDevice, s));
+    MH_TRY(upload(d_m, dmax, 8 * (size_t)(nlab + 1), s));
+    MH_TRY(upload(d_q, q, 8 * (size_t)(nlab + 1), s));
+    MH_TRY(d_r.alloc(sizeof(mhip_final_record) * (size_t)(nlab + 1)));
+    MH_TRY(hyps_levels_dev(nlab, d_o.as<int64_t>(), d_c.as<uint32_t>(), d_s.as<double>(), d_m.as<double>(), 1, d_q.as<double>(),
+                           d_r.as<mhip_final_record>(), s));
+    return download(records, d_r, sizeof(mhip_final_record) * (size_t)(nlab + 1), s);
+}
+
+int mhip_final_depths_f32(const float *data, const int32_t *labels, int64_t n, int64_t W, int64_t nlab, mhip_final_record *records, float *out)
+{
+    MH_ARG(data && labels && records && out && n >= 1 && W >= 0 && nlab >= 0, "final_depths_f32(data, labels, n>=1, W>=0, nlab>=0, records, out)");
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    std::vector<mhip_final_record> rec(records, records + nlab + 1);
+    for (auto &r : rec) r.wet_cells = 0;
+    DevBuf d_d, d_l, d_r, d_out;
+    MH_TRY(upload(d_d, data, (size_t)n * 4, s));
+    MH_TRY(upload(d_l, labels, (size_t)n * 4, s));
+    MH_TRY(upload(d_r, rec.data(), sizeof(mhip_final_record) * (size_t)(nlab + 1), s));
+    MH_TRY(d_out.alloc((size_t)n * 4));
+    MH_TRY(final_depths_dev(d_d.as<float>(), d_l.as<int32_t>(), n, W, nlab, d_r.as<mhip_final_record>(), d_out.as<float>(), s));
+    MH_HIP(hipMemcpyAsync(records, d_r.p, sizeof(mhip_final_record) * (size_t)(nlab + 1), hipMemcpyDeviceToHost, s));
+    return download(out, d_out, (size_t)n * 4, s);
+}
+
 int mhip_watersheds_i32(const uint8_t *flowdir, int32_t *labels, int64_t H, int64_t W, int32_t unassigned)
 {
     MH_ARG(flowdir && labels && H >= 1 && W >= 1, "watersheds_i32(flowdir, labels, H>=1, W>=1)");
@@ -561,6 +657,10 @@ struct mhip_ctx {
     int64_t nlabels_raw = -1, nlabels = -1;
     bool labels_components = false;   // LABELS came from the library's own labelling (not uploaded): 8-connected components
     bool labels_filtered = false;
+    bool stats_valid = false;         // `stats` are the label_stats of the resident DEPTHS by the resident LABELS
+    // hypsometry of the resident labels (mhip_ctx_hyps): layout, table, and the records of the last mhip_ctx_final_depths
+    DevBuf hyps_off, hyps_cnt, hyps_sum, hyps_rec;
+    int64_t hyps_total = -1, hyps_spills = 0;     // -1: no table of the resident depths and labels
     double sh = 0, dg = 0;
     int32_t fill_rounds = 0, noflat_rounds = 0;
     FillStats fill_st, noflat_st;
@@ -577,7 +677,8 @@ struct mhip_ctx {
 static size_t raster_elem(int which)
 {
     switch (which) {
-    case MHIP_R_DEM: case MHIP_R_FILLED: case MHIP_R_DEPTHS: case MHIP_R_LABELS: case MHIP_R_WATERSHEDS: case MHIP_R_NGDIST: return 4;
+    case MHIP_R_DEM: case MHIP_R_FILLED: case MHIP_R_DEPTHS: case MHIP_R_LABELS: case MHIP_R_WATERSHEDS: case MHIP_R_NGDIST:
+    case MHIP_R_FINALDEPTHS: return 4;
     case MHIP_R_NOFLAT: case MHIP_R_ACCUM: return 8;
     case MHIP_R_FLOWDIR: return 1;
     default: return 0;
@@ -590,6 +691,7 @@ static int ctx_raster(mhip_ctx *c, int which)
     return MHIP_OK;
 }
 
+constexpr int HYPS_KERNEL_SLOT = 1 << 29, FINAL_KERNEL_SLOT = 1 << 28;      // event pairs of single kernels (mhip_ctx_kernel_ms)
 static int ctx_events(mhip_ctx *c, int stage, hipEvent_t **a, hipEvent_t **b)
 {
     auto it = c->ev.find(stage);
@@ -738,6 +840,7 @@ int mhip_ctx_upload(mhip_ctx *c, int which, const void *host)
     if (which == MHIP_R_LABELS) { c->nlabels = -1; c->nlabels_raw = -1; c->labels_filtered = true; c->labels_components = false; }
     if (which == MHIP_R_FLOWDIR) c->nodir_valid = false;
     if (which == MHIP_R_FLOWDIR || which == MHIP_R_DEM || which == MHIP_R_ACCUM) c->acc_keep.valid = false;
+    if (which == MHIP_R_DEM || which == MHIP_R_DEPTHS || which == MHIP_R_LABELS) { c->stats_valid = false; c->hyps_total = -1; }
     return MHIP_OK;
 }
 
@@ -757,6 +860,7 @@ int mhip_ctx_upload_rows(mhip_ctx *c, int which, int64_t row0, int64_t nrows, co
         for (int k = 0; k < MHIP_R_COUNT_; ++k) c->have[k] = false;
     if (which == MHIP_R_DEM || which == MHIP_R_FILLED) c->fill_st.have_minmax = false;
     if (which == MHIP_R_FLOWDIR) c->nodir_valid = false;
+    if (which == MHIP_R_DEM || which == MHIP_R_DEPTHS || which == MHIP_R_LABELS) { c->stats_valid = false; c->hyps_total = -1; }
     MH_HIP(hipMemcpyAsync(c->r[which].as<char>() + rowb * (size_t)(c->ht + row0), host, rowb * (size_t)nrows, hipMemcpyHostToDevice, cs(c)));
     MH_HIP(stream_sync(cs(c)));      // the caller reuses its window buffer
     if (row0 + nrows == c->H_owned) {
@@ -1733,6 +1837,8 @@ static int stage_depths(mhip_ctx *c, hipStream_t s)
     MH_TRY(ctx_raster(c, MHIP_R_DEPTHS));
     MH_TRY(depths_dev(c->r[MHIP_R_FILLED].as<float>(), c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_DEPTHS].as<float>(), c->H * c->W, s));
     c->have[MHIP_R_DEPTHS] = true;
+    c->stats_valid = false;
+    c->hyps_total = -1;
     return MHIP_OK;
 }
 
@@ -1873,6 +1979,8 @@ static int stage_label(mhip_ctx *c, hipStream_t s)
     c->labels_components = true;
     c->labels_filtered = false;
     c->nlabels = c->nlabels_raw;
+    c->stats_valid = false;
+    c->hyps_total = -1;
     return MHIP_OK;
 }
 
@@ -2192,6 +2300,10 @@ int mhip_ctx_kernel_ms(mhip_ctx *c, const char *kernel, float *ms_total, int32_t
         *launches = REPS;
         return MHIP_OK;
     }
+    if (k == "hyps_table" || k == "final_depths") {      // events around the one kernel inside mhip_ctx_hyps / mhip_ctx_final_depths
+        *launches = 1;
+        return mhip_ctx_stage_ms(c, k == "hyps_table" ? HYPS_KERNEL_SLOT : FINAL_KERNEL_SLOT, ms_total);
+    }
     if (k == "fill_round") {
         *launches = c->fill_rounds;
         return mhip_ctx_stage_ms(c, MHIP_STAGE_FILL, ms_total);
@@ -2234,6 +2346,8 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "noflat_reject_unreached") *value = c->noflat_st.geo_unreached;
     else if (k == "noflat_reject_mismatch") *value = c->noflat_st.geo_mismatch;
     else if (k == "noflat_cycles") *value = c->noflat_st.cycles;
+    else if (k == "hyps_bins") *value = c->hyps_total;               // -1: no table (mhip_ctx_hyps)
+    else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
     else {
@@ -2296,6 +2410,8 @@ static int ctx_apply_keep_on(mhip_ctx *c, const uint8_t *keep, hipStream_t s)
                               hipMemcpyDeviceToDevice, s));
     }
     c->labels_filtered = true;
+    c->stats_valid = true;
+    c->hyps_total = -1;
     return MHIP_OK;
 }
 
@@ -2320,6 +2436,89 @@ int mhip_ctx_pourpoints(mhip_ctx *c, mhip_index_record *records)
     MH_ARG(c && records && c->pour.p, "ctx_pourpoints needs a POURPOINTS run");
     MH_HIP(hipMemcpyAsync(records, c->pour.p, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
     MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+/* ---- final state of the bluespots on the resident rasters (hyps.hip) ------------------------------------------------------ */
+int mhip_ctx_hyps(mhip_ctx *c, double res, int64_t *total)
+{
+    MH_ARG(c && total && hyps_res_ok(res), "ctx_hyps(ctx, 0 < res < inf, total)");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "hypsometry on a row band is not built (the tables of the bands add up: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_DEPTHS] && c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_hyps needs the DEPTHS and LABELS rasters");
+    MH_ARG(c->labels_filtered, "ctx_hyps needs mhip_ctx_apply_keep after the LABEL run");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t n = c->H * c->W;
+    c->hyps_total = -1;
+    if (!c->stats_valid) {       // uploaded rasters: the labels' largest depths first
+        MH_TRY(ctx_label_max(c, s));
+        MH_TRY(c->stats.alloc(sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1)));
+        MH_TRY(label_stats_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->nlabels, c->stats.as<mhip_stat_record>(), s,
+                               c->W, c->labels_components));
+        c->stats_valid = true;
+    }
+    const int64_t nlab = c->nlabels;
+    MH_TRY(c->hyps_off.alloc(8 * (size_t)(nlab + 2)));
+    hipEvent_t *e1, *k0, *k1;
+    MH_TRY(ctx_events(c, HYPS_KERNEL_SLOT, &k0, &k1));
+    MH_TRY(stage_begin(c, MHIP_STAGE_HYPS, s, &e1));
+    int64_t tot = 0;
+    MH_TRY(hyps_layout_dev(c->stats.as<double>() + 1, 4, nlab, res, c->hyps_off.as<int64_t>(), &tot, s));     // (`max` of mhip_stat_record)
+    MH_TRY(c->hyps_cnt.alloc(4 * (size_t)tot));
+    MH_TRY(c->hyps_sum.alloc(8 * (size_t)tot));
+    MH_TRY(hyps_table_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->W, nlab, res, c->hyps_off.as<int64_t>(), tot,
+                          c->hyps_cnt.as<uint32_t>(), c->hyps_sum.as<double>(), &c->hyps_spills, s, *k0, *k1));
+    MH_HIP(hipEventRecord(*e1, s));
+    c->ev_valid[MHIP_STAGE_HYPS] = true;
+    c->ev_valid[HYPS_KERNEL_SLOT] = true;
+    c->hyps_total = tot;
+    *total = tot;
+    return MHIP_OK;
+}
+
+int mhip_ctx_hyps_fetch(mhip_ctx *c, int64_t *offsets, int64_t *counts, double *sums)
+{
+    MH_ARG(c && offsets && counts && sums, "ctx_hyps_fetch(ctx, offsets, counts, sums)");
+    MH_ARG(c->hyps_total >= 0, "ctx_hyps_fetch needs mhip_ctx_hyps on the resident depths and labels");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t tot = (size_t)c->hyps_total;
+    std::vector<uint32_t> c32(tot + 1);
+    MH_HIP(hipMemcpyAsync(offsets, c->hyps_off.p, 8 * (size_t)(c->nlabels + 2), hipMemcpyDeviceToHost, s));
+    if (tot) {
+        MH_HIP(hipMemcpyAsync(c32.data(), c->hyps_cnt.p, 4 * tot, hipMemcpyDeviceToHost, s));
+        MH_HIP(hipMemcpyAsync(sums, c->hyps_sum.p, 8 * tot, hipMemcpyDeviceToHost, s));
+    }
+    MH_HIP(stream_sync(s));
+    for (size_t k = 0; k < tot; ++k) counts[k] = (int64_t)c32[k];
+    return MHIP_OK;
+}
+
+int mhip_ctx_final_depths(mhip_ctx *c, const double *q, mhip_final_record *records)
+{
+    MH_ARG(c && q && records, "ctx_final_depths(ctx, q, records)");
+    MH_ARG(c->hyps_total >= 0 && c->stats_valid, "ctx_final_depths needs mhip_ctx_hyps on the resident depths and labels");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t nlab = c->nlabels, n = c->H * c->W;
+    DevBuf d_q;
+    MH_TRY(upload(d_q, q, 8 * (size_t)(nlab + 1), s));
+    MH_TRY(c->hyps_rec.alloc(sizeof(mhip_final_record) * (size_t)(nlab + 1)));
+    MH_TRY(ctx_raster(c, MHIP_R_FINALDEPTHS));
+    c->have[MHIP_R_FINALDEPTHS] = false;
+    hipEvent_t *e1, *k0, *k1;
+    MH_TRY(ctx_events(c, FINAL_KERNEL_SLOT, &k0, &k1));
+    MH_TRY(stage_begin(c, MHIP_STAGE_FINALDEPTHS, s, &e1));
+    MH_TRY(hyps_levels_dev(nlab, c->hyps_off.as<int64_t>(), c->hyps_cnt.as<uint32_t>(), c->hyps_sum.as<double>(), c->stats.as<double>() + 1, 4,
+                           d_q.as<double>(), c->hyps_rec.as<mhip_final_record>(), s));
+    MH_TRY(final_depths_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->W, nlab, c->hyps_rec.as<mhip_final_record>(),
+                            c->r[MHIP_R_FINALDEPTHS].as<float>(), s, *k0, *k1));      // (synchronises: d_q goes back to the pool)
+    MH_HIP(hipEventRecord(*e1, s));
+    c->ev_valid[MHIP_STAGE_FINALDEPTHS] = true;
+    c->ev_valid[FINAL_KERNEL_SLOT] = true;
+    c->have[MHIP_R_FINALDEPTHS] = true;
+    MH_HIP(hipMemcpyAsync(records, c->hyps_rec.p, sizeof(mhip_final_record) * (size_t)(nlab + 1), hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
     return MHIP_OK;
 }
 

@@ -388,6 +388,19 @@ int label_arg_dev(const double *d_data, const int32_t *d_labels, int64_t H, int6
                   mhip_index_record *d_rec, hipStream_t s, bool components = false);
 int label_count_dev(const int32_t *d_labels, int64_t n, int64_t nlab, int64_t *d_counts, hipStream_t s, int64_t W = 0);
 int label_max_dev(const int32_t *d_labels, int64_t n, int32_t *out_max, hipStream_t s);
+// hyps.hip: hypsometry tables of the labels, water levels for given amounts, final-state depths.
+// Bins of label l are the table entries [offsets[l], offsets[l + 1]); MHIP_HYPS_MAX_BINS bounds offsets[nlab + 1].
+constexpr int64_t HYPS_MAX_BINS = (int64_t)1 << 30;   // keys of the tile tables are int32; counts + sums: 12 bytes a bin
+// dmax[l * stride]: the labels' largest depths (stride in doubles: 4 walks the `max` field of mhip_stat_record)
+int hyps_layout_dev(const double *d_dmax, int64_t stride, int64_t nlab, double res, int64_t *d_offsets, int64_t *total, hipStream_t s);
+// ev0 / ev1 (optional): recorded around the table kernel alone; *lds_spills: runs that found no slot in their tile's table
+int hyps_table_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t W, int64_t nlab, double res, const int64_t *d_offsets,
+                   int64_t total, uint32_t *d_counts, double *d_sums, int64_t *lds_spills, hipStream_t s, hipEvent_t ev0 = nullptr,
+                   hipEvent_t ev1 = nullptr);
+int hyps_levels_dev(int64_t nlab, const int64_t *d_offsets, const uint32_t *d_counts, const double *d_sums, const double *d_dmax, int64_t stride,
+                    const double *d_q, mhip_final_record *d_rec, hipStream_t s);
+int final_depths_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t W, int64_t nlab, mhip_final_record *d_rec, float *d_out,
+                     hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,
                    bool band_mode = false, const unsigned int *d_known_interior_nodir = nullptr, const int32_t *d_src = nullptr, PourLink *pour = nullptr);
@@ -398,7 +411,47 @@ int negative_lut_dev(int32_t *d_lab, int64_t n, const int32_t *d_lut, int64_t nl
 
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- tile geometry shared by the LDS-table kernels (label_ops.hip, hyps.hip) --------------------------------------
+// The raster (width W, n cells; a flat array is treated as 256 columns wide) is cut into tiles of TR rows x 256 columns;
+// a block owns a tile, its four wavefronts the four 64-column strips of every row.
+constexpr int TR = 32;
+struct TileGeom {
+    int64_t n, W;
+    int64_t ntr, ntc;
+};
+__host__ __device__ inline TileGeom tile_geom(int64_t n, int64_t W)
+{
+    TileGeom g;
+    g.n = n;
+    g.W = (W > 0 && n % W == 0) ? W : 256;
+    const int64_t H = cdiv(n, g.W);
+    g.ntr = cdiv(H, TR);
+    g.ntc = cdiv(g.W, 256);
+    return g;
+}
+// one block per tile up to 256 CUs x 8 blocks, then tile-stride
+inline unsigned tile_grid(const TileGeom &g)
+{
+    const int64_t nt = g.ntr * g.ntc;
+    return (unsigned)(nt < 2048 ? (nt > 0 ? nt : 1) : 2048);
+}
+
 #ifdef __HIPCC__
+// open-addressing slot of `key` in an LDS table of TS (power of two) slots, -1 when the probe limit is hit (the caller
+// then falls back to the global atomics); keys[] holds -1 for an empty slot
+template <int TS> __device__ __forceinline__ int table_slot(int *keys, int key)
+{
+    unsigned h = ((unsigned)key * 2654435761u) >> 7;
+#pragma unroll 1
+    for (int probe = 0; probe < 16; ++probe) {
+        h &= (unsigned)(TS - 1);
+        const int prev = atomicCAS(&keys[h], -1, key);
+        if (prev == -1 || prev == key) return (int)h;
+        ++h;
+    }
+    return -1;
+}
+
 // "Does any thread of the workgroup say yes?" with ONE barrier per call.  The library's __syncthreads_or is a reduction through 256
 // bytes of LDS of its own with two barriers; the loops that end on such a vote (pointer doubling, label-correcting sweeps) are
 // bound by exactly these barriers.  Three LDS words take turns: call n raises w[n % 3] in front of its barrier and reads it behind;

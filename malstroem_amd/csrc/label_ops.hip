@@ -77,40 +77,8 @@ __global__ __launch_bounds__(256) void stats_init_kernel(StatAcc a, int64_t nrec
     a.count[i] = 0ull;
 }
 
-// ---- tile geometry shared by the LDS-table kernels ----------------------------------------------------------------
-// The raster (width W, n cells; a flat array is treated as 256 columns wide) is cut into tiles of TR rows x 256 columns;
-// a block owns a tile, its four wavefronts the four 64-column strips of every row.
-constexpr int TR = 32;
-struct TileGeom {
-    int64_t n, W;
-    int64_t ntr, ntc;
-};
-__host__ __device__ inline TileGeom tile_geom(int64_t n, int64_t W)
-{
-    TileGeom g;
-    g.n = n;
-    g.W = (W > 0 && n % W == 0) ? W : 256;
-    const int64_t H = cdiv(n, g.W);
-    g.ntr = cdiv(H, TR);
-    g.ntc = cdiv(g.W, 256);
-    return g;
-}
-
-// open-addressing slot of `key` in an LDS table of TS (power of two) slots, -1 when the probe limit is hit (the caller
-// then falls back to the global atomics); keys[] holds -1 for an empty slot
-template <int TS> __device__ __forceinline__ int table_slot(int *keys, int key)
-{
-    unsigned h = ((unsigned)key * 2654435761u) >> 7;
-#pragma unroll 1
-    for (int probe = 0; probe < 16; ++probe) {
-        h &= (unsigned)(TS - 1);
-        const int prev = atomicCAS(&keys[h], -1, key);
-        if (prev == -1 || prev == key) return (int)h;
-        ++h;
-    }
-    return -1;
-}
-
+// (tile geometry and the LDS table's open addressing -- TR, TileGeom, tile_geom, table_slot, tile_grid -- live in common.hpp: hyps.hip
+// cuts the raster the same way)
 // A thread follows its column down the tile (32 rows x 256 columns per workgroup, four rows of loads in flight) and keeps the
 // VERTICAL run of equal labels it is in -- label, min, max, sum, count -- in registers; when the label changes the run goes to the
 // label's slot of the tile's LDS table, and the table leaves as one record per (label, tile).  Background cells go to registers
@@ -795,13 +763,6 @@ int check_bad(DevBuf &bad, hipStream_t s, const char *what)
 }
 
 }  // namespace
-
-// one block per tile up to 256 CUs x 8 blocks, then tile-stride
-static unsigned tile_grid(const TileGeom &g)
-{
-    const int64_t nt = g.ntr * g.ntc;
-    return (unsigned)(nt < 2048 ? (nt > 0 ? nt : 1) : 2048);
-}
 
 int label_stats_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t nlab, mhip_stat_record *d_rec,
                     hipStream_t s, int64_t W, bool components)

@@ -10,14 +10,17 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (INDEX_DTYPE, R_ACCUM, R_DEM, R_DEPTHS, R_FILLED, R_FLOWDIR, R_LABELS, R_NGDIST, R_NOFLAT, R_WATERSHEDS,
-                   RASTER_DTYPE, STAGE_ACCUM, STAGE_FILL, STAGE_FLOWDIR, STAGE_LABEL, STAGE_NOFLAT,
-                   STAGE_POURPOINTS, STAGE_WATERSHED, STAT_DTYPE)
+from ._lib import (FINAL_DTYPE, INDEX_DTYPE, R_ACCUM, R_DEM, R_DEPTHS, R_FILLED, R_FINALDEPTHS, R_FLOWDIR, R_LABELS, R_NGDIST, R_NOFLAT,
+                   R_WATERSHEDS, RASTER_DTYPE, STAGE_ACCUM, STAGE_FILL, STAGE_FINALDEPTHS, STAGE_FLOWDIR, STAGE_HYPS, STAGE_LABEL,
+                   STAGE_NOFLAT, STAGE_POURPOINTS, STAGE_WATERSHED, STAT_DTYPE)
 
 STAGES = {"fill": STAGE_FILL, "noflat": STAGE_NOFLAT, "flowdir": STAGE_FLOWDIR, "accum": STAGE_ACCUM,
           "label": STAGE_LABEL, "watershed": STAGE_WATERSHED, "pourpoints": STAGE_POURPOINTS}
+# timing slots of hypsometry() / final_depths() for stage_ms(); run() does not take them
+TIMED = dict(STAGES, hyps=STAGE_HYPS, finaldepths=STAGE_FINALDEPTHS)
 RASTERS = {"dem": R_DEM, "filled": R_FILLED, "depths": R_DEPTHS, "noflat": R_NOFLAT, "flowdir": R_FLOWDIR,
-           "accum": R_ACCUM, "labels": R_LABELS, "watersheds": R_WATERSHEDS, "ngdist": R_NGDIST}
+           "accum": R_ACCUM, "labels": R_LABELS, "watersheds": R_WATERSHEDS, "ngdist": R_NGDIST,
+           "finaldepths": R_FINALDEPTHS}
 
 
 class HydroPipeline(object):
@@ -104,7 +107,7 @@ class HydroPipeline(object):
 
     def stage_ms(self, stage):
         ms = ctypes.c_float(0)
-        _lib.call("mhip_ctx_stage_ms", self._ctx, STAGES[stage], ctypes.byref(ms))
+        _lib.call("mhip_ctx_stage_ms", self._ctx, TIMED[stage], ctypes.byref(ms))
         return ms.value
 
     def kernel_ms(self, family):
@@ -166,4 +169,37 @@ class HydroPipeline(object):
     def pourpoints(self):
         rec = np.zeros(self.get_int("nlabels") + 1, dtype=INDEX_DTYPE)
         _lib.call("mhip_ctx_pourpoints", self._ctx, _lib.ptr(rec))
+        return rec
+
+    # ---- final state of the bluespots (finalstate.py) ---------------------------------
+    def hypsometry(self, resolution):
+        """Build the hypsometry tables of the resident depths and (filtered or uploaded) labels at ``resolution`` metres; they stay
+        on the device for ``final_depths``.  Returns the number of bins."""
+        from .finalstate import check_resolution
+        total = ctypes.c_int64(0)
+        _lib.call("mhip_ctx_hyps", self._ctx, ctypes.c_double(check_resolution(resolution)), ctypes.byref(total))
+        return total.value
+
+    def hypsometry_tables(self):
+        """``(offsets, counts, sums)`` of the last ``hypsometry()``: bins of label ``l`` are ``[offsets[l], offsets[l + 1])``."""
+        total = self.get_int("hyps_bins")
+        if total < 0:
+            raise ValueError("hypsometry() has not been run on the resident depths and labels")
+        offsets = np.zeros(self.get_int("nlabels") + 2, dtype=np.int64)
+        counts = np.zeros(total, dtype=np.int64)
+        sums = np.zeros(total, dtype=np.float64)
+        _lib.call("mhip_ctx_hyps_fetch", self._ctx, _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(sums))
+        return offsets, counts, sums
+
+    def final_depths(self, q):
+        """Water level and final depths for ``q[l]`` cell-metres of water in bluespot ``l`` (``nlabels + 1`` entries, entry 0
+        ignored).  Returns the per-label records (``_lib.FINAL_DTYPE``); the raster is ``download("finaldepths")``."""
+        if self.get_int("hyps_bins") < 0:
+            raise ValueError("hypsometry() has not been run on the resident depths and labels")
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        n = self.get_int("nlabels")
+        if q.shape != (n + 1,):
+            raise ValueError("q must have nlabels + 1 = %d entries" % (n + 1))
+        rec = np.zeros(n + 1, dtype=FINAL_DTYPE)
+        _lib.call("mhip_ctx_final_depths", self._ctx, _lib.ptr(q), _lib.ptr(rec))
         return rec
