@@ -381,8 +381,8 @@ int mhip_ctx_upload_dem(mhip_ctx *ctx, const float *dem_band);       /* H_local 
 int mhip_ctx_upload(mhip_ctx *ctx, int which, const void *host);     /* any raster (for sub-commands) */
 int mhip_ctx_download(mhip_ctx *ctx, int which, void *host);         /* H_local x W */
 /* the same in row windows [row0, row0 + nrows) of the owned raster (the reference's io.py:21-159 moves whole rasters): a
- * streaming reader / writer keeps one window on the host whatever the raster's size; a raster counts as present once its
- * last row has arrived */
+ * streaming reader / writer keeps one window on the host whatever the raster's size; a raster counts as absent from its
+ * first window on and as present once its last row has arrived */
 int mhip_ctx_upload_rows(mhip_ctx *ctx, int which, int64_t row0, int64_t nrows, const void *host);
 int mhip_ctx_download_rows(mhip_ctx *ctx, int which, int64_t row0, int64_t nrows, void *host);
 int mhip_ctx_run(mhip_ctx *ctx, int stage_mask);                     /* asynchronous on the ctx stream */
@@ -405,7 +405,9 @@ int mhip_ctx_kernel_ms(mhip_ctx *ctx, const char *kernel, float *ms_total, int32
 int mhip_ctx_get_i64(mhip_ctx *ctx, const char *key, int64_t *value);
 int mhip_ctx_get_f64(mhip_ctx *ctx, const char *key, double *value);  /* "short", "diag" */
 /* label filter between MHIP_STAGE_LABEL and MHIP_STAGE_WATERSHED (reference bluespots.py:165-172):
- * download raw stats (nlabels_raw+1 records), decide on host, upload keep flags. */
+ * download raw stats (nlabels_raw+1 records), decide on host, upload keep flags.
+ * The three record getters (and mhip_ctx_band_fetch / _gather / _foreign_counts) return the records of the RESIDENT rasters or
+ * MHIP_EINVAL: a raster that was written again -- by a stage, an upload, a band call -- takes the records derived from it down. */
 int mhip_ctx_raw_stats(mhip_ctx *ctx, mhip_stat_record *records);
 int mhip_ctx_apply_keep(mhip_ctx *ctx, const uint8_t *keep);          /* NULL = keep all */
 int mhip_ctx_stats(mhip_ctx *ctx, mhip_stat_record *records);         /* nlabels+1, after apply_keep */

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/malstroem_hip.h"
 
@@ -19,6 +20,7 @@ const char *dev_env(const char *name);
 // hipStreamSynchronize with a short busy wait first: the round loops of the fills read a few words back every 16-32 launches and
 // the device idles while a sleeping host thread is woken (30-50 us per read-back; MALSTROEM_HIP_SPIN_US=0 turns the busy wait off)
 hipError_t stream_sync(hipStream_t s);
+int require_device();   // MHIP_ENODEV without a HIP device: there is no CPU fallback
 
 #define MH_HIP(expr)                                                                             \
     do {                                                                                         \
@@ -45,7 +47,7 @@ hipError_t stream_sync(hipStream_t s);
 
 // ---- device scratch buffer (RAII, stream-ordered free is not needed: all work is on one stream and
 //      we synchronise before releasing) ------------------------------------------------------------
-// Blocks come from a small caching pool (api.hip) so that the iterative stages and repeated pipeline runs do
+// Blocks come from a small caching pool (runtime.hip) so that the iterative stages and repeated pipeline runs do
 // not pay hipMalloc/hipFree (the latter synchronises the device) inside the hot path.
 int pool_alloc(void **p, size_t bytes);
 void pool_free(void *p, size_t bytes);
@@ -74,6 +76,16 @@ struct DevBuf {
     }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+
+// ---- host-layer helpers shared by the entry points (runtime.hip, api.hip, ctx*.hip) -------------------------------------
+int upload(DevBuf &b, const void *host, size_t bytes, hipStream_t s);           // alloc + asynchronous copy
+int download(void *host, const DevBuf &b, size_t bytes, hipStream_t s);         // copy + synchronise
+int64_t build_rank_lut(const uint8_t *keep, int64_t nlab, std::vector<int32_t> &lut);
+inline bool hyps_res_ok(double res) { return res > 0.0 && res <= 1.7976931348623157e308; }   // (false for NaN)
+// api.hip: the stream walk for a batch of cells over two rasters on the device (mhip_trace_downstream_i32, mhip_ctx_trace_downstream)
+int trace_on_device(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int64_t W, const int64_t *cells_rc, int64_t n, int use_bg,
+                    int32_t bg, int32_t *out_label, int32_t *out_found, int64_t *out_len, const int64_t *offsets, int64_t *out_cells,
+                    hipStream_t s);
 
 // ---- AGNPS direction codes (reference flow.py:30-38, deltas _flow.pyx:36-46) -------------------
 // code k: U 0, UR 1, R 2, DR 3, D 4, DL 5, L 6, UL 7, NODIR 8
@@ -225,7 +237,7 @@ struct PfRun {
     int publish_edges(hipStream_t s);
 };
 // a call-back fired once, on the stage's stream, at a chosen point of a stage (mhip_ctx_run starts the label branch when the
-// no-flats fill has left its throughput-bound first rounds: see api.hip)
+// no-flats fill has left its throughput-bound first rounds: see ctx_run.hip)
 struct StageHook {
     void (*fn)(void *, hipStream_t) = nullptr;
     void *arg = nullptr;

@@ -1,0 +1,538 @@
+// ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
+// getters, the per-label records, the label filter, hypsometry and final depths, and the one rule for what a write of a resident
+// raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
+#include <string>
+#include <vector>
+
+#include "ctx.hpp"
+
+namespace mh {
+
+static void drop_hyps(mhip_ctx *c)
+{
+    c->hyps_total = -1;
+    c->have[MHIP_R_FINALDEPTHS] = false;
+}
+
+void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
+{
+    switch (which) {
+    case MHIP_R_DEM:    // a new DEM invalidates everything derived from the previous one
+        for (int k = 0; k < MHIP_R_COUNT_; ++k) {
+            if (k == MHIP_R_DEM) continue;
+            c->have[k] = false;
+            ctx_wrote(c, k, true);
+        }
+        break;
+    case MHIP_R_FILLED:
+        if (uploaded) c->fill_st.have_minmax = false;      // (no flood of this context saw its DEM; the context's own fill sets the extremes)
+        break;
+    case MHIP_R_DEPTHS:
+        c->stats_valid = false;
+        drop_hyps(c);
+        break;
+    case MHIP_R_NOFLAT:
+        c->pour_valid = false;
+        break;
+    case MHIP_R_FLOWDIR:
+        c->nodir_valid = false;
+        c->acc_keep.valid = false;
+        break;
+    case MHIP_R_ACCUM:
+        c->acc_keep.valid = false;
+        c->pour_valid = false;
+        break;
+    case MHIP_R_LABELS:
+        c->nlabels = c->nlabels_raw = -1;
+        c->labels_components = false;
+        c->stats_valid = false;
+        c->ws_counts_valid = false;
+        c->pour_valid = false;
+        drop_hyps(c);
+        break;
+    case MHIP_R_WATERSHEDS:
+        c->ws_counts_valid = false;
+        break;
+    default:
+        break;
+    }
+}
+
+int ctx_fork_join_events(mhip_ctx *c)
+{
+    if (c->ev_fork) return MHIP_OK;
+    for (hipEvent_t *e : {&c->ev_flowdir, &c->ev_join, &c->ev_label, &c->ev_tail, &c->ev_fork}) MH_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return MHIP_OK;
+}
+
+int ctx_ensure_labels_final(mhip_ctx *c, hipStream_t s)
+{
+    if (!c->labels_filtered) return ctx_apply_keep_on(c, nullptr, s);
+    return MHIP_OK;
+}
+
+int ctx_label_max(mhip_ctx *c, hipStream_t s)
+{
+    if (c->nlabels < 0) {
+        int32_t m = 0;
+        MH_TRY(label_max_dev(c->r[MHIP_R_LABELS].as<int32_t>(), c->H * c->W, &m, s));
+        c->nlabels = m < 0 ? 0 : m;
+    }
+    return MHIP_OK;
+}
+
+int ctx_apply_keep_on(mhip_ctx *c, const uint8_t *keep, hipStream_t s)
+{
+    MH_ARG(c && c->have[MHIP_R_LABELS] && c->nlabels_raw >= 0 && !c->labels_filtered, "ctx_apply_keep needs a fresh LABEL run");
+    const int64_t n = c->H * c->W;
+    // a write of LABELS that renumbers them: the raw count stays known, and kept components stay components
+    const int64_t nraw = c->nlabels_raw;
+    const bool components = c->labels_components;
+    ctx_wrote(c, MHIP_R_LABELS);
+    c->nlabels_raw = nraw;
+    c->labels_components = components;
+    if (keep) {
+        std::vector<int32_t> lut;
+        c->nlabels = build_rank_lut(keep, c->nlabels_raw, lut);
+        DevBuf d_lut;
+        MH_TRY(d_lut.alloc(lut.size() * 4));
+        MH_HIP(hipMemcpyAsync(d_lut.p, lut.data(), lut.size() * 4, hipMemcpyHostToDevice, s));
+        MH_TRY(relabel_lut_dev(c->r[MHIP_R_LABELS].as<int32_t>(), d_lut.as<int32_t>(), c->nlabels_raw, n, s));
+        MH_TRY(c->stats.alloc(sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1)));
+        MH_TRY(label_stats_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->nlabels,
+                               c->stats.as<mhip_stat_record>(), s, c->W, c->labels_components));   // (kept components stay components)
+    } else {
+        // keep everything (background excluded by construction): labels and stats are the raw ones
+        c->nlabels = c->nlabels_raw;
+        MH_TRY(c->stats.alloc(sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1)));
+        MH_HIP(hipMemcpyAsync(c->stats.p, c->raw_stats.p, sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1),
+                              hipMemcpyDeviceToDevice, s));
+    }
+    c->labels_filtered = true;
+    c->stats_valid = true;
+    return MHIP_OK;
+}
+
+}  // namespace mh
+
+using namespace mh;
+
+extern "C" {
+
+int mhip_comm_available(void) { return comm_available(); }
+
+int mhip_comm_unique_id(void *id128)
+{
+    MH_ARG(id128, "comm_unique_id(id128)");
+    MH_TRY(require_device());
+    return comm_unique_id(id128);
+}
+
+int mhip_ctx_create_band(mhip_ctx **out, int64_t H_global, int64_t W, int64_t row0, int64_t H_local, int device, int rank,
+                         int nranks, const void *nccl_unique_id)
+{
+    MH_ARG(out && H_global >= 1 && W >= 1 && H_local >= 1 && row0 >= 0 && row0 + H_local <= H_global, "ctx_create_band geometry");
+    MH_ARG(rank >= 0 && nranks >= 1 && rank < nranks, "ctx_create_band(rank, nranks)");
+    MH_TRY(require_device());
+    MH_HIP(hipSetDevice(device));
+    void *comm = nullptr;
+    if (nccl_unique_id) MH_TRY(comm_create(&comm, nccl_unique_id, rank, nranks));   // collective over all bands
+    mhip_ctx *c = new mhip_ctx();
+    c->comm = comm;
+    c->ht = row0 > 0 ? 1 : 0;
+    c->hb = row0 + H_local < H_global ? 1 : 0;
+    c->H_owned = H_local;
+    c->H = H_local + c->ht + c->hb;
+    c->W = W; c->H_global = H_global; c->row0 = row0;
+    c->device = device; c->rank = rank; c->nranks = nranks;
+    // the main stream carries the critical path (fill -> no-flats -> D8 -> accumulation): highest priority; the label / watershed
+    // branch of mhip_ctx_run fills the gaps on streams of the lowest
+    int prio_least = 0, prio_greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    if (hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_greatest) != hipSuccess) {
+        comm_destroy(c->comm);
+        delete c;
+        set_error("hipStreamCreate failed");
+        return MHIP_EHIP;
+    }
+    *out = c;
+    return MHIP_OK;
+}
+
+int mhip_ctx_create(mhip_ctx **out, int64_t H, int64_t W, int device)
+{
+    return mhip_ctx_create_band(out, H, W, 0, H, device, 0, 1, nullptr);
+}
+
+int mhip_ctx_destroy(mhip_ctx *c)
+{
+    if (!c) return MHIP_OK;
+    (void)hipSetDevice(c->device);
+    (void)stream_sync(c->stream);
+    for (StageTimer &t : c->timers)
+        for (hipEvent_t e : {t.a, t.b})
+            if (e) (void)hipEventDestroy(e);
+    (void)hipStreamDestroy(c->stream);
+    for (hipStream_t st : {c->stream_b, c->stream_c}) {
+        if (st) {
+            (void)stream_sync(st);
+            (void)hipStreamDestroy(st);
+        }
+    }
+    for (hipEvent_t e : {c->ev_fork, c->ev_flowdir, c->ev_join, c->ev_label, c->ev_tail, c->ev_cand})
+        if (e) (void)hipEventDestroy(e);
+    delete c->geo;
+    delete c->pf;
+    delete c->run[0];
+    delete c->run[1];
+    comm_destroy(c->comm);
+    comm_destroy(c->comm_b);
+    delete c;
+    return MHIP_OK;
+}
+
+int mhip_ctx_comm_add_side(mhip_ctx *c, const void *nccl_unique_id)
+{
+    MH_ARG(c && nccl_unique_id && c->comm && !c->comm_b, "ctx_comm_add_side(ctx, id) needs a band context with a communicator and no side communicator yet");
+    MH_HIP(hipSetDevice(c->device));
+    return comm_create(&c->comm_b, nccl_unique_id, c->rank, c->nranks);     // collective over all bands
+}
+
+int mhip_ctx_side_begin(mhip_ctx *c)
+{
+    MH_ARG(c, "ctx");
+    MH_HIP(hipSetDevice(c->device));
+    if (!c->stream_b) MH_HIP(hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));      // (a higher or lower priority moves nothing: measured in round 4)
+    MH_TRY(ctx_fork_join_events(c));
+    MH_HIP(hipEventRecord(c->ev_fork, c->stream));          // everything the main stream has been given so far ...
+    MH_HIP(hipStreamWaitEvent(c->stream_b, c->ev_fork, 0));  // ... is visible to the side stream
+    t_side_ctx = c;
+    return MHIP_OK;
+}
+
+int mhip_ctx_side_end(mhip_ctx *c)
+{
+    MH_ARG(c && t_side_ctx == c, "ctx_side_end without ctx_side_begin on this thread");
+    MH_HIP(hipSetDevice(c->device));
+    MH_HIP(stream_sync(c->stream_b));
+    t_side_ctx = nullptr;
+    return MHIP_OK;
+}
+
+int mhip_ctx_upload(mhip_ctx *c, int which, const void *host)
+{
+    MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_, "ctx_upload(ctx, which, host)");
+    MH_HIP(hipSetDevice(c->device));
+    MH_TRY(ctx_raster(c, which));
+    ctx_wrote(c, which, /*uploaded=*/true);
+    const size_t rowb = raster_elem(which) * (size_t)c->W;
+    MH_HIP(hipMemcpyAsync(c->r[which].as<char>() + rowb * c->ht, host, rowb * (size_t)c->H_owned, hipMemcpyHostToDevice, cs(c)));
+    MH_HIP(stream_sync(cs(c)));
+    c->have[which] = true;
+    if (which == MHIP_R_LABELS) c->labels_filtered = true;      // (uploaded labels are final: their count is max(labels), taken when asked for)
+    return MHIP_OK;
+}
+
+int mhip_ctx_upload_dem(mhip_ctx *c, const float *dem) { return mhip_ctx_upload(c, MHIP_R_DEM, dem); }
+
+/* Windowed transfers (reference io.py:21-159 moves whole rasters through the host): rows [row0, row0 + nrows) of the OWNED
+ * raster.  Every window is a write of the raster (ctx_wrote, as mhip_ctx_upload); the raster counts as absent from the first
+ * window on and as present once its last row has been uploaded.  The host side needs one window, whatever the raster's size. */
+int mhip_ctx_upload_rows(mhip_ctx *c, int which, int64_t row0, int64_t nrows, const void *host)
+{
+    MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_ && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned,
+           "ctx_upload_rows(ctx, which, row0, nrows, host)");
+    MH_HIP(hipSetDevice(c->device));
+    MH_TRY(ctx_raster(c, which));
+    ctx_wrote(c, which, /*uploaded=*/true);
+    c->have[which] = false;
+    const size_t rowb = raster_elem(which) * (size_t)c->W;
+    MH_HIP(hipMemcpyAsync(c->r[which].as<char>() + rowb * (size_t)(c->ht + row0), host, rowb * (size_t)nrows, hipMemcpyHostToDevice, cs(c)));
+    MH_HIP(stream_sync(cs(c)));      // the caller reuses its window buffer
+    if (row0 + nrows == c->H_owned) {
+        c->have[which] = true;
+        if (which == MHIP_R_LABELS) c->labels_filtered = true;
+    }
+    return MHIP_OK;
+}
+
+int mhip_ctx_download_rows(mhip_ctx *c, int which, int64_t row0, int64_t nrows, void *host)
+{
+    MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_ && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned,
+           "ctx_download_rows(ctx, which, row0, nrows, host)");
+    MH_ARG(c->have[which], "raster has not been computed or uploaded");
+    MH_HIP(hipSetDevice(c->device));
+    const size_t rowb = raster_elem(which) * (size_t)c->W;
+    MH_HIP(hipMemcpyAsync(host, c->r[which].as<char>() + rowb * (size_t)(c->ht + row0), rowb * (size_t)nrows, hipMemcpyDeviceToHost, cs(c)));
+    MH_HIP(stream_sync(cs(c)));
+    return MHIP_OK;
+}
+
+int mhip_ctx_download(mhip_ctx *c, int which, void *host)
+{
+    MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_, "ctx_download(ctx, which, host)");
+    MH_ARG(c->have[which], "raster has not been computed or uploaded");
+    MH_HIP(hipSetDevice(c->device));
+    const size_t rowb = raster_elem(which) * (size_t)c->W;
+    MH_HIP(hipMemcpyAsync(host, c->r[which].as<char>() + rowb * c->ht, rowb * (size_t)c->H_owned, hipMemcpyDeviceToHost, cs(c)));
+    MH_HIP(stream_sync(cs(c)));
+    return MHIP_OK;
+}
+/* the same walk over the context's resident flow directions and (filtered) bluespot labels: no raster leaves the device */
+int mhip_ctx_trace_downstream(mhip_ctx *c, const int64_t *cells_rc, int64_t n, int use_background, int32_t background, int32_t *out_label,
+                              int32_t *out_found, int64_t *out_len, const int64_t *offsets, int64_t *out_cells)
+{
+    MH_ARG(c && n >= 0 && (n == 0 || cells_rc), "ctx_trace_downstream(ctx, cells, n, ...)");
+    MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_LABELS], "ctx_trace_downstream needs flow directions and labels");
+    MH_ARG(!c->ht && !c->hb, "stream tracing runs on an undivided raster");
+    if (n == 0) return MHIP_OK;
+    MH_HIP(hipSetDevice(c->device));
+    return trace_on_device(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_LABELS].as<int32_t>(), c->H, c->W, cells_rc, n, use_background,
+                           background, out_label, out_found, out_len, offsets, out_cells, c->stream);
+}
+
+int mhip_ctx_sync(mhip_ctx *c)
+{
+    MH_ARG(c, "ctx");
+    MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+int mhip_ctx_stage_ms(mhip_ctx *c, int stage, float *ms)
+{
+    MH_ARG(c && ms, "ctx_stage_ms(ctx, stage, ms)");
+    const int k = timer_slot(stage);
+    MH_ARG(k >= 0 && c->timers[k].valid, "stage has not been run");
+    MH_HIP(hipEventSynchronize(c->timers[k].b));
+    MH_HIP(hipEventElapsedTime(ms, c->timers[k].a, c->timers[k].b));
+    return MHIP_OK;
+}
+
+int mhip_ctx_kernel_ms(mhip_ctx *c, const char *kernel, float *ms_total, int32_t *launches)
+{
+    MH_ARG(c && kernel && ms_total && launches, "ctx_kernel_ms(ctx, kernel, ms, launches)");
+    const std::string k(kernel);
+    if (k == "d8") {
+        *launches = 1;
+        return mhip_ctx_stage_ms(c, MHIP_STAGE_FLOWDIR, ms_total);
+    }
+    if (k == "d8_steady") {
+        // steady-state throughput of the D8 stencil: 16 launches back to back between ONE pair of events on the context's stream
+        // (a pair of events around a single 0.43 ms launch adds ~30 us of bracket to it); the resident surface and directions
+        MH_ARG(c->have[MHIP_R_NOFLAT] && !c->ht && !c->hb, "d8_steady needs the no-flats surface on an undivided context");
+        MH_HIP(hipSetDevice(c->device));
+        MH_TRY(ctx_raster(c, MHIP_R_FLOWDIR));
+        MH_TRY(c->nodir_cnt.alloc(4));
+        constexpr int REPS = 16;
+        StageTimer *t;
+        MH_TRY(ctx_timer(c, D8_STEADY_SLOT, &t));
+        hipStream_t s = c->stream;
+        ctx_wrote(c, MHIP_R_FLOWDIR);
+        MH_HIP(hipMemsetAsync(c->nodir_cnt.p, 0, 4, s));
+        for (int i = 0; i < REPS + 2; ++i) {
+            if (i == 2) MH_HIP(hipEventRecord(t->a, s));      // (two untimed launches first)
+            MH_TRY(d8_dev(c->r[MHIP_R_NOFLAT].as<double>(), c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->H, c->W, 1, s, 0, c->H_global,
+                          c->nodir_cnt.as<unsigned int>()));
+        }
+        MH_HIP(hipEventRecord(t->b, s));
+        MH_HIP(hipEventSynchronize(t->b));
+        MH_HIP(hipEventElapsedTime(ms_total, t->a, t->b));
+        c->have[MHIP_R_FLOWDIR] = true;
+        c->nodir_valid = true;
+        *launches = REPS;
+        return MHIP_OK;
+    }
+    if (k == "hyps_table" || k == "final_depths") {      // events around the one kernel inside mhip_ctx_hyps / mhip_ctx_final_depths
+        *launches = 1;
+        return mhip_ctx_stage_ms(c, k == "hyps_table" ? HYPS_KERNEL_SLOT : FINAL_KERNEL_SLOT, ms_total);
+    }
+    if (k == "fill_round") {
+        *launches = c->fill_rounds;
+        return mhip_ctx_stage_ms(c, MHIP_STAGE_FILL, ms_total);
+    }
+    if (k == "noflat_round") {
+        *launches = c->noflat_rounds;
+        return mhip_ctx_stage_ms(c, MHIP_STAGE_NOFLAT, ms_total);
+    }
+    set_error("unknown kernel family '%s'", kernel);
+    return MHIP_EINVAL;
+}
+
+int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
+{
+    MH_ARG(c && key && value, "ctx_get_i64(ctx, key, value)");
+    const std::string k(key);
+    if (k == "nlabels_raw") *value = c->nlabels_raw;
+    else if (k == "nlabels") {
+        if (c->nlabels < 0 && c->have[MHIP_R_LABELS]) {   // labels came in by upload: their count is max(labelled), like the reference takes it
+            MH_HIP(hipSetDevice(c->device));
+            MH_TRY(ctx_label_max(c, c->stream));
+        }
+        *value = c->nlabels;
+    }
+    else if (k == "fill_rounds") *value = c->fill_rounds;
+    else if (k == "noflat_rounds") *value = c->noflat_rounds;
+    else if (k == "fill_visits") *value = c->fill_st.visits;
+    else if (k == "fill_cycles") *value = c->fill_st.cycles;
+    else if (k == "fill_tiles") *value = c->fill_st.tiles;
+    else if (k == "fill_algorithm") *value = c->fill_st.algorithm;   // 0 iterative tile schedule, 1 tiled priority-flood
+    else if (k == "fill_launches") *value = c->fill_st.rounds;
+    else if (k == "fill_hot_launches") *value = c->fill_st.hot_launches;
+    else if (k == "noflat_hot_launches") *value = c->noflat_st.hot_launches;
+    else if (k == "accum_algorithm") *value = c->accum_algorithm;   // 0 full accumulation, 1 a row band's second pass as a delta over the boundary pass's graph
+    else if (k == "pour_algorithm") *value = c->pour_algorithm;   // 0 a pass over values + labels (label_ops.hip), 1 keys out of the accumulation's final pass (PourLink)
+    else if (k == "noflat_algorithm") *value = c->noflat_st.algorithm;   // 0 float64 relaxation (fill.hip), 2 integer geodesic transform (noflat_geo.hip)
+    else if (k == "noflat_visits") *value = c->noflat_st.visits;
+    else if (k == "noflat_reject") *value = c->noflat_st.geo_reject;            // diagnostics: FillStats::geo_reject and its counts
+    else if (k == "noflat_reject_irregular") *value = c->noflat_st.geo_irregular;
+    else if (k == "noflat_reject_unreached") *value = c->noflat_st.geo_unreached;
+    else if (k == "noflat_reject_mismatch") *value = c->noflat_st.geo_mismatch;
+    else if (k == "noflat_cycles") *value = c->noflat_st.cycles;
+    else if (k == "hyps_bins") *value = c->hyps_total;               // -1: no table (mhip_ctx_hyps)
+    else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
+    else if (k == "H") *value = c->H;
+    else if (k == "W") *value = c->W;
+    else {
+        set_error("unknown key '%s'", key);
+        return MHIP_EINVAL;
+    }
+    return MHIP_OK;
+}
+
+int mhip_ctx_get_f64(mhip_ctx *c, const char *key, double *value)
+{
+    MH_ARG(c && key && value, "ctx_get_f64(ctx, key, value)");
+    const std::string k(key);
+    if (k == "short") *value = c->sh;
+    else if (k == "diag") *value = c->dg;
+    else if (k == "fill_hot_ms") *value = c->fill_st.hot_ms;          // pf_tile_kernel, HIP events around its launch
+    else if (k == "noflat_hot_ms") *value = c->noflat_st.hot_ms;      // the ng_round_kernel launches (span of the round loop)
+    else {
+        set_error("unknown key '%s'", key);
+        return MHIP_EINVAL;
+    }
+    return MHIP_OK;
+}
+
+int mhip_ctx_raw_stats(mhip_ctx *c, mhip_stat_record *records)
+{
+    MH_ARG(c && records && c->raw_stats.p && c->nlabels_raw >= 0, "ctx_raw_stats needs a LABEL run");
+    MH_HIP(hipMemcpyAsync(records, c->raw_stats.p, sizeof(mhip_stat_record) * (size_t)(c->nlabels_raw + 1), hipMemcpyDeviceToHost,
+                          c->stream));
+    MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+int mhip_ctx_apply_keep(mhip_ctx *c, const uint8_t *keep)
+{
+    MH_ARG(c, "ctx");
+    MH_HIP(hipSetDevice(c->device));
+    return ctx_apply_keep_on(c, keep, c->stream);
+}
+
+int mhip_ctx_stats(mhip_ctx *c, mhip_stat_record *records)
+{
+    MH_ARG(c && records && c->stats_valid && c->labels_filtered, "ctx_stats needs LABEL + apply_keep (or mhip_ctx_hyps) on the resident depths and labels");
+    MH_HIP(hipMemcpyAsync(records, c->stats.p, sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+int mhip_ctx_watershed_counts(mhip_ctx *c, int64_t *counts)
+{
+    MH_ARG(c && counts && c->ws_counts_valid, "ctx_watershed_counts needs a WATERSHED run on the resident labels");
+    MH_HIP(hipMemcpyAsync(counts, c->ws_counts.p, 8 * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+int mhip_ctx_pourpoints(mhip_ctx *c, mhip_index_record *records)
+{
+    MH_ARG(c && records && c->pour_valid, "ctx_pourpoints needs a POURPOINTS run on the resident labels and accumulated flow");
+    MH_HIP(hipMemcpyAsync(records, c->pour.p, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+/* ---- final state of the bluespots on the resident rasters (hyps.hip) ------------------------------------------------------ */
+int mhip_ctx_hyps(mhip_ctx *c, double res, int64_t *total)
+{
+    MH_ARG(c && total && hyps_res_ok(res), "ctx_hyps(ctx, 0 < res < inf, total)");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "hypsometry on a row band is not built (the tables of the bands add up: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_DEPTHS] && c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_hyps needs the DEPTHS and LABELS rasters");
+    MH_ARG(c->labels_filtered, "ctx_hyps needs mhip_ctx_apply_keep after the LABEL run");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t n = c->H * c->W;
+    c->hyps_total = -1;
+    if (!c->stats_valid) {       // uploaded rasters: the labels' largest depths first
+        MH_TRY(ctx_label_max(c, s));
+        MH_TRY(c->stats.alloc(sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1)));
+        MH_TRY(label_stats_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->nlabels, c->stats.as<mhip_stat_record>(), s,
+                               c->W, c->labels_components));
+        c->stats_valid = true;
+    }
+    const int64_t nlab = c->nlabels;
+    MH_TRY(c->hyps_off.alloc(8 * (size_t)(nlab + 2)));
+    StageTimer *k;
+    MH_TRY(ctx_timer(c, HYPS_KERNEL_SLOT, &k));
+    MH_TRY(stage_begin(c, MHIP_STAGE_HYPS, s));
+    int64_t tot = 0;
+    MH_TRY(hyps_layout_dev(c->stats.as<double>() + 1, 4, nlab, res, c->hyps_off.as<int64_t>(), &tot, s));     // (`max` of mhip_stat_record)
+    MH_TRY(c->hyps_cnt.alloc(4 * (size_t)tot));
+    MH_TRY(c->hyps_sum.alloc(8 * (size_t)tot));
+    MH_TRY(hyps_table_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->W, nlab, res, c->hyps_off.as<int64_t>(), tot,
+                          c->hyps_cnt.as<uint32_t>(), c->hyps_sum.as<double>(), &c->hyps_spills, s, k->a, k->b));
+    MH_TRY(stage_end(c, MHIP_STAGE_HYPS, s));
+    k->valid = true;
+    c->hyps_total = tot;
+    *total = tot;
+    return MHIP_OK;
+}
+
+int mhip_ctx_hyps_fetch(mhip_ctx *c, int64_t *offsets, int64_t *counts, double *sums)
+{
+    MH_ARG(c && offsets && counts && sums, "ctx_hyps_fetch(ctx, offsets, counts, sums)");
+    MH_ARG(c->hyps_total >= 0, "ctx_hyps_fetch needs mhip_ctx_hyps on the resident depths and labels");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t tot = (size_t)c->hyps_total;
+    std::vector<uint32_t> c32(tot + 1);
+    MH_HIP(hipMemcpyAsync(offsets, c->hyps_off.p, 8 * (size_t)(c->nlabels + 2), hipMemcpyDeviceToHost, s));
+    if (tot) {
+        MH_HIP(hipMemcpyAsync(c32.data(), c->hyps_cnt.p, 4 * tot, hipMemcpyDeviceToHost, s));
+        MH_HIP(hipMemcpyAsync(sums, c->hyps_sum.p, 8 * tot, hipMemcpyDeviceToHost, s));
+    }
+    MH_HIP(stream_sync(s));
+    for (size_t k = 0; k < tot; ++k) counts[k] = (int64_t)c32[k];
+    return MHIP_OK;
+}
+
+int mhip_ctx_final_depths(mhip_ctx *c, const double *q, mhip_final_record *records)
+{
+    MH_ARG(c && q && records, "ctx_final_depths(ctx, q, records)");
+    MH_ARG(c->hyps_total >= 0 && c->stats_valid, "ctx_final_depths needs mhip_ctx_hyps on the resident depths and labels");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t nlab = c->nlabels, n = c->H * c->W;
+    DevBuf d_q;
+    MH_TRY(upload(d_q, q, 8 * (size_t)(nlab + 1), s));
+    MH_TRY(c->hyps_rec.alloc(sizeof(mhip_final_record) * (size_t)(nlab + 1)));
+    MH_TRY(ctx_raster(c, MHIP_R_FINALDEPTHS));
+    c->have[MHIP_R_FINALDEPTHS] = false;
+    StageTimer *k;
+    MH_TRY(ctx_timer(c, FINAL_KERNEL_SLOT, &k));
+    MH_TRY(stage_begin(c, MHIP_STAGE_FINALDEPTHS, s));
+    MH_TRY(hyps_levels_dev(nlab, c->hyps_off.as<int64_t>(), c->hyps_cnt.as<uint32_t>(), c->hyps_sum.as<double>(), c->stats.as<double>() + 1, 4,
+                           d_q.as<double>(), c->hyps_rec.as<mhip_final_record>(), s));
+    MH_TRY(final_depths_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->W, nlab, c->hyps_rec.as<mhip_final_record>(),
+                            c->r[MHIP_R_FINALDEPTHS].as<float>(), s, k->a, k->b));      // (synchronises: d_q goes back to the pool)
+    MH_TRY(stage_end(c, MHIP_STAGE_FINALDEPTHS, s));
+    k->valid = true;
+    c->have[MHIP_R_FINALDEPTHS] = true;
+    MH_HIP(hipMemcpyAsync(records, c->hyps_rec.p, sizeof(mhip_final_record) * (size_t)(nlab + 1), hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
+}  // extern "C"

@@ -873,7 +873,7 @@ class HipBand(object):
 
     def ccl_begin(self):
         """ccl_local without its emit pass: the number of band-local labels; of the labels raster only the edge rows exist until
-        ``ccl_finish`` (csrc/api.hip: mhip_ctx_band_ccl_begin)"""
+        ``ccl_finish`` (csrc/ctx_band.hip: mhip_ctx_band_ccl_begin)"""
         n = ctypes.c_int64(0)
         _lib.call("mhip_ctx_band_ccl_begin", self._ctx, ctypes.byref(n))
         return int(n.value)
@@ -1795,7 +1795,7 @@ class BandPipeline(object):
                 raise (err + err_side)[0] if (err or err_side) else RuntimeError("another band failed in this phase of the chain")
 
         try:
-            # like the single-GPU DAG (csrc/api.hip, measured there): the no-flats fill has the GPU to itself -- its many small
+            # like the single-GPU DAG (csrc/ctx_run.hip, measured there): the no-flats fill has the GPU to itself -- its many small
             # launches queue behind the labelling's long workgroups otherwise -- then labelling + watersheds (the latter
             # need labels and flow directions) run next to D8 + accumulation.  (Round 4: the labelling beside the no-flats fill, as in
             # one context: the no-flats stage 29 -> 43 ms at 4 bands of 32768^2 on one GPU and the step 115.7 / 119.2 -> 114.7 / 118.5

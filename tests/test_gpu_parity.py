@@ -348,7 +348,7 @@ def test_tools_run_on_the_device_pipeline(alg, fx):
 
 @pytest.mark.parametrize("shape", [(700, 450), (1024, 1024), (1500, 1300)])
 def test_whole_chain_in_one_request_matches_oracle(alg, shape):
-    """mhip_ctx_run with every stage bit set takes the overlapped path of the stage DAG (api.hip): same bits as the
+    """mhip_ctx_run with every stage bit set takes the overlapped path of the stage DAG (ctx_run.hip): same bits as the
     oracle run stage by stage."""
     from malstroem_amd.pipeline import HydroPipeline
     dem = fbm(shape[0], shape[1], seed=7)
