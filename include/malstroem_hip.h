@@ -41,6 +41,8 @@ typedef struct { double value; int64_t row, col; } mhip_index_record;
  * [('drawdown','<f8'),('dmax_final','<f8'),('qmodel','<f8'),('wet_cells','<i8')]: water level below the spill level, largest
  * final depth, the amount the hypsometry table holds at that level (cell-metres), cells left with water */
 typedef struct { double drawdown, dmax_final, qmodel; int64_t wet_cells; } mhip_final_record;
+/* most rain events of one mhip_label_wet_at_f32 / mhip_ctx_wet_at call */
+#define MHIP_WETAT_MAX_EVENTS 16
 
 /* ---- library / device ------------------------------------------------------------------------- */
 const char *mhip_last_error(void);
@@ -131,6 +133,15 @@ int mhip_hyps_levels(int64_t nlab, const int64_t *offsets, const int64_t *counts
                      mhip_final_record *records);
 int mhip_final_depths_f32(const float *data, const int32_t *labels, int64_t n, int64_t W, int64_t nlab, mhip_final_record *records,
                           float *out);
+/* The rain of a series at which every cell gets wet, in one pass (no reference counterpart).  K events,
+ * 1 <= K <= MHIP_WETAT_MAX_EVENTS, in the order given: drawdown[K][nlab + 1] (event-major; row k = the `drawdown` column of event
+ * k's mhip_final_records) and values[K], the rain of each event -- finite, > 0 and strictly increasing, anything else is MHIP_EINVAL.
+ * A labelled cell is wet in event k when mhip_final_depths_f32 would leave water on it (double(d) - drawdown[k][label] > 0; a tie is
+ * dry, a NaN draw-down never wets); out = values[k] of the FIRST such k of the list (the draw-downs of a label need not fall with
+ * k), 0 when there is none and on background.  wet (optional): [K][nlab + 1] wet cells per event and label, whichever event came
+ * first -- the wet_cells of mhip_final_depths_f32 for every event at once; wet[k][0] = 0.  W: the raster's width (0: a flat array). */
+int mhip_label_wet_at_f32(const float *data, const int32_t *labels, int64_t n, int64_t W, int64_t nlab, int32_t K, const double *drawdown,
+                          const float *values, float *out, int64_t *wet);
 
 /* flow.watersheds_from_labels(flowdir, labelled, unassigned)  reference flow.py:398-412 ->
  * _flow.pyx:276-403. In place on labels. Terminates on flow cycles (reference does not). */
@@ -392,8 +403,9 @@ int mhip_ctx_trace_downstream(mhip_ctx *ctx, const int64_t *cells_rc, int64_t n,
                               int32_t *out_label, int32_t *out_found, int64_t *out_len, const int64_t *offsets, int64_t *out_cells);
 /* after mhip_ctx_sync: milliseconds (HIP events on the ctx stream) of `stage` (single bit) in the last run */
 int mhip_ctx_stage_ms(mhip_ctx *ctx, int stage, float *ms);
-/* milliseconds / launch count of one named kernel family in the last run ("d8", "fill_round", "noflat_round"; "hyps_table" and
- * "final_depths": the table kernel of the last mhip_ctx_hyps / the raster pass of the last mhip_ctx_final_depths alone);
+/* milliseconds / launch count of one named kernel family in the last run ("d8", "fill_round", "noflat_round"; "hyps_table",
+ * "final_depths" and "wet_at": the table kernel of the last mhip_ctx_hyps / the raster pass of the last mhip_ctx_final_depths /
+ * of the last mhip_ctx_wet_at alone);
  * "d8_steady" is a measurement of its own: it LAUNCHES the D8 stencil on the resident no-flats surface 16 times back to back
  * between one pair of events (steady-state throughput; an undivided context only) and returns their total */
 int mhip_ctx_kernel_ms(mhip_ctx *ctx, const char *kernel, float *ms_total, int32_t *launches);
@@ -421,6 +433,13 @@ int mhip_ctx_pourpoints(mhip_ctx *ctx, mhip_index_record *records);   /* nlabels
 int mhip_ctx_hyps(mhip_ctx *ctx, double res, int64_t *total);
 int mhip_ctx_hyps_fetch(mhip_ctx *ctx, int64_t *offsets, int64_t *counts, double *sums);
 int mhip_ctx_final_depths(mhip_ctx *ctx, const double *q, mhip_final_record *records);
+/* mhip_label_wet_at_f32 on the resident DEPTHS and LABELS, after mhip_ctx_hyps (an undivided context, like it): q[K][nlabels + 1]
+ * cell-metres and values[K] mm (the rule above) -> records[K][nlabels + 1], row k bit for bit what mhip_ctx_final_depths(ctx, q[k], .)
+ * returns (wet_cells included), from K runs of the levels and ONE pass over the rasters.  The raster stays in a buffer of the
+ * context (not a member of enum mhip_raster; MHIP_R_FINALDEPTHS is left alone) until DEPTHS or LABELS are written again;
+ * wet_at_rows copies rows [row0, row0 + nrows) of it.  mhip_ctx_get_i64 "wet_at_events": K of the raster held, -1: none. */
+int mhip_ctx_wet_at(mhip_ctx *ctx, int32_t K, const double *q, const float *values, mhip_final_record *records);
+int mhip_ctx_wet_at_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
 
 #ifdef __cplusplus
 }

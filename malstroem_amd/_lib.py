@@ -19,6 +19,8 @@ STAT_DTYPE = np.dtype([("min", "<f8"), ("max", "<f8"), ("sum", "<f8"), ("count",
 INDEX_DTYPE = np.dtype([("value", "<f8"), ("row", "<i8"), ("col", "<i8")])                    # _label.pyx:26-28
 FINAL_DTYPE = np.dtype([("drawdown", "<f8"), ("dmax_final", "<f8"), ("qmodel", "<f8"), ("wet_cells", "<i8")])   # mhip_final_record
 
+WETAT_MAX_EVENTS = 16     # MHIP_WETAT_MAX_EVENTS: most rain events of one wet_at call
+
 OK, EINVAL, EHIP, ENODEV, ELIMIT, ENOTCONV, ECOMM = 0, -1, -2, -3, -4, -5, -6
 
 STAGE_FILL, STAGE_NOFLAT, STAGE_FLOWDIR, STAGE_ACCUM = 1, 2, 4, 8
@@ -50,7 +52,7 @@ SYMBOLS = [
     "mhip_ctx_has_comm", "mhip_ctx_exchange_halo", "mhip_ctx_exchange_edge_rows", "mhip_ctx_comm_add_side", "mhip_band_union_find", "mhip_band_accum_pairs", "mhip_band_accum_solve", "mhip_band_label_pairs",
     "mhip_band_label_merge", "mhip_band_ws_publish", "mhip_band_ws_lut", "mhip_band_merge_records", "mhip_tg_create", "mhip_tg_destroy", "mhip_tg_barrier", "mhip_tg_allreduce_max", "mhip_tg_offer", "mhip_tg_take", "mhip_shm_barrier", "mhip_ctx_allreduce_max",
     "mhip_label_hyps_layout", "mhip_label_hyps_f32", "mhip_hyps_levels", "mhip_final_depths_f32", "mhip_ctx_hyps", "mhip_ctx_hyps_fetch",
-    "mhip_ctx_final_depths",
+    "mhip_ctx_final_depths", "mhip_label_wet_at_f32", "mhip_ctx_wet_at", "mhip_ctx_wet_at_rows",
 ]
 
 _lib = None

@@ -181,3 +181,41 @@ def final_depths(data, labelled, offsets, counts, sums, q, resolution):
     out = np.empty(data.shape, dtype=np.float32)
     _lib.call("mhip_final_depths_f32", _lib.ptr(data), _lib.ptr(lab), _lib.i64(lab.size), _lib.i64(width), _lib.i64(nlabels), _lib.ptr(rec), _lib.ptr(out))
     return out, rec
+
+
+def check_events(values):
+    """The rains of a ``wet_at`` series as a float32 array: 1 to ``_lib.WETAT_MAX_EVENTS`` values, finite, > 0 and strictly increasing
+    (as float32: what the raster holds); anything else raises ``ValueError``."""
+    v = np.asarray(values)
+    if v.ndim != 1 or v.dtype.kind not in "fiu":
+        raise ValueError("values: a one-dimensional sequence of numbers expected")
+    if not 1 <= v.size <= _lib.WETAT_MAX_EVENTS:
+        raise ValueError("wet_at takes 1 to %d events, got %d" % (_lib.WETAT_MAX_EVENTS, v.size))
+    with np.errstate(over="ignore"):
+        v = np.ascontiguousarray(v, dtype=np.float32)
+    if not (np.isfinite(v).all() and (v > 0).all() and (np.diff(v) > 0).all()):
+        raise ValueError("values must be finite, > 0 and strictly increasing (as float32), got %r" % (v.tolist(),))
+    return v
+
+
+def wet_at(data, labelled, drawdown, values):
+    """The rain of a series at which every cell gets wet: ``(raster float32, wet int64 [K, nlabels + 1])``.
+
+    ``drawdown``: float64 ``[K, nlabels + 1]``, row ``k`` the ``drawdown`` column of event ``k``'s ``final_depths`` records;
+    ``values``: the rain of each event, finite, > 0 and strictly increasing.  ``raster = values[k]`` of the first event of the list
+    in which ``final_depths`` leaves water on the cell (``float64(depth) - drawdown[k, label] > 0``), 0 where none does and on
+    background; ``wet[k, l]``: the cells of label ``l`` with water in event ``k`` (``wet_cells`` of that event's records)."""
+    data, lab, width = _depths(data, labelled)
+    vals = check_events(values)
+    t = np.asarray(drawdown)
+    if t.dtype != np.float64:
+        raise ValueError("dtype mismatch: float64 draw-downs expected, got '%s'" % t.dtype)
+    if t.ndim != 2 or t.shape[0] != vals.size or t.shape[1] < 1:
+        raise ValueError("drawdown must have the shape (K, nlabels + 1) with K = len(values) = %d, got %s" % (vals.size, t.shape))
+    t = np.ascontiguousarray(t)
+    nlabels = t.shape[1] - 1
+    out = np.empty(data.shape, dtype=np.float32)
+    wet = np.zeros(t.shape, dtype=np.int64)
+    _lib.call("mhip_label_wet_at_f32", _lib.ptr(data), _lib.ptr(lab), _lib.i64(lab.size), _lib.i64(width), _lib.i64(nlabels),
+              ctypes.c_int32(vals.size), _lib.ptr(t), _lib.ptr(vals), _lib.ptr(out), _lib.ptr(wet))
+    return out, wet

@@ -87,7 +87,7 @@ def parse_filter(filter):
 
 
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
-                finalstate=False, hyps_resolution=0.05):
+                finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -99,9 +99,15 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     ``finalstate``: also write, for every rain event, the raster of the water depths the event leaves behind
     (``finaldepths_<mm:g>.tif``; ``finalstate.FinalStateTool`` on the pipeline the bluespots were computed on, hypsometry tables at
     ``hyps_resolution`` metres) and the vector layer ``finalstate``: the events with water level, largest depth and wet area per
-    bluespot; the dict gains ``finalstate`` and ``finaldepths``.  Not on row bands yet."""
+    bluespot; the dict gains ``finalstate`` and ``finaldepths``.  Not on row bands yet.
+
+    ``onset`` (with ``finalstate``): also write ``wet_at.tif`` -- every cell holds the smallest rain of ``rain`` in mm that leaves
+    water on it, 0 (nodata) where none does; the dict gains ``wet_at``.  ``final_rasters=False`` (with ``finalstate``): no
+    ``finaldepths_<mm:g>.tif``; the ``finalstate`` layer is the same."""
     if vector:
         raise NotImplementedError("vectorisation of bluespots / watersheds (GDAL polygonize) is outside malstroem_amd's hot path")
+    if (onset or not final_rasters) and not finalstate:
+        raise ValueError("onset and final_rasters belong to the final state: pass finalstate=True")
     if comm is not None and comm.size > 1:
         if finalstate:
             raise NotImplementedError("finalstate on row bands: the hypsometry tables of the bands add up (counts and sums of a global "
@@ -157,9 +163,13 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                 written[tag] = os.path.join(outdir, 'finaldepths_{}.tif'.format(tag))
                 return io.RasterWriter(written[tag], tr, crs)
             final_writer = io.VectorWriter('GeoJSON', outvector, 'finalstate', None, None, crs)
+            onset_path = os.path.join(outdir, 'wet_at.tif')
             FinalStateTool(dem_reader, dem_reader, io.VectorReader(outvector, events_writer.layername), depths_writer_for, hyps_resolution,
-                           pipeline=pipe, device=device, output_eventdata=final_writer).process()
+                           pipeline=pipe, device=device, output_eventdata=final_writer,
+                           output_onset=io.RasterWriter(onset_path, tr, crs, 0) if onset else None, depth_rasters=final_rasters).process()
             res.update(finalstate=final_writer.filepath, finaldepths=written)
+            if onset:
+                res["wet_at"] = onset_path
     finally:
         pipe.close()
         dem_reader.close()

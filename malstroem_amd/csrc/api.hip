@@ -353,6 +353,27 @@ int mhip_final_depths_f32(const float *data, const int32_t *labels, int64_t n, i
     return download(out, d_out, (size_t)n * 4, s);
 }
 
+int mhip_label_wet_at_f32(const float *data, const int32_t *labels, int64_t n, int64_t W, int64_t nlab, int32_t K, const double *drawdown,
+                          const float *values, float *out, int64_t *wet)
+{
+    MH_ARG(data && labels && drawdown && values && out && n >= 1 && W >= 0 && nlab >= 0,
+           "label_wet_at_f32(data, labels, n>=1, W>=0, nlab>=0, K, drawdown, values, out, wet)");
+    MH_ARG(wet_at_events_ok(K, values), "label_wet_at_f32: 1 to 16 events whose values are finite, > 0 and strictly increasing");
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    const size_t nt = (size_t)K * (size_t)(nlab + 1);
+    DevBuf d_d, d_l, d_t, d_out, d_w;
+    MH_TRY(upload(d_d, data, (size_t)n * 4, s));
+    MH_TRY(upload(d_l, labels, (size_t)n * 4, s));
+    MH_TRY(upload(d_t, drawdown, 8 * nt, s));
+    MH_TRY(d_out.alloc((size_t)n * 4));
+    if (wet) MH_TRY(d_w.alloc(8 * nt));
+    MH_TRY(wet_at_dev(d_d.as<float>(), d_l.as<int32_t>(), n, W, nlab, K, d_t.as<double>(), 1, values, d_out.as<float>(),
+                      wet ? d_w.as<int64_t>() : nullptr, 1, s));
+    if (wet) MH_HIP(hipMemcpyAsync(wet, d_w.p, 8 * nt, hipMemcpyDeviceToHost, s));
+    return download(out, d_out, (size_t)n * 4, s);
+}
+
 int mhip_watersheds_i32(const uint8_t *flowdir, int32_t *labels, int64_t H, int64_t W, int32_t unassigned)
 {
     MH_ARG(flowdir && labels && H >= 1 && W >= 1, "watersheds_i32(flowdir, labels, H>=1, W>=1)");

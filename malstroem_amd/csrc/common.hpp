@@ -413,6 +413,13 @@ int hyps_levels_dev(int64_t nlab, const int64_t *d_offsets, const uint32_t *d_co
                     const double *d_q, mhip_final_record *d_rec, hipStream_t s);
 int final_depths_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t W, int64_t nlab, mhip_final_record *d_rec, float *d_out,
                      hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// wetat.hip: the first event of a rain series that wets each cell.  d_drawdown[(k * (nlab + 1) + l) * stride]: the
+// draw-down of label l in event k (stride 4 walks the `drawdown` field of K * (nlab + 1) mhip_final_records); values: HOST, the
+// rains; d_wet (optional) receives the wet cells per (event, label) at d_wet[(k * (nlab + 1) + l) * wet_stride].  Synchronises.
+bool wet_at_events_ok(int64_t K, const float *values);      // 1 <= K <= MHIP_WETAT_MAX_EVENTS; finite, > 0, strictly increasing
+int wet_at_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t W, int64_t nlab, int K, const double *d_drawdown, int64_t stride,
+               const float *values, float *d_out, int64_t *d_wet, int64_t wet_stride, hipStream_t s, hipEvent_t ev0 = nullptr,
+               hipEvent_t ev1 = nullptr);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,
                    bool band_mode = false, const unsigned int *d_known_interior_nodir = nullptr, const int32_t *d_src = nullptr, PourLink *pour = nullptr);

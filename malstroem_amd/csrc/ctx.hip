@@ -12,6 +12,8 @@ static void drop_hyps(mhip_ctx *c)
 {
     c->hyps_total = -1;
     c->have[MHIP_R_FINALDEPTHS] = false;
+    c->wetat_events = -1;      // (every call that fills the buffer has synchronised: nothing on the device still uses it)
+    c->wetat_out.release();
 }
 
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
@@ -346,6 +348,10 @@ int mhip_ctx_kernel_ms(mhip_ctx *c, const char *kernel, float *ms_total, int32_t
         *launches = 1;
         return mhip_ctx_stage_ms(c, k == "hyps_table" ? HYPS_KERNEL_SLOT : FINAL_KERNEL_SLOT, ms_total);
     }
+    if (k == "wet_at") {      // ... and around the raster pass of the last mhip_ctx_wet_at
+        *launches = 1;
+        return mhip_ctx_stage_ms(c, WETAT_KERNEL_SLOT, ms_total);
+    }
     if (k == "fill_round") {
         *launches = c->fill_rounds;
         return mhip_ctx_stage_ms(c, MHIP_STAGE_FILL, ms_total);
@@ -390,6 +396,7 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "noflat_cycles") *value = c->noflat_st.cycles;
     else if (k == "hyps_bins") *value = c->hyps_total;               // -1: no table (mhip_ctx_hyps)
     else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
+    else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
     else {
@@ -532,6 +539,48 @@ int mhip_ctx_final_depths(mhip_ctx *c, const double *q, mhip_final_record *recor
     c->have[MHIP_R_FINALDEPTHS] = true;
     MH_HIP(hipMemcpyAsync(records, c->hyps_rec.p, sizeof(mhip_final_record) * (size_t)(nlab + 1), hipMemcpyDeviceToHost, s));
     MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
+/* ---- the rain at which every cell gets wet (wetat.hip): K levels, one pass over the resident rasters ------------------------- */
+int mhip_ctx_wet_at(mhip_ctx *c, int32_t K, const double *q, const float *values, mhip_final_record *records)
+{
+    MH_ARG(c && q && values && records, "ctx_wet_at(ctx, K, q, values, records)");
+    MH_ARG(wet_at_events_ok(K, values), "ctx_wet_at: 1 to 16 events whose values are finite, > 0 and strictly increasing");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "wet_at on a row band is not built (it needs the bands' hypsometry tables: a later step); use an undivided context");
+    MH_ARG(c->hyps_total >= 0 && c->stats_valid, "ctx_wet_at needs mhip_ctx_hyps on the resident depths and labels");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t nlab = c->nlabels, n = c->H * c->W;
+    const size_t nt = (size_t)K * (size_t)(nlab + 1);
+    DevBuf d_q, d_rec;
+    MH_TRY(upload(d_q, q, 8 * nt, s));
+    MH_TRY(d_rec.alloc(sizeof(mhip_final_record) * nt));
+    c->wetat_events = -1;
+    MH_TRY(c->wetat_out.alloc(4 * (size_t)n));
+    StageTimer *k;
+    MH_TRY(ctx_timer(c, WETAT_KERNEL_SLOT, &k));
+    for (int32_t e = 0; e < K; ++e)
+        MH_TRY(hyps_levels_dev(nlab, c->hyps_off.as<int64_t>(), c->hyps_cnt.as<uint32_t>(), c->hyps_sum.as<double>(), c->stats.as<double>() + 1, 4,
+                               d_q.as<double>() + (size_t)e * (size_t)(nlab + 1), d_rec.as<mhip_final_record>() + (size_t)e * (size_t)(nlab + 1), s));
+    // the draw-downs out of the records' first field, the wet cells into their last (the levels left 0 there)
+    MH_TRY(wet_at_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->W, nlab, K, d_rec.as<double>(), 4, values,
+                      c->wetat_out.as<float>(), d_rec.as<int64_t>() + 3, 4, s, k->a, k->b));      // (synchronises)
+    k->valid = true;
+    c->wetat_events = K;
+    MH_HIP(hipMemcpyAsync(records, d_rec.p, sizeof(mhip_final_record) * nt, hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
+int mhip_ctx_wet_at_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
+{
+    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_wet_at_rows(ctx, row0, nrows, dst)");
+    MH_ARG(c->wetat_events > 0 && c->wetat_out.p, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels");
+    MH_HIP(hipSetDevice(c->device));
+    const size_t rowb = 4 * (size_t)c->W;
+    MH_HIP(hipMemcpyAsync(dst, c->wetat_out.as<char>() + rowb * (size_t)row0, rowb * (size_t)nrows, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(stream_sync(c->stream));
     return MHIP_OK;
 }
 

@@ -67,8 +67,8 @@ struct StageTimer {
     bool valid = false;     // the pair brackets a run that has been queued
 };
 constexpr int N_STAGE_BITS = 9;                                                           // MHIP_STAGE_FILL .. MHIP_STAGE_FINALDEPTHS
-constexpr int FINAL_KERNEL_SLOT = 1 << 28, HYPS_KERNEL_SLOT = 1 << 29, D8_STEADY_SLOT = 1 << 30;     // event pairs of single kernels
-constexpr int N_TIMERS = N_STAGE_BITS + 3;
+constexpr int WETAT_KERNEL_SLOT = 1 << 27, FINAL_KERNEL_SLOT = 1 << 28, HYPS_KERNEL_SLOT = 1 << 29, D8_STEADY_SLOT = 1 << 30;     // event pairs of single kernels
+constexpr int N_TIMERS = N_STAGE_BITS + 4;
 
 }  // namespace mh
 
@@ -108,6 +108,10 @@ struct mhip_ctx {
     // hypsometry of the resident labels (mhip_ctx_hyps): layout, table, and the records of the last mhip_ctx_final_depths
     mh::DevBuf hyps_off, hyps_cnt, hyps_sum, hyps_rec;
     int64_t hyps_total = -1, hyps_spills = 0;     // -1: no table of the resident depths and labels
+    // the raster of the last mhip_ctx_wet_at (float32, H x W; not a member of mhip_raster) and its number of events; -1: none.  It
+    // lives and dies with the tables (drop_hyps)
+    mh::DevBuf wetat_out;
+    int wetat_events = -1;
     double sh = 0, dg = 0;
     int32_t fill_rounds = 0, noflat_rounds = 0;
     mh::FillStats fill_st, noflat_st;
@@ -144,7 +148,8 @@ inline int timer_slot(int stage)      // -1: neither one stage bit nor a single-
 {
     for (int b = 0; b < N_STAGE_BITS; ++b)
         if (stage == 1 << b) return b;
-    return stage == FINAL_KERNEL_SLOT ? N_STAGE_BITS : stage == HYPS_KERNEL_SLOT ? N_STAGE_BITS + 1 : stage == D8_STEADY_SLOT ? N_STAGE_BITS + 2 : -1;
+    return stage == FINAL_KERNEL_SLOT ? N_STAGE_BITS : stage == HYPS_KERNEL_SLOT ? N_STAGE_BITS + 1 : stage == D8_STEADY_SLOT ? N_STAGE_BITS + 2 :
+           stage == WETAT_KERNEL_SLOT ? N_STAGE_BITS + 3 : -1;
 }
 inline int ctx_timer(mhip_ctx *c, int stage, StageTimer **t)
 {

@@ -70,10 +70,14 @@ class FinalStateTool(object):
     ``pipeline``: a ``HydroPipeline`` that still holds the depths and the filtered labels -- nothing is read or uploaded then.
     ``output_eventdata``: optional vector writer for the features with the added columns ``lvl_drawdown_<mm:g>`` (metres below
     the spill level), ``dmax_<mm:g>`` (largest final depth) and ``wetarea_<mm:g>``; ``process()`` returns them as well.
+    ``output_onset``: optional raster writer (``wet_at.tif``, nodata 0) for the map of the whole series: per cell the smallest
+    rain in mm of the series that leaves water on it, 0 where none does (the events are then taken in ascending mm,
+    which must be > 0 and distinct).  ``depth_rasters=False``: no depth raster per event is computed or written
+    (``output_depths_for_event`` is not called); the columns come from the same single pass and are identical.
     """
 
     def __init__(self, input_depths, input_labeled, input_eventdata, output_depths_for_event, resolution, pipeline=None, device=0,
-                 output_eventdata=None):
+                 output_eventdata=None, output_onset=None, depth_rasters=True):
         self.input_depths = input_depths
         self.input_labeled = input_labeled
         self.input_eventdata = input_eventdata
@@ -82,7 +86,27 @@ class FinalStateTool(object):
         self.pipeline = pipeline
         self.device = device
         self.output_eventdata = output_eventdata
+        self.output_onset = output_onset
+        self.depth_rasters = bool(depth_rasters)
         self.logger = logging.getLogger(__name__)
+
+    @staticmethod
+    def _event_q(features, tag, nlabels, cell_area):
+        """-> (q[nlabels + 1] cell-metres of event ``tag``, [(properties, bluespot id)] of the features that take its columns)"""
+        q = np.zeros(nlabels + 1, dtype=np.float64)        # bluespots absent from the layer hold no water
+        rows = []
+        for f in features:
+            p = f["properties"]
+            b = p.get("bspot_id")
+            if b is None or not 1 <= b <= nlabels:          # junction nodes; the background's pour point
+                continue
+            v = p.get("v_" + tag)
+            if p.get("pctv_" + tag) == 100:                 # full is full, whatever v / cell_area rounds to
+                q[b] = np.inf
+            else:
+                q[b] = 0.0 if v is None or v != v else v / cell_area
+            rows.append((p, b))
+        return q, rows
 
     def process(self):
         transform = self.input_depths.transform
@@ -103,27 +127,26 @@ class FinalStateTool(object):
             nbins = pipe.hypsometry(self.resolution)
             nlabels = pipe.get_int("nlabels")
             self.logger.info("{} bins for {} bluespots".format(nbins, nlabels))
-            for mm, tag in events:
+            series = None
+            if self.output_onset is not None or not self.depth_rasters:
+                # one pass for the whole series: the events in ascending rain, the records of all of them and the onset raster
+                events = sorted(events)
+                if events:
+                    qs = np.stack([self._event_q(features, tag, nlabels, cell_area)[0] for mm, tag in events])
+                    series = pipe.wet_at(qs, [mm for mm, tag in events])
+                    del qs
+            for k, (mm, tag) in enumerate(events):
                 self.logger.info("  {}mm".format(tag))
-                q = np.zeros(nlabels + 1, dtype=np.float64)        # bluespots absent from the layer hold no water
-                rows = []
-                for f in features:
-                    p = f["properties"]
-                    b = p.get("bspot_id")
-                    if b is None or not 1 <= b <= nlabels:          # junction nodes; the background's pour point
-                        continue
-                    v = p.get("v_" + tag)
-                    if p.get("pctv_" + tag) == 100:                 # full is full, whatever v / cell_area rounds to
-                        q[b] = np.inf
-                    else:
-                        q[b] = 0.0 if v is None or v != v else v / cell_area
-                    rows.append((p, b))
-                rec = pipe.final_depths(q)
+                q, rows = self._event_q(features, tag, nlabels, cell_area)
+                rec = pipe.final_depths(q) if self.depth_rasters else series[k]
                 for p, b in rows:
                     p["lvl_drawdown_" + tag] = float(rec["drawdown"][b])
                     p["dmax_" + tag] = float(rec["dmax_final"][b])
                     p["wetarea_" + tag] = float(rec["wet_cells"][b] * cell_area)
-                pipe.download_to("finaldepths", self.output_depths_for_event(tag))
+                if self.depth_rasters:
+                    pipe.download_to("finaldepths", self.output_depths_for_event(tag))
+            if self.output_onset is not None and series is not None:
+                pipe.download_wet_at_to(self.output_onset)
             if self.output_eventdata is not None:
                 self.output_eventdata.write_geojson_features(features)
             self.logger.info("Done")

@@ -203,3 +203,41 @@ class HydroPipeline(object):
         rec = np.zeros(n + 1, dtype=FINAL_DTYPE)
         _lib.call("mhip_ctx_final_depths", self._ctx, _lib.ptr(q), _lib.ptr(rec))
         return rec
+
+    # ---- the rain at which every cell gets wet ---------------------------------------
+    def wet_at(self, qs, values):
+        """``final_depths`` for the K events of a rain series at once, with ONE pass over the rasters: ``qs`` ``[K, nlabels + 1]``
+        cell-metres, ``values`` the rain of each event (finite, > 0, strictly increasing).  Returns the records ``[K, nlabels + 1]``
+        (row ``k``: what ``final_depths(qs[k])`` returns); the raster -- per cell the first rain of the list that leaves water on
+        it, 0 where none does -- stays on the device for ``download_wet_at`` / ``download_wet_at_to``."""
+        from .algorithms.label import check_events
+        vals = check_events(values)
+        if self.get_int("hyps_bins") < 0:
+            raise ValueError("hypsometry() has not been run on the resident depths and labels")
+        n = self.get_int("nlabels")
+        q = np.ascontiguousarray(qs, dtype=np.float64)
+        if q.shape != (vals.size, n + 1):
+            raise ValueError("qs must have the shape (K, nlabels + 1) = (%d, %d)" % (vals.size, n + 1))
+        rec = np.zeros((vals.size, n + 1), dtype=FINAL_DTYPE)
+        _lib.call("mhip_ctx_wet_at", self._ctx, ctypes.c_int32(vals.size), _lib.ptr(q), _lib.ptr(vals), _lib.ptr(rec))
+        return rec
+
+    def download_wet_at_rows(self, row0, nrows):
+        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
+        _lib.call("mhip_ctx_wet_at_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
+        return out
+
+    def download_wet_at(self):
+        """The raster of the last ``wet_at`` (float32); ``ValueError`` once the depths or labels it was made from are gone."""
+        return self.download_wet_at_rows(0, self.shape[0])
+
+    def download_wet_at_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        if hasattr(writer, "write_window"):
+            writer.open(self.shape, np.float32)
+            for row0 in range(0, self.shape[0], int(max_rows)):
+                n = min(int(max_rows), self.shape[0] - row0)
+                writer.write_window(row0, self.download_wet_at_rows(row0, n))
+            writer.close()
+        else:
+            writer.write(self.download_wet_at())
