@@ -147,6 +147,17 @@ int mhip_label_wet_at_f32(const float *data, const int32_t *labels, int64_t n, i
  * _flow.pyx:276-403. In place on labels. Terminates on flow cycles (reference does not). */
 int mhip_watersheds_i32(const uint8_t *flowdir, int32_t *labels_inout, int64_t H, int64_t W, int32_t unassigned);
 
+/* Flow distance to the receiving terminal and the longest flow path per label (no reference counterpart).  A cell is
+ * a terminal when its label is != 0, its code is > 7 or its downstream neighbour lies outside the raster; every other cell walks
+ * downstream to its first terminal over `no` orthogonal and `nd` diagonal steps.  labels == NULL: no cell is labelled.
+ * out_dist = float((double(no) + double(nd) * 1.4142135623730951) * scale), -1 for a cell whose walk never ends (a flow cycle);
+ * scale: the cell size, finite and > 0.  records (optional, nlab + 1): for label l the cell with the largest u = double(no) +
+ * double(nd) * sqrt2 among the cells whose terminal carries l (l = 0: an unlabelled terminal), compared in float64, the first in
+ * raster order among equals; value = u * scale; (-inf, -1, -1) where nothing competes.  With records a label outside [0, nlab] is
+ * MHIP_EINVAL.  unresolved (optional): the number of cells that hold -1. */
+int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, double scale, int64_t nlab, float *out_dist,
+                       mhip_index_record *records, int64_t *unresolved);
+
 /* net.next_downstream_label(flowdir, labeled, cell, background_label, geometry) for a BATCH of cells -- what
  * net.pourpoint_network / geometric_pourpoint_network loop over (reference net.py:142-192, 195-224).  cells_rc: n (row, col)
  * pairs.  Per cell: out_found = 1 and out_label = the first label on the downstream walk that differs from the start cell's
@@ -440,6 +451,13 @@ int mhip_ctx_final_depths(mhip_ctx *ctx, const double *q, mhip_final_record *rec
  * wet_at_rows copies rows [row0, row0 + nrows) of it.  mhip_ctx_get_i64 "wet_at_events": K of the raster held, -1: none. */
 int mhip_ctx_wet_at(mhip_ctx *ctx, int32_t K, const double *q, const float *values, mhip_final_record *records);
 int mhip_ctx_wet_at_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
+/* mhip_flow_distance on the resident FLOWDIR and (filtered or uploaded) LABELS of an undivided context, nlab = its "nlabels"; a row
+ * band is refused.  The raster and the records stay in buffers of the context (no member of enum mhip_raster) until FLOWDIR or LABELS
+ * are written again: flow_distance_rows copies rows [row0, row0 + nrows) of the raster, flow_distance_records the nlabels + 1
+ * records.  mhip_ctx_get_i64 "flow_distance_unresolved": the unresolved cells of the result held, -1: none. */
+int mhip_ctx_flow_distance(mhip_ctx *ctx, double scale, int64_t *unresolved);
+int mhip_ctx_flow_distance_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
+int mhip_ctx_flow_distance_records(mhip_ctx *ctx, mhip_index_record *records);
 
 #ifdef __cplusplus
 }

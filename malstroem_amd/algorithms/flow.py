@@ -4,6 +4,8 @@ Raster-wide stages (``terrain_flowdirection``, ``accumulated_flow``, ``watershed
 as HIP kernels; the per-cell helpers used by the stream-network code (``upstream_cells``,
 ``trace_downstream`` ...) are tiny host utilities on NumPy arrays.
 """
+import ctypes
+
 import numpy as np
 
 from .. import _lib
@@ -92,6 +94,45 @@ def watersheds_from_labels(flowdir, labelled, unassigned):
               int(unassigned))
     if work is not labelled:
         labelled[...] = work
+
+
+def check_cellsize(cellsize):
+    """The cell size of a flow distance as a float: finite and > 0 (``ValueError`` otherwise; nothing touches the library)."""
+    try:
+        v = float(cellsize)
+    except (TypeError, ValueError):
+        raise ValueError("cellsize must be a number, got %r" % (cellsize,))
+    if not (np.isfinite(v) and v > 0.0):
+        raise ValueError("cellsize must be finite and > 0, got %r" % (cellsize,))
+    return v
+
+
+def flow_distance(flowdir, labelled=None, cellsize=1.0, records=False):
+    """Distance along the flow path from every cell to the terminal it drains to -- the first labelled cell (``labelled != 0``), a cell
+    without direction, or the last cell before the path leaves the raster -- as float32 in units of ``cellsize`` (a diagonal step is
+    ``2**0.5`` cells); -1 where the walk never ends (a flow cycle).  No reference counterpart.
+
+    ``records=True``: ``(raster, records, unresolved)`` -- ``records[l]`` (``_lib.INDEX_DTYPE``, ``max(labelled) + 1`` entries) is the
+    head of the longest flow path among the cells whose terminal carries label ``l`` (``l = 0``: an unlabelled terminal): its length
+    and its cell, the first in raster order among equals; ``unresolved`` counts the cells that hold -1."""
+    scale = check_cellsize(cellsize)
+    fd = _flowdir(flowdir)
+    lab, nlab = None, 0
+    if labelled is not None:
+        lab = np.asarray(labelled)
+        if lab.shape != fd.shape:
+            raise ValueError("shape mismatch")
+        if lab.dtype != np.int32:
+            raise ValueError("Buffer dtype mismatch, expected 'int32' but got '%s'" % lab.dtype)
+        lab = np.ascontiguousarray(lab)
+    if lab is not None and records:
+        nlab = max(int(lab.max()), 0) if lab.size else 0
+    out = np.empty(fd.shape, dtype=np.float32)
+    rec = np.zeros(nlab + 1, dtype=_lib.INDEX_DTYPE) if records else None
+    unresolved = ctypes.c_int64(0)
+    _lib.call("mhip_flow_distance", _lib.ptr(fd), _lib.ptr(lab) if lab is not None else None, _lib.i64(fd.shape[0]), _lib.i64(fd.shape[1]),
+              ctypes.c_double(scale), _lib.i64(nlab), _lib.ptr(out), _lib.ptr(rec) if records else None, ctypes.byref(unresolved))
+    return (out, rec, unresolved.value) if records else out
 
 
 # ---- per-cell host helpers (reference flow.py:170-301), used by stream tracing and tests --------------

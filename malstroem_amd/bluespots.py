@@ -94,12 +94,17 @@ class BluespotTool(object):
     Same inputs/outputs as the reference.  ``pipeline``: an optional ``HydroPipeline`` left behind by
     ``DemTool.process(keep_pipeline=True)``; then nothing is re-read or recomputed (in particular the
     no-flats surface the reference computes a second time, bluespots.py:203-204, is reused).
+
+    ``output_flowlength_raster`` (no reference counterpart): a raster writer for ``flowlength.tif`` -- per cell the
+    distance in metres along the flow path to the bluespot it drains to (to the raster edge or a sink where it drains to none; nodata
+    -1 on a flow cycle).  Every pour point then also carries ``wshed_lfp``, the length in metres of the longest flow path of the
+    bluespot's local watershed, and ``lfp_row`` / ``lfp_col``, the cell that path starts at.  Without it the layer is unchanged.
     """
 
     def __init__(self, input_depths, input_flowdir, input_bluespot_filter_function,
                  output_labeled_raster, output_pourpoints, output_watersheds_raster,
                  input_accum=None, input_dem=None, output_labeled_vector=None, output_watersheds_vector=None,
-                 pipeline=None, device=0):
+                 pipeline=None, device=0, output_flowlength_raster=None):
         self.input_depths = input_depths
         self.input_flowdir = input_flowdir
         self.input_bluespot_filter_function = input_bluespot_filter_function
@@ -112,6 +117,7 @@ class BluespotTool(object):
         self.output_watersheds_vector = output_watersheds_vector
         self.pipeline = pipeline
         self.device = device
+        self.output_flowlength_raster = output_flowlength_raster
         assert self.input_accum or self.input_dem or pipeline, "Either input_dem or input_accum must be specified"
         if output_labeled_vector or output_watersheds_vector:
             raise NotImplementedError("vectorisation (GDAL polygonize) is outside malstroem_amd's hot path")
@@ -157,6 +163,14 @@ class BluespotTool(object):
             pp_pix = pipe.pourpoints()
             self.logger.info("Writing {} pour points".format(len(pp_pix)))
             pour_points = assemble_pourpoints(transform, pp_pix, bluespot_stats, watershed_stats)
+            if self.output_flowlength_raster:
+                self.logger.info("Calculating flow lengths")
+                unresolved = pipe.flow_distance(cell_width)
+                if unresolved:
+                    self.logger.warning("{} cells lie on or drain into a flow cycle: no flow length".format(unresolved))
+                pipe.download_flow_distance_to(self.output_flowlength_raster)
+                for feature, lfp in zip(pour_points, pipe.flow_distance_records()):
+                    feature['properties'].update(wshed_lfp=float(lfp['value']), lfp_row=int(lfp['row']), lfp_col=int(lfp['col']))
             self.output_pourpoints.write_geojson_features(dict(type="FeatureCollection", features=pour_points))
             self.logger.info("Done")
         finally:

@@ -87,7 +87,7 @@ def parse_filter(filter):
 
 
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
-                finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True):
+                finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -103,7 +103,11 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
 
     ``onset`` (with ``finalstate``): also write ``wet_at.tif`` -- every cell holds the smallest rain of ``rain`` in mm that leaves
     water on it, 0 (nodata) where none does; the dict gains ``wet_at``.  ``final_rasters=False`` (with ``finalstate``): no
-    ``finaldepths_<mm:g>.tif``; the ``finalstate`` layer is the same."""
+    ``finaldepths_<mm:g>.tif``; the ``finalstate`` layer is the same.
+
+    ``flowlength``: also write ``flowlength.tif`` -- per cell the distance in metres along the flow path to the bluespot it drains to
+    (nodata -1) -- and give every pour point ``wshed_lfp`` / ``lfp_row`` / ``lfp_col``, the longest flow path of its local watershed
+    (``BluespotTool(output_flowlength_raster=...)``); the dict gains ``flowlength``.  Not on row bands yet."""
     if vector:
         raise NotImplementedError("vectorisation of bluespots / watersheds (GDAL polygonize) is outside malstroem_amd's hot path")
     if (onset or not final_rasters) and not finalstate:
@@ -112,6 +116,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         if finalstate:
             raise NotImplementedError("finalstate on row bands: the hypsometry tables of the bands add up (counts and sums of a global "
                                       "label), which is not built yet; run it on one context")
+        if flowlength:
+            raise NotImplementedError("flowlength on row bands: a flow path crosses the seams between the bands, and the walk over "
+                                      "them is not built yet; run it on one context")
         return _process_all_bands(dem, outdir, rain, accum, filter, comm, device, nodatasubst, backend_factory)
     if not os.path.isdir(outdir) or os.listdir(outdir):
         raise ValueError("outdir isn't an empty directory")
@@ -137,9 +144,11 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         pourpoint_writer = io.VectorWriter('GeoJSON', outvector, 'pourpoints', None, None, crs)
         watershed_writer = io.RasterWriter(os.path.join(outdir, 'watersheds.tif'), tr, crs, 0)
         labeled_writer = io.RasterWriter(os.path.join(outdir, 'bluespots.tif'), tr, crs, 0)
+        flowlength_path = os.path.join(outdir, 'flowlength.tif')
         BluespotTool(input_depths=dem_reader, input_flowdir=dem_reader, input_bluespot_filter_function=filter_function,
                      input_accum=None, input_dem=dem_reader, output_labeled_raster=labeled_writer, output_pourpoints=pourpoint_writer,
-                     output_watersheds_raster=watershed_writer, pipeline=pipe, device=device).process()
+                     output_watersheds_raster=watershed_writer, pipeline=pipe, device=device,
+                     output_flowlength_raster=io.RasterWriter(flowlength_path, tr, crs, -1) if flowlength else None).process()
         nlabels = pipe.get_int("nlabels")
         # Process pourpoints: the walk runs on the resident flow directions and labels
         pourpoints_reader = io.VectorReader(outvector, pourpoint_writer.layername)
@@ -154,6 +163,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         RainTool(nodes_reader, events_writer, rain).process()
         res = dict(outdir=outdir, vector=outvector, nlabels=nlabels, events=events_writer.filepath,
                    nodes=nodes_writer.filepath, streams=streams_writer.filepath, pourpoints=pourpoint_writer.filepath)
+        if flowlength:
+            res["flowlength"] = flowlength_path
         if finalstate:
             # Final state of every event: the depths and the filtered labels are still on the device
             from .finalstate import FinalStateTool

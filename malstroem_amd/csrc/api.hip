@@ -1,6 +1,6 @@
 // api.hip -- the host-raster entry points of libmalstroem_hip.so (declared in include/malstroem_hip.h): upload -> stage -> download,
 // one per malstroem.algorithms stage function, over the device-pointer stage implementations (fill.hip, d8.hip, accum.hip, ccl.hip,
-// label_ops.hip, hyps.hip, watershed.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
+// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
 #include <vector>
 
 #include "common.hpp"
@@ -385,6 +385,25 @@ int mhip_watersheds_i32(const uint8_t *flowdir, int32_t *labels, int64_t H, int6
     MH_TRY(upload(d_l, labels, n * 4, s));
     MH_TRY(watersheds_dev(d_fd.as<uint8_t>(), d_l.as<int32_t>(), H, W, unassigned, s));
     return download(labels, d_l, n * 4, s);
+}
+
+int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, double scale, int64_t nlab, float *out_dist,
+                       mhip_index_record *records, int64_t *unresolved)
+{
+    MH_ARG(flowdir && out_dist && H >= 1 && W >= 1 && nlab >= 0, "flow_distance(flowdir, labels, H>=1, W>=1, scale, nlab>=0, out, records, unresolved)");
+    MH_ARG(flow_distance_scale_ok(scale), "flow_distance: the scale must be finite and > 0");
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    const size_t n = (size_t)(H * W);
+    DevBuf d_fd, d_l, d_out, d_rec;
+    MH_TRY(upload(d_fd, flowdir, n, s));
+    if (labels) MH_TRY(upload(d_l, labels, n * 4, s));
+    MH_TRY(d_out.alloc(n * 4));
+    if (records) MH_TRY(d_rec.alloc(sizeof(mhip_index_record) * (size_t)(nlab + 1)));
+    MH_TRY(flow_distance_dev(d_fd.as<uint8_t>(), labels ? d_l.as<int32_t>() : nullptr, H, W, scale, nlab, d_out.as<float>(),
+                             records ? d_rec.as<mhip_index_record>() : nullptr, unresolved, s));
+    if (records) MH_HIP(hipMemcpyAsync(records, d_rec.p, sizeof(mhip_index_record) * (size_t)(nlab + 1), hipMemcpyDeviceToHost, s));
+    return download(out_dist, d_out, n * 4, s);
 }
 
 int mhip_trace_downstream_i32(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, const int64_t *cells_rc, int64_t n,

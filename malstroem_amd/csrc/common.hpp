@@ -420,6 +420,12 @@ bool wet_at_events_ok(int64_t K, const float *values);      // 1 <= K <= MHIP_WE
 int wet_at_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t W, int64_t nlab, int K, const double *d_drawdown, int64_t stride,
                const float *values, float *d_out, int64_t *d_wet, int64_t wet_stride, hipStream_t s, hipEvent_t ev0 = nullptr,
                hipEvent_t ev1 = nullptr);
+// flowdist.hip: flow distance to the receiving terminal (float32 raster, -1 where a walk never ends) and, with d_rec (nlab + 1
+// records), the head of the longest flow path per label of the terminal.  d_lab may be nullptr: no cell is labelled.
+// Synchronises.  MHIP_EINVAL: with d_rec, a label outside [0, nlab].
+bool flow_distance_scale_ok(double scale);      // finite and > 0
+int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int64_t W, double scale, int64_t nlab, float *d_out, mhip_index_record *d_rec,
+                      int64_t *unresolved, hipStream_t s);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,
                    bool band_mode = false, const unsigned int *d_known_interior_nodir = nullptr, const int32_t *d_src = nullptr, PourLink *pour = nullptr);
@@ -456,6 +462,37 @@ inline unsigned tile_grid(const TileGeom &g)
 }
 
 #ifdef __HIPCC__
+// ---- the D8 forest in 64 x 64 tiles, shared by the watersheds and the flow distance (watershed.hip, flowdist.hip) -------------
+// the cell downstream of cell i, -1 when it has no direction (a code > 7) or the step leaves the raster
+__device__ __forceinline__ int64_t downstream(const uint8_t *fd, int64_t i, int64_t H, int64_t W)
+{
+    const unsigned code = fd[i];
+    if (code > 7u) return -1;
+    const int64_t r = i / W, c = i - r * W;
+    const int64_t nr = r + dir_dr((int)code), nc = c + dir_dc((int)code);
+    if (nr < 0 || nr >= H || nc < 0 || nc >= W) return -1;
+    return nr * W + nc;
+}
+constexpr int WS_TILE = 64;
+// The perimeter cells of the tiles -- the only cells a path can ENTER a tile at -- also live in a compact array, 256 slots per tile
+// (1 KB: the jumps over the entry cells gather there instead of in the raster, where a tile's left / right columns cost a
+// sector per cell: 8.7 B per raster cell for 6 % of the cells).  slot: top row, bottom row, left column, right column.
+__device__ __forceinline__ int ws_perim_slot(int lr, int lc)
+{
+    if (lr == 0) return lc;
+    if (lr == WS_TILE - 1) return WS_TILE + lc;
+    if (lc == 0) return 2 * WS_TILE + (lr - 1);
+    if (lc == WS_TILE - 1) return 2 * WS_TILE + (WS_TILE - 2) + (lr - 1);
+    return -1;
+}
+// the node of an entry cell; -1 for a cell inside its tile (a pointer caught in a flow cycle: it never resolves)
+__device__ __forceinline__ int64_t ws_node_of(int32_t cell, uint32_t W, int ntc)
+{
+    const uint32_t r = (uint32_t)cell / W, c = (uint32_t)cell - r * W;
+    const int slot = ws_perim_slot((int)(r & 63u), (int)(c & 63u));
+    return slot < 0 ? -1 : (int64_t)((r >> 6) * (uint32_t)ntc + (c >> 6)) * 256 + slot;
+}
+
 // open-addressing slot of `key` in an LDS table of TS (power of two) slots, -1 when the probe limit is hit (the caller
 // then falls back to the global atomics); keys[] holds -1 for an empty slot
 template <int TS> __device__ __forceinline__ int table_slot(int *keys, int key)

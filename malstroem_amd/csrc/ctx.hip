@@ -1,6 +1,7 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
 // getters, the per-label records, the label filter, hypsometry and final depths, and the one rule for what a write of a resident
 // raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -14,6 +15,14 @@ static void drop_hyps(mhip_ctx *c)
     c->have[MHIP_R_FINALDEPTHS] = false;
     c->wetat_events = -1;      // (every call that fills the buffer has synchronised: nothing on the device still uses it)
     c->wetat_out.release();
+}
+
+static void drop_flow_distance(mhip_ctx *c)
+{
+    std::lock_guard<std::mutex> lk(c->fdist_mu);
+    c->fdist_unresolved = -1;      // (the call that fills the buffers has synchronised: nothing on the device still uses them)
+    c->fdist_out.release();
+    c->fdist_rec.release();
 }
 
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
@@ -39,6 +48,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
     case MHIP_R_FLOWDIR:
         c->nodir_valid = false;
         c->acc_keep.valid = false;
+        drop_flow_distance(c);
         break;
     case MHIP_R_ACCUM:
         c->acc_keep.valid = false;
@@ -51,6 +61,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
         c->ws_counts_valid = false;
         c->pour_valid = false;
         drop_hyps(c);
+        drop_flow_distance(c);
         break;
     case MHIP_R_WATERSHEDS:
         c->ws_counts_valid = false;
@@ -397,6 +408,7 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "hyps_bins") *value = c->hyps_total;               // -1: no table (mhip_ctx_hyps)
     else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
     else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels
+    else if (k == "flow_distance_unresolved") *value = c->fdist_unresolved;   // -1: no result of mhip_ctx_flow_distance on the resident flow directions and labels
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
     else {
@@ -580,6 +592,50 @@ int mhip_ctx_wet_at_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
     MH_HIP(hipSetDevice(c->device));
     const size_t rowb = 4 * (size_t)c->W;
     MH_HIP(hipMemcpyAsync(dst, c->wetat_out.as<char>() + rowb * (size_t)row0, rowb * (size_t)nrows, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+/* ---- flow distance to the receiving bluespot, longest flow path per watershed (flowdist.hip) ------------------------------------ */
+int mhip_ctx_flow_distance(mhip_ctx *c, double scale, int64_t *unresolved)
+{
+    MH_ARG(c && unresolved, "ctx_flow_distance(ctx, scale, unresolved)");
+    MH_ARG(flow_distance_scale_ok(scale), "ctx_flow_distance: the scale must be finite and > 0");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "flow distance on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_flow_distance needs the FLOWDIR and LABELS rasters");
+    MH_ARG(c->labels_filtered, "ctx_flow_distance needs mhip_ctx_apply_keep after the LABEL run");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    MH_TRY(ctx_label_max(c, s));
+    const int64_t nlab = c->nlabels, n = c->H * c->W;
+    drop_flow_distance(c);
+    MH_TRY(c->fdist_out.alloc(4 * (size_t)n));
+    MH_TRY(c->fdist_rec.alloc(sizeof(mhip_index_record) * (size_t)(nlab + 1)));
+    int64_t u = 0;
+    MH_TRY(flow_distance_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_LABELS].as<int32_t>(), c->H, c->W, scale, nlab, c->fdist_out.as<float>(),
+                             c->fdist_rec.as<mhip_index_record>(), &u, s));      // (synchronises)
+    c->fdist_unresolved = u;
+    *unresolved = u;
+    return MHIP_OK;
+}
+
+int mhip_ctx_flow_distance_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
+{
+    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_flow_distance_rows(ctx, row0, nrows, dst)");
+    MH_ARG(c->fdist_unresolved >= 0 && c->fdist_out.p, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels");
+    MH_HIP(hipSetDevice(c->device));
+    const size_t rowb = 4 * (size_t)c->W;
+    MH_HIP(hipMemcpyAsync(dst, c->fdist_out.as<char>() + rowb * (size_t)row0, rowb * (size_t)nrows, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(stream_sync(c->stream));
+    return MHIP_OK;
+}
+
+int mhip_ctx_flow_distance_records(mhip_ctx *c, mhip_index_record *records)
+{
+    MH_ARG(c && records, "ctx_flow_distance_records(ctx, records)");
+    MH_ARG(c->fdist_unresolved >= 0 && c->fdist_rec.p, "ctx_flow_distance_records needs mhip_ctx_flow_distance on the resident flow directions and labels");
+    MH_HIP(hipSetDevice(c->device));
+    MH_HIP(hipMemcpyAsync(records, c->fdist_rec.p, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
     MH_HIP(stream_sync(c->stream));
     return MHIP_OK;
 }

@@ -112,6 +112,12 @@ struct mhip_ctx {
     // lives and dies with the tables (drop_hyps)
     mh::DevBuf wetat_out;
     int wetat_events = -1;
+    // the raster (float32, H x W; not a member of mhip_raster) and the records of the last mhip_ctx_flow_distance, and its number of
+    // unresolved cells; -1: none.  They live and die with FLOWDIR and LABELS, which the two host threads of a request may write at
+    // the same time: the buffers are handed back under the lock
+    mh::DevBuf fdist_out, fdist_rec;
+    std::atomic<int64_t> fdist_unresolved{-1};
+    std::mutex fdist_mu;
     double sh = 0, dg = 0;
     int32_t fill_rounds = 0, noflat_rounds = 0;
     mh::FillStats fill_st, noflat_st;

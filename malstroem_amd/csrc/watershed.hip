@@ -26,16 +26,6 @@ namespace {
 constexpr int32_t NONE = 0x7fffffff;
 constexpr uint32_t QFLAG = 0x80000000u, QMASK = 0x7fffffffu, QTERM = 0x7fffffffu;
 
-__device__ __forceinline__ int64_t downstream(const uint8_t *fd, int64_t i, int64_t H, int64_t W)
-{
-    const unsigned code = fd[i];
-    if (code > 7u) return -1;
-    const int64_t r = i / W, c = i - r * W;
-    const int64_t nr = r + dir_dr((int)code), nc = c + dir_dc((int)code);
-    if (nr < 0 || nr >= H || nc < 0 || nc >= W) return -1;
-    return nr * W + nc;
-}
-
 // (16 cells per thread: a byte per thread made this count a 1.7 ms pass over 268 M cells)
 __global__ __launch_bounds__(256) void ws_count_interior_nodir(const uint8_t *__restrict__ fd, int64_t H, int64_t W,
                                                               unsigned int *count)
@@ -132,25 +122,9 @@ __global__ __launch_bounds__(256) void ws_jump_kernel(int32_t *P, uint32_t *Q, i
 // first cell of its path outside the tile -- an ENTRY cell on the perimeter of a neighbouring tile.  Only perimeter cells are
 // jumped through global memory (6 % of the raster, and one hop now crosses a tile); the final pass takes one more hop for the
 // cells that still point at an entry.
-constexpr int WT = 64;
-// The perimeter cells of the tiles -- the only cells a path can ENTER a tile at -- also live in a compact array, 256 slots per tile
-// (1 KB: the jumps over the entry cells gather there instead of in the raster, where a tile's left / right columns cost a
-// sector per cell: 8.7 B per raster cell for 6 % of the cells).  slot: top row, bottom row, left column, right column.
-__device__ __forceinline__ int ws_perim_slot(int lr, int lc)
-{
-    if (lr == 0) return lc;
-    if (lr == WT - 1) return WT + lc;
-    if (lc == 0) return 2 * WT + (lr - 1);
-    if (lc == WT - 1) return 2 * WT + (WT - 2) + (lr - 1);
-    return -1;
-}
-// the node of an entry cell; -1 for a cell inside its tile (a pointer caught in a flow cycle: it never resolves)
-__device__ __forceinline__ int64_t ws_node_of(int32_t cell, uint32_t W, int ntc)
-{
-    const uint32_t r = (uint32_t)cell / W, c = (uint32_t)cell - r * W;
-    const int slot = ws_perim_slot((int)(r & 63u), (int)(c & 63u));
-    return slot < 0 ? -1 : (int64_t)((r >> 6) * (uint32_t)ntc + (c >> 6)) * 256 + slot;
-}
+constexpr int WT = WS_TILE;
+// (the compact array of the tiles' perimeter cells, 256 slots per tile -- ws_perim_slot, ws_node_of -- is in common.hpp: the flow
+// distance walks the same forest)
 // `pc` (optional): the pour-point candidates of the tile on the way (common.hpp: PourCandDev) -- a cell whose downstream cell does
 // not carry its own label (or which has none).  Whether the downstream cell is labelled is in `val` already.
 __global__ __launch_bounds__(256) void ws_tile_kernel(const uint8_t *__restrict__ fd, const int32_t *__restrict__ lab, int32_t *__restrict__ P, int64_t H,

@@ -241,3 +241,44 @@ class HydroPipeline(object):
             writer.close()
         else:
             writer.write(self.download_wet_at())
+
+    # ---- flow distance to the receiving bluespot, longest flow path per watershed -------
+    def flow_distance(self, cellsize=1.0):
+        """Distance along the flow path from every cell to the bluespot (or raster edge, or sink) it drains to, in units of
+        ``cellsize``, on the resident flow directions and (filtered or uploaded) labels.  Returns the number of cells whose walk
+        never ends (a flow cycle; they hold -1).  The raster and the records stay on the device for ``download_flow_distance`` /
+        ``download_flow_distance_to`` / ``flow_distance_records`` until the flow directions or the labels are written again."""
+        from .algorithms.flow import check_cellsize
+        unresolved = ctypes.c_int64(0)
+        _lib.call("mhip_ctx_flow_distance", self._ctx, ctypes.c_double(check_cellsize(cellsize)), ctypes.byref(unresolved))
+        return unresolved.value
+
+    def flow_distance_records(self):
+        """``records[l]`` (``nlabels + 1`` of ``_lib.INDEX_DTYPE``): length and head cell of the longest flow path of bluespot ``l``'s
+        local watershed (``l = 0``: of what drains to no bluespot); ``ValueError`` once the rasters it was made from are gone."""
+        if self.get_int("flow_distance_unresolved") < 0:
+            raise ValueError("flow_distance() has not been run on the resident flow directions and labels")
+        rec = np.zeros(self.get_int("nlabels") + 1, dtype=INDEX_DTYPE)
+        _lib.call("mhip_ctx_flow_distance_records", self._ctx, _lib.ptr(rec))
+        return rec
+
+    def download_flow_distance_rows(self, row0, nrows):
+        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
+        _lib.call("mhip_ctx_flow_distance_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
+        return out
+
+    def download_flow_distance(self):
+        """The raster of the last ``flow_distance`` (float32); ``ValueError`` once the flow directions or labels it was made from are
+        gone."""
+        return self.download_flow_distance_rows(0, self.shape[0])
+
+    def download_flow_distance_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        if hasattr(writer, "write_window"):
+            writer.open(self.shape, np.float32)
+            for row0 in range(0, self.shape[0], int(max_rows)):
+                n = min(int(max_rows), self.shape[0] - row0)
+                writer.write_window(row0, self.download_flow_distance_rows(row0, n))
+            writer.close()
+        else:
+            writer.write(self.download_flow_distance())
