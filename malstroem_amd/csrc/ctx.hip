@@ -71,6 +71,23 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
     }
 }
 
+int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, int64_t nrows, void *host, hipMemcpyKind kind)
+{
+    MH_HIP(hipSetDevice(c->device));
+    const size_t rowb = elem_bytes * (size_t)c->W;
+    char *dev = (char *)dev_base + rowb * (size_t)(c->ht + row0);
+    const bool up = kind == hipMemcpyHostToDevice;
+    MH_HIP(hipMemcpyAsync(up ? (void *)dev : host, up ? host : (void *)dev, rowb * (size_t)nrows, kind, cs(c)));
+    MH_HIP(stream_sync(cs(c)));      // (an upload's caller reuses its window buffer)
+    return MHIP_OK;
+}
+
+int ctx_fetch(mhip_ctx *c, const DevBuf &buf, size_t bytes, void *host)
+{
+    MH_HIP(hipSetDevice(c->device));
+    return download(host, buf, bytes, c->stream);
+}
+
 int ctx_fork_join_events(mhip_ctx *c)
 {
     if (c->ev_fork) return MHIP_OK;
@@ -235,15 +252,7 @@ int mhip_ctx_side_end(mhip_ctx *c)
 int mhip_ctx_upload(mhip_ctx *c, int which, const void *host)
 {
     MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_, "ctx_upload(ctx, which, host)");
-    MH_HIP(hipSetDevice(c->device));
-    MH_TRY(ctx_raster(c, which));
-    ctx_wrote(c, which, /*uploaded=*/true);
-    const size_t rowb = raster_elem(which) * (size_t)c->W;
-    MH_HIP(hipMemcpyAsync(c->r[which].as<char>() + rowb * c->ht, host, rowb * (size_t)c->H_owned, hipMemcpyHostToDevice, cs(c)));
-    MH_HIP(stream_sync(cs(c)));
-    c->have[which] = true;
-    if (which == MHIP_R_LABELS) c->labels_filtered = true;      // (uploaded labels are final: their count is max(labels), taken when asked for)
-    return MHIP_OK;
+    return mhip_ctx_upload_rows(c, which, 0, c->H_owned, host);
 }
 
 int mhip_ctx_upload_dem(mhip_ctx *c, const float *dem) { return mhip_ctx_upload(c, MHIP_R_DEM, dem); }
@@ -259,12 +268,10 @@ int mhip_ctx_upload_rows(mhip_ctx *c, int which, int64_t row0, int64_t nrows, co
     MH_TRY(ctx_raster(c, which));
     ctx_wrote(c, which, /*uploaded=*/true);
     c->have[which] = false;
-    const size_t rowb = raster_elem(which) * (size_t)c->W;
-    MH_HIP(hipMemcpyAsync(c->r[which].as<char>() + rowb * (size_t)(c->ht + row0), host, rowb * (size_t)nrows, hipMemcpyHostToDevice, cs(c)));
-    MH_HIP(stream_sync(cs(c)));      // the caller reuses its window buffer
+    MH_TRY(ctx_copy_rows(c, c->r[which].p, raster_elem(which), row0, nrows, const_cast<void *>(host), hipMemcpyHostToDevice));
     if (row0 + nrows == c->H_owned) {
         c->have[which] = true;
-        if (which == MHIP_R_LABELS) c->labels_filtered = true;
+        if (which == MHIP_R_LABELS) c->labels_filtered = true;      // (uploaded labels are final: their count is max(labels), taken when asked for)
     }
     return MHIP_OK;
 }
@@ -274,23 +281,15 @@ int mhip_ctx_download_rows(mhip_ctx *c, int which, int64_t row0, int64_t nrows, 
     MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_ && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned,
            "ctx_download_rows(ctx, which, row0, nrows, host)");
     MH_ARG(c->have[which], "raster has not been computed or uploaded");
-    MH_HIP(hipSetDevice(c->device));
-    const size_t rowb = raster_elem(which) * (size_t)c->W;
-    MH_HIP(hipMemcpyAsync(host, c->r[which].as<char>() + rowb * (size_t)(c->ht + row0), rowb * (size_t)nrows, hipMemcpyDeviceToHost, cs(c)));
-    MH_HIP(stream_sync(cs(c)));
-    return MHIP_OK;
+    return ctx_copy_rows(c, c->r[which].p, raster_elem(which), row0, nrows, host, hipMemcpyDeviceToHost);
 }
 
 int mhip_ctx_download(mhip_ctx *c, int which, void *host)
 {
     MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_, "ctx_download(ctx, which, host)");
-    MH_ARG(c->have[which], "raster has not been computed or uploaded");
-    MH_HIP(hipSetDevice(c->device));
-    const size_t rowb = raster_elem(which) * (size_t)c->W;
-    MH_HIP(hipMemcpyAsync(host, c->r[which].as<char>() + rowb * c->ht, rowb * (size_t)c->H_owned, hipMemcpyDeviceToHost, cs(c)));
-    MH_HIP(stream_sync(cs(c)));
-    return MHIP_OK;
+    return mhip_ctx_download_rows(c, which, 0, c->H_owned, host);
 }
+
 /* the same walk over the context's resident flow directions and (filtered) bluespot labels: no raster leaves the device */
 int mhip_ctx_trace_downstream(mhip_ctx *c, const int64_t *cells_rc, int64_t n, int use_background, int32_t background, int32_t *out_label,
                               int32_t *out_found, int64_t *out_len, const int64_t *offsets, int64_t *out_cells)
@@ -436,10 +435,7 @@ int mhip_ctx_get_f64(mhip_ctx *c, const char *key, double *value)
 int mhip_ctx_raw_stats(mhip_ctx *c, mhip_stat_record *records)
 {
     MH_ARG(c && records && c->raw_stats.p && c->nlabels_raw >= 0, "ctx_raw_stats needs a LABEL run");
-    MH_HIP(hipMemcpyAsync(records, c->raw_stats.p, sizeof(mhip_stat_record) * (size_t)(c->nlabels_raw + 1), hipMemcpyDeviceToHost,
-                          c->stream));
-    MH_HIP(stream_sync(c->stream));
-    return MHIP_OK;
+    return ctx_fetch(c, c->raw_stats, sizeof(mhip_stat_record) * (size_t)(c->nlabels_raw + 1), records);
 }
 
 int mhip_ctx_apply_keep(mhip_ctx *c, const uint8_t *keep)
@@ -452,25 +448,19 @@ int mhip_ctx_apply_keep(mhip_ctx *c, const uint8_t *keep)
 int mhip_ctx_stats(mhip_ctx *c, mhip_stat_record *records)
 {
     MH_ARG(c && records && c->stats_valid && c->labels_filtered, "ctx_stats needs LABEL + apply_keep (or mhip_ctx_hyps) on the resident depths and labels");
-    MH_HIP(hipMemcpyAsync(records, c->stats.p, sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(stream_sync(c->stream));
-    return MHIP_OK;
+    return ctx_fetch(c, c->stats, sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1), records);
 }
 
 int mhip_ctx_watershed_counts(mhip_ctx *c, int64_t *counts)
 {
     MH_ARG(c && counts && c->ws_counts_valid, "ctx_watershed_counts needs a WATERSHED run on the resident labels");
-    MH_HIP(hipMemcpyAsync(counts, c->ws_counts.p, 8 * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(stream_sync(c->stream));
-    return MHIP_OK;
+    return ctx_fetch(c, c->ws_counts, 8 * (size_t)(c->nlabels + 1), counts);
 }
 
 int mhip_ctx_pourpoints(mhip_ctx *c, mhip_index_record *records)
 {
     MH_ARG(c && records && c->pour_valid, "ctx_pourpoints needs a POURPOINTS run on the resident labels and accumulated flow");
-    MH_HIP(hipMemcpyAsync(records, c->pour.p, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(stream_sync(c->stream));
-    return MHIP_OK;
+    return ctx_fetch(c, c->pour, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
 }
 
 /* ---- final state of the bluespots on the resident rasters (hyps.hip) ------------------------------------------------------ */
@@ -549,9 +539,7 @@ int mhip_ctx_final_depths(mhip_ctx *c, const double *q, mhip_final_record *recor
     MH_TRY(stage_end(c, MHIP_STAGE_FINALDEPTHS, s));
     k->valid = true;
     c->have[MHIP_R_FINALDEPTHS] = true;
-    MH_HIP(hipMemcpyAsync(records, c->hyps_rec.p, sizeof(mhip_final_record) * (size_t)(nlab + 1), hipMemcpyDeviceToHost, s));
-    MH_HIP(stream_sync(s));
-    return MHIP_OK;
+    return ctx_fetch(c, c->hyps_rec, sizeof(mhip_final_record) * (size_t)(nlab + 1), records);
 }
 
 /* ---- the rain at which every cell gets wet (wetat.hip): K levels, one pass over the resident rasters ------------------------- */
@@ -580,20 +568,14 @@ int mhip_ctx_wet_at(mhip_ctx *c, int32_t K, const double *q, const float *values
                       c->wetat_out.as<float>(), d_rec.as<int64_t>() + 3, 4, s, k->a, k->b));      // (synchronises)
     k->valid = true;
     c->wetat_events = K;
-    MH_HIP(hipMemcpyAsync(records, d_rec.p, sizeof(mhip_final_record) * nt, hipMemcpyDeviceToHost, s));
-    MH_HIP(stream_sync(s));
-    return MHIP_OK;
+    return ctx_fetch(c, d_rec, sizeof(mhip_final_record) * nt, records);
 }
 
 int mhip_ctx_wet_at_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
 {
     MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_wet_at_rows(ctx, row0, nrows, dst)");
     MH_ARG(c->wetat_events > 0 && c->wetat_out.p, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels");
-    MH_HIP(hipSetDevice(c->device));
-    const size_t rowb = 4 * (size_t)c->W;
-    MH_HIP(hipMemcpyAsync(dst, c->wetat_out.as<char>() + rowb * (size_t)row0, rowb * (size_t)nrows, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(stream_sync(c->stream));
-    return MHIP_OK;
+    return ctx_copy_rows(c, c->wetat_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
 }
 
 /* ---- flow distance to the receiving bluespot, longest flow path per watershed (flowdist.hip) ------------------------------------ */
@@ -623,21 +605,14 @@ int mhip_ctx_flow_distance_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float 
 {
     MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_flow_distance_rows(ctx, row0, nrows, dst)");
     MH_ARG(c->fdist_unresolved >= 0 && c->fdist_out.p, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels");
-    MH_HIP(hipSetDevice(c->device));
-    const size_t rowb = 4 * (size_t)c->W;
-    MH_HIP(hipMemcpyAsync(dst, c->fdist_out.as<char>() + rowb * (size_t)row0, rowb * (size_t)nrows, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(stream_sync(c->stream));
-    return MHIP_OK;
+    return ctx_copy_rows(c, c->fdist_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
 }
 
 int mhip_ctx_flow_distance_records(mhip_ctx *c, mhip_index_record *records)
 {
     MH_ARG(c && records, "ctx_flow_distance_records(ctx, records)");
     MH_ARG(c->fdist_unresolved >= 0 && c->fdist_rec.p, "ctx_flow_distance_records needs mhip_ctx_flow_distance on the resident flow directions and labels");
-    MH_HIP(hipSetDevice(c->device));
-    MH_HIP(hipMemcpyAsync(records, c->fdist_rec.p, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(stream_sync(c->stream));
-    return MHIP_OK;
+    return ctx_fetch(c, c->fdist_rec, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
 }
 
 }  // extern "C"

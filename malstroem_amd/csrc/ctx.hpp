@@ -201,6 +201,13 @@ static inline bool on_side(mhip_ctx *c) { return t_side_ctx == c; }
 // was derived from the old content.  Host-only flag work.  uploaded: the content comes from outside (an uploaded FILLED surface
 // has no flood of this context behind it).
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded = false);
+// ---- the two ways data crosses between the host and a context (ctx.hip) -----------------------------------------------------------
+// Rows [row0, row0 + nrows) of the OWNED rows of `dev_base`, a device array of the local raster's full-width rows (halo rows
+// included) of `elem_bytes` per cell, to or from `host` by `kind`: one copy on cs(c), then one synchronisation.  The caller has
+// checked the window against H_owned.  Every whole-raster and windowed transfer of ctx.hip is this call.
+int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, int64_t nrows, void *host, hipMemcpyKind kind);
+// `bytes` of a record buffer to `host` on the main stream, synchronised: every record getter after its validity test
+int ctx_fetch(mhip_ctx *c, const DevBuf &buf, size_t bytes, void *host);
 // the fork / join events of the two branches (mhip_ctx_side_begin, mhip_ctx_run), created once
 int ctx_fork_join_events(mhip_ctx *c);
 // the label filter and what follows a LABELS write lazily (mhip_ctx_apply_keep; the stages that want final labels)

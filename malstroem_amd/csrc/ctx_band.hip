@@ -32,6 +32,24 @@ static int update_halo_rows(mhip_ctx *c, int which, const void *top, const void 
     return MHIP_OK;
 }
 
+// the edge-row getters: rows side0 / side1 of raster `which` into dst0 / dst1 (nullptr: not wanted), host or device memory by
+// `kind`.  One synchronisation: a transport reads a device destination on its own stream.
+static int copy_edge_rows(mhip_ctx *c, int which, int side0, void *dst0, int side1, void *dst1, hipMemcpyKind kind, const char *usage)
+{
+    MH_ARG(c && which >= 0 && which < MHIP_R_COUNT_, usage);
+    MH_ARG(c->r[which].p, "raster has not been computed or uploaded");
+    const int side[2] = {side0, side1};
+    void *const dst[2] = {dst0, dst1};
+    for (int k = 0; k < 2; ++k) MH_ARG(!dst[k] || side[k] < 2 || (side[k] == 2 ? c->ht : c->hb), "this band has no halo row on that side");
+    if (!dst0 && !dst1) return MHIP_OK;
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = cs(c);
+    for (int k = 0; k < 2; ++k)
+        if (dst[k]) MH_HIP(hipMemcpyAsync(dst[k], row_ptr(c, which, side[k]), row_bytes(c, which), kind, s));
+    MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
 // a relabelling of the resident labels: new numbers on the same cells (components stay components), `nlabels` of them over all bands
 static void labels_renumbered(mhip_ctx *c, int64_t nlabels)
 {
@@ -75,41 +93,27 @@ int mhip_ctx_band_info(mhip_ctx *c, int64_t *row_off, int64_t *rows_local, int32
 
 int mhip_ctx_get_edge_row(mhip_ctx *c, int which, int side, void *host)
 {
-    MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_ && side >= 0 && side <= 3, "ctx_get_edge_row(ctx, which, side, host)");
-    MH_ARG(c->r[which].p, "raster has not been computed or uploaded");
-    MH_ARG(side < 2 || (side == 2 ? c->ht : c->hb), "this band has no halo row on that side");
-    MH_HIP(hipSetDevice(c->device));
-    MH_HIP(hipMemcpyAsync(host, row_ptr(c, which, side), row_bytes(c, which), hipMemcpyDeviceToHost, cs(c)));
-    MH_HIP(stream_sync(cs(c)));
-    return MHIP_OK;
+    static const char *const usage = "ctx_get_edge_row(ctx, which, side, host)";
+    MH_ARG(host && side >= 0 && side <= 3, usage);
+    return copy_edge_rows(c, which, side, host, 0, nullptr, hipMemcpyDeviceToHost, usage);
 }
 
 int mhip_ctx_set_halo_row(mhip_ctx *c, int which, int side, const void *host, int32_t *changed)
 {
     MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_ && (side == 0 || side == 1), "ctx_set_halo_row(ctx, which, side, host)");
     MH_ARG(side == 0 ? c->ht : c->hb, "this band has no halo row on that side");
-    MH_HIP(hipSetDevice(c->device));
-    MH_TRY(ctx_raster(c, which));
-    const size_t rowb = row_bytes(c, which);
-    DevBuf tmp;
-    MH_TRY(tmp.alloc(rowb));
-    MH_HIP(hipMemcpyAsync(tmp.p, host, rowb, hipMemcpyHostToDevice, cs(c)));
-    int ch = 0;
-    MH_TRY(row_update_dev(row_ptr(c, which, 2 + side), tmp.p, (int64_t)rowb, &ch, cs(c)));
-    if (changed) *changed = ch;
+    int32_t ch[2];
+    MH_TRY(mhip_ctx_set_halo_rows(c, which, side == 0 ? host : nullptr, side == 1 ? host : nullptr, ch));
+    if (changed) *changed = ch[side];
     return MHIP_OK;
 }
 
 // the same two calls for a transport that moves DEVICE buffers (RCCL send/recv on tensors of the launcher)
 int mhip_ctx_get_edge_row_dev(mhip_ctx *c, int which, int side, void *dev_dst)
 {
-    MH_ARG(c && dev_dst && which >= 0 && which < MHIP_R_COUNT_ && side >= 0 && side <= 3, "ctx_get_edge_row_dev(ctx, which, side, dev)");
-    MH_ARG(c->r[which].p, "raster has not been computed or uploaded");
-    MH_ARG(side < 2 || (side == 2 ? c->ht : c->hb), "this band has no halo row on that side");
-    MH_HIP(hipSetDevice(c->device));
-    MH_HIP(hipMemcpyAsync(dev_dst, row_ptr(c, which, side), row_bytes(c, which), hipMemcpyDeviceToDevice, cs(c)));
-    MH_HIP(stream_sync(cs(c)));   // the transport reads the buffer on its own stream
-    return MHIP_OK;
+    static const char *const usage = "ctx_get_edge_row_dev(ctx, which, side, dev)";
+    MH_ARG(dev_dst && side >= 0 && side <= 3, usage);
+    return copy_edge_rows(c, which, side, dev_dst, 0, nullptr, hipMemcpyDeviceToDevice, usage);
 }
 
 int mhip_ctx_set_halo_row_dev(mhip_ctx *c, int which, int side, const void *dev_src, int32_t *changed)
@@ -130,15 +134,7 @@ int mhip_ctx_set_halo_row_dev(mhip_ctx *c, int which, int side, const void *dev_
  * compared with / stored into the halo rows; changed[0 / 1] = the top / bottom halo row changed. */
 int mhip_ctx_get_edge_rows(mhip_ctx *c, int which, void *host_first, void *host_last)
 {
-    MH_ARG(c && which >= 0 && which < MHIP_R_COUNT_, "ctx_get_edge_rows(ctx, which, first, last)");
-    MH_ARG(c->r[which].p, "raster has not been computed or uploaded");
-    if (!host_first && !host_last) return MHIP_OK;
-    MH_HIP(hipSetDevice(c->device));
-    hipStream_t s = cs(c);
-    if (host_first) MH_HIP(hipMemcpyAsync(host_first, row_ptr(c, which, 0), row_bytes(c, which), hipMemcpyDeviceToHost, s));
-    if (host_last) MH_HIP(hipMemcpyAsync(host_last, row_ptr(c, which, 1), row_bytes(c, which), hipMemcpyDeviceToHost, s));
-    MH_HIP(stream_sync(s));
-    return MHIP_OK;
+    return copy_edge_rows(c, which, 0, host_first, 1, host_last, hipMemcpyDeviceToHost, "ctx_get_edge_rows(ctx, which, first, last)");
 }
 
 int mhip_ctx_set_halo_rows(mhip_ctx *c, int which, const void *host_top, const void *host_bottom, int32_t *changed)

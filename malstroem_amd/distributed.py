@@ -32,7 +32,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import INDEX_DTYPE, R_DEM, R_FILLED, R_FLOWDIR, R_NOFLAT, RASTER_DTYPE, STAGE_ACCUM, STAGE_FLOWDIR, STAT_DTYPE
-from .pipeline import RASTERS
+from ._ctx import RASTERS, CtxHandle
 
 __all__ = ["band_rows", "Comm", "SingleComm", "ThreadComm", "SocketComm", "HybridComm", "HipBand", "BandPipeline"]
 
@@ -665,15 +665,15 @@ class HybridComm(Comm):
 
 # ---- compute backend: one band context on one GPU -----------------------------------------------------------------
 
-class HipBand(object):
+class HipBand(CtxHandle):
     """ctypes face of a band ``mhip_ctx`` (include/malstroem_hip.h, row-band protocol)."""
 
     def __init__(self, H_global, W, row0, nrows, device=0, rank=0, size=1, unique_id=None):
         """``unique_id``: the 128 bytes of rank 0's ``HipBand.new_unique_id()``; with it the context joins the RCCL
         communicator of all ``size`` bands (a collective call) and moves its halo rows itself."""
+        super().__init__((nrows, W))
         self.W, self.nrows, self.row0, self.H_global = int(W), int(nrows), int(row0), int(H_global)
         self.has_side_comm = False
-        self._ctx = ctypes.c_void_p()
         uid = None
         if unique_id is not None:
             if len(unique_id) != 128:
@@ -720,31 +720,14 @@ class HipBand(object):
         _lib.call("mhip_ctx_allreduce_max", self._ctx, ctypes.c_double(float(value)), ctypes.byref(out))
         return out.value
 
-    def close(self):
-        if self._ctx:
-            _lib.call("mhip_ctx_destroy", self._ctx)
-            self._ctx = ctypes.c_void_p()
-
-    def upload(self, name, arr):
-        which = RASTERS[name]
-        a = np.ascontiguousarray(arr, dtype=RASTER_DTYPE[which])
-        if a.shape != (self.nrows, self.W):
-            raise ValueError("band raster must be %s, got %s" % ((self.nrows, self.W), a.shape))
-        _lib.call("mhip_ctx_upload", self._ctx, which, _lib.ptr(a))
-
-    def download(self, name):
-        which = RASTERS[name]
-        out = np.empty((self.nrows, self.W), dtype=RASTER_DTYPE[which])
-        _lib.call("mhip_ctx_download", self._ctx, which, _lib.ptr(out))
-        return out
+    def _shape_error(self, got):
+        return "band raster must be %s, got %s" % (self.shape, got)
 
     def download_rows(self, name, row0, nrows):
-        """rows [row0, row0 + nrows) of the band's OWNED rows (a window on the host, whatever the band's height)"""
-        which = RASTERS[name]
-        out = np.empty((int(nrows), self.W), dtype=RASTER_DTYPE[which])
-        if nrows:
-            _lib.call("mhip_ctx_download_rows", self._ctx, which, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
+        """rows [row0, row0 + nrows) of the band's OWNED rows (a window on the host, whatever the band's height); no rows: no call"""
+        if not nrows:
+            return np.empty((0, self.W), dtype=RASTER_DTYPE[RASTERS[name]])
+        return super().download_rows(name, row0, nrows)
 
     def get_edge_row(self, name, side):
         which = RASTERS[name]
@@ -850,14 +833,14 @@ class HipBand(object):
 
     def run_flowdir(self):
         _lib.call("mhip_ctx_run", self._ctx, STAGE_FLOWDIR)
-        _lib.call("mhip_ctx_sync", self._ctx)
+        self.sync()
 
     def zero_raster(self, name):
         _lib.call("mhip_ctx_zero_raster", self._ctx, RASTERS[name])
 
     def run_accum(self):
         _lib.call("mhip_ctx_run", self._ctx, STAGE_ACCUM)
-        _lib.call("mhip_ctx_sync", self._ctx)
+        self.sync()
 
     def accum_boundary(self):
         """Boundary pass of the band accumulation (``mhip_ctx_band_accum_boundary``): ACCUM = the band's own contribution;
@@ -935,11 +918,6 @@ class HipBand(object):
     def apply_neg_lut(self, name, lut):
         lut = np.ascontiguousarray(lut, dtype=np.int32)
         _lib.call("mhip_ctx_band_apply_neg_lut", self._ctx, RASTERS[name], _lib.ptr(lut), _lib.i64(lut.size))
-
-    def get_int(self, key):
-        v = ctypes.c_int64(0)
-        _lib.call("mhip_ctx_get_i64", self._ctx, key.encode(), ctypes.byref(v))
-        return v.value
 
     def side_begin(self):
         """The calling thread's band calls run on the context's side stream from here on (after everything issued so far)."""

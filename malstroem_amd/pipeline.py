@@ -10,72 +10,39 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (FINAL_DTYPE, INDEX_DTYPE, R_ACCUM, R_DEM, R_DEPTHS, R_FILLED, R_FINALDEPTHS, R_FLOWDIR, R_LABELS, R_NGDIST, R_NOFLAT,
-                   R_WATERSHEDS, RASTER_DTYPE, STAGE_ACCUM, STAGE_FILL, STAGE_FINALDEPTHS, STAGE_FLOWDIR, STAGE_HYPS, STAGE_LABEL,
+from ._ctx import RASTERS, CtxHandle
+from ._lib import (FINAL_DTYPE, INDEX_DTYPE, RASTER_DTYPE, STAGE_ACCUM, STAGE_FILL, STAGE_FINALDEPTHS, STAGE_FLOWDIR, STAGE_HYPS, STAGE_LABEL,
                    STAGE_NOFLAT, STAGE_POURPOINTS, STAGE_WATERSHED, STAT_DTYPE)
 
 STAGES = {"fill": STAGE_FILL, "noflat": STAGE_NOFLAT, "flowdir": STAGE_FLOWDIR, "accum": STAGE_ACCUM,
           "label": STAGE_LABEL, "watershed": STAGE_WATERSHED, "pourpoints": STAGE_POURPOINTS}
 # timing slots of hypsometry() / final_depths() for stage_ms(); run() does not take them
 TIMED = dict(STAGES, hyps=STAGE_HYPS, finaldepths=STAGE_FINALDEPTHS)
-RASTERS = {"dem": R_DEM, "filled": R_FILLED, "depths": R_DEPTHS, "noflat": R_NOFLAT, "flowdir": R_FLOWDIR,
-           "accum": R_ACCUM, "labels": R_LABELS, "watersheds": R_WATERSHEDS, "ngdist": R_NGDIST,
-           "finaldepths": R_FINALDEPTHS}
 
 
-class HydroPipeline(object):
+def write_windows(writer, shape, dtype, rows_fn, max_rows):
+    """Stream a ``shape`` raster of ``dtype`` into a writer with ``open`` / ``write_window`` / ``close``, ``rows_fn(row0, nrows)``
+    giving one window of at most ``max_rows`` rows at a time; falls back to ``write(array)`` of the whole raster."""
+    if not hasattr(writer, "write_window"):
+        writer.write(rows_fn(0, shape[0]))
+        return
+    writer.open(shape, dtype)
+    for row0 in range(0, shape[0], int(max_rows)):
+        writer.write_window(row0, rows_fn(row0, min(int(max_rows), shape[0] - row0)))
+    writer.close()
+
+
+class HydroPipeline(CtxHandle):
     """Rasters of one H x W DEM (or one row band of it) resident on one MI355X."""
 
     def __init__(self, shape, device=0):
-        self.shape = (int(shape[0]), int(shape[1]))
-        self._ctx = ctypes.c_void_p()
+        super().__init__(shape)
         _lib.call("mhip_ctx_create", ctypes.byref(self._ctx), _lib.i64(self.shape[0]), _lib.i64(self.shape[1]), int(device))
 
-    def close(self):
-        if self._ctx:
-            _lib.call("mhip_ctx_destroy", self._ctx)
-            self._ctx = ctypes.c_void_p()
+    def _shape_error(self, got):
+        return "raster shape %s does not match the pipeline shape %s" % (got, self.shape)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # ---- data movement ---------------------------------------------------------------------------
-    def upload(self, name, array):
-        which = RASTERS[name]
-        a = np.ascontiguousarray(array, dtype=RASTER_DTYPE[which])
-        if a.shape != self.shape:
-            raise ValueError("raster shape %s does not match the pipeline shape %s" % (a.shape, self.shape))
-        _lib.call("mhip_ctx_upload", self._ctx, which, _lib.ptr(a))
-
-    def download(self, name):
-        which = RASTERS[name]
-        out = np.empty(self.shape, dtype=RASTER_DTYPE[which])
-        _lib.call("mhip_ctx_download", self._ctx, which, _lib.ptr(out))
-        return out
-
-    # ---- windowed data movement (malstroem_amd.io readers / writers): one window on the host, whatever the raster's size
-    def upload_rows(self, name, row0, array):
-        which = RASTERS[name]
-        a = np.ascontiguousarray(array, dtype=RASTER_DTYPE[which])
-        if a.ndim != 2 or a.shape[1] != self.shape[1]:
-            raise ValueError("window must be full-width rows of the pipeline's raster")
-        _lib.call("mhip_ctx_upload_rows", self._ctx, which, _lib.i64(row0), _lib.i64(a.shape[0]), _lib.ptr(a))
-
-    def download_rows(self, name, row0, nrows):
-        which = RASTERS[name]
-        out = np.empty((int(nrows), self.shape[1]), dtype=RASTER_DTYPE[which])
-        _lib.call("mhip_ctx_download_rows", self._ctx, which, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
-
+    # ---- data movement: upload / download and their windowed forms are CtxHandle's -----------------
     def upload_from(self, name, reader, max_rows=None):
         """Stream raster ``name`` from a reader with ``iter_windows`` (malstroem_amd.io.RasterReader); falls back to ``read()``."""
         if hasattr(reader, "iter_windows"):
@@ -86,14 +53,7 @@ class HydroPipeline(object):
 
     def download_to(self, name, writer, max_rows=4096):
         """Stream raster ``name`` into a writer with ``open`` / ``write_window`` / ``close``; falls back to ``write(array)``."""
-        if hasattr(writer, "write_window"):
-            writer.open(self.shape, RASTER_DTYPE[RASTERS[name]])
-            for row0 in range(0, self.shape[0], int(max_rows)):
-                n = min(int(max_rows), self.shape[0] - row0)
-                writer.write_window(row0, self.download_rows(name, row0, n))
-            writer.close()
-        else:
-            writer.write(self.download(name))
+        write_windows(writer, self.shape, RASTER_DTYPE[RASTERS[name]], lambda row0, n: self.download_rows(name, row0, n), max_rows)
 
     # ---- stages ------------------------------------------------------------------------------------
     def run(self, *stages):
@@ -101,9 +61,6 @@ class HydroPipeline(object):
         for s in stages:
             mask |= STAGES[s] if isinstance(s, str) else int(s)
         _lib.call("mhip_ctx_run", self._ctx, mask)
-
-    def sync(self):
-        _lib.call("mhip_ctx_sync", self._ctx)
 
     def stage_ms(self, stage):
         ms = ctypes.c_float(0)
@@ -128,16 +85,6 @@ class HydroPipeline(object):
         gbs = ctypes.c_double(0)
         _lib.call("mhip_read_bandwidth", _lib.i64(nbytes), ctypes.c_int32(reps), ctypes.byref(gbs))
         return gbs.value
-
-    def get_int(self, key):
-        v = ctypes.c_int64(0)
-        _lib.call("mhip_ctx_get_i64", self._ctx, key.encode(), ctypes.byref(v))
-        return v.value
-
-    def get_float(self, key):
-        v = ctypes.c_double(0)
-        _lib.call("mhip_ctx_get_f64", self._ctx, key.encode(), ctypes.byref(v))
-        return v.value
 
     # ---- label bookkeeping (bluespots.py:159-172) -------------------------------------------------
     def raw_stats(self):
@@ -233,14 +180,7 @@ class HydroPipeline(object):
 
     def download_wet_at_to(self, writer, max_rows=4096):
         """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
-        if hasattr(writer, "write_window"):
-            writer.open(self.shape, np.float32)
-            for row0 in range(0, self.shape[0], int(max_rows)):
-                n = min(int(max_rows), self.shape[0] - row0)
-                writer.write_window(row0, self.download_wet_at_rows(row0, n))
-            writer.close()
-        else:
-            writer.write(self.download_wet_at())
+        write_windows(writer, self.shape, np.float32, self.download_wet_at_rows, max_rows)
 
     # ---- flow distance to the receiving bluespot, longest flow path per watershed (DESIGN.md 11) -------
     def flow_distance(self, cellsize=1.0):
@@ -274,11 +214,4 @@ class HydroPipeline(object):
 
     def download_flow_distance_to(self, writer, max_rows=4096):
         """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
-        if hasattr(writer, "write_window"):
-            writer.open(self.shape, np.float32)
-            for row0 in range(0, self.shape[0], int(max_rows)):
-                n = min(int(max_rows), self.shape[0] - row0)
-                writer.write_window(row0, self.download_flow_distance_rows(row0, n))
-            writer.close()
-        else:
-            writer.write(self.download_flow_distance())
+        write_windows(writer, self.shape, np.float32, self.download_flow_distance_rows, max_rows)
