@@ -41,6 +41,17 @@ typedef struct { double value; int64_t row, col; } mhip_index_record;
  * [('drawdown','<f8'),('dmax_final','<f8'),('qmodel','<f8'),('wet_cells','<i8')]: water level below the spill level, largest
  * final depth, the amount the hypsometry table holds at that level (cell-metres), cells left with water */
 typedef struct { double drawdown, dmax_final, qmodel; int64_t wet_cells; } mhip_final_record;
+/* DEM adaptations (mhip_burn_lines_f32 below).  A segment between two cells, each coordinate within +-2**29 and
+ * free to lie outside the raster; `line`: the line it belongs to, `koff`: the steps of the line's earlier segments.  numpy
+ * [('r0','<i4'),('c0','<i4'),('r1','<i4'),('c1','<i4'),('line','<i4'),('koff','<i4')] */
+typedef struct { int32_t r0, c0, r1, c1, line, koff; } mhip_burn_segment;
+/* a line: the levels at its first / last vertex (NaN: the DEM's value there), the steps of all its segments, flags: bit 0 raise
+ * (0 lower), bit 1 4-connected (0 8-connected).  numpy [('z0','<f8'),('z1','<f8'),('ntotal','<i4'),('flags','<i4')] */
+typedef struct { double z0, z1; int32_t ntotal, flags; } mhip_burn_line;
+/* what became of a line: the levels used (NaN when skipped), the cells of the raster it enumerates (0 when skipped), status 0 burnt,
+ * 1 skipped: a vertex to sample lies outside, 2 skipped: the sampled value is not finite or is nodata.  numpy
+ * [('z0','<f8'),('z1','<f8'),('cells','<i8'),('status','<i4'),('pad','<i4')] */
+typedef struct { double z0, z1; int64_t cells; int32_t status, pad; } mhip_burn_result;
 /* most rain events of one mhip_label_wet_at_f32 / mhip_ctx_wet_at call */
 #define MHIP_WETAT_MAX_EVENTS 16
 
@@ -157,6 +168,19 @@ int mhip_watersheds_i32(const uint8_t *flowdir, int32_t *labels_inout, int64_t H
  * MHIP_EINVAL.  unresolved (optional): the number of cells that hold -1. */
 int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, double scale, int64_t nlab, float *out_dist,
                        mhip_index_record *records, int64_t *unresolved);
+
+/* Burn lines into a DEM in place (no reference counterpart; the definition is tests/_burn.py).  Segment (r0, c0) ->
+ * (r1, c1) has n = max(|dr|, |dc|) steps along its major axis (the column when |dc| >= |dr|); step k = 0 .. n sits at major = start
+ * + sign * k, minor = start + sign * ((2 * k * dmin + n) / (2 * n)) in integers; a 4-connected line also takes the corner cell (major
+ * of k, minor of k - 1) where the minor coordinate moves.  Level of a step: float(z0 * (1 - t) + z1 * t) in float64 with t =
+ * double(koff + k) / double(ntotal) (ntotal == 0: the smaller of z0, z1 for a lower line, the larger for a raise line); a NaN z0 / z1
+ * is the value of the DEM as it came in at the first vertex of the line's segment of the smallest koff / the last vertex of its
+ * segment of the largest koff + n.  All lower lines write min(dem, z), then all raise lines max(dem, z); cells outside are ignored,
+ * a NaN cell stays.  The result depends on no order of lines or segments.  nodata: NaN = none.  results[nline].
+ * MHIP_EINVAL before any device work: a line index out of range, a coordinate beyond 2**29, koff < 0 or koff + n > ntotal, an
+ * explicit level that is infinite or beyond the float32 range, flags > 3, a negative count.  nseg == 0: nothing is burnt. */
+int mhip_burn_lines_f32(float *dem, int64_t H, int64_t W, int64_t nseg, const mhip_burn_segment *segments, int64_t nline,
+                        const mhip_burn_line *lines, double nodata, mhip_burn_result *results);
 
 /* net.next_downstream_label(flowdir, labeled, cell, background_label, geometry) for a BATCH of cells -- what
  * net.pourpoint_network / geometric_pourpoint_network loop over (reference net.py:142-192, 195-224).  cells_rc: n (row, col)
@@ -458,6 +482,11 @@ int mhip_ctx_wet_at_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst)
 int mhip_ctx_flow_distance(mhip_ctx *ctx, double scale, int64_t *unresolved);
 int mhip_ctx_flow_distance_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
 int mhip_ctx_flow_distance_records(mhip_ctx *ctx, mhip_index_record *records);
+/* mhip_burn_lines_f32 on the resident DEM of an undivided context, in place; a row band is refused.  One more writer of the DEM:
+ * every raster, record set, table and result derived from it is dropped as after an upload (the stages run again on the adapted
+ * DEM).  nseg == 0 leaves the context as it is. */
+int mhip_ctx_burn_lines(mhip_ctx *ctx, int64_t nseg, const mhip_burn_segment *segments, int64_t nline, const mhip_burn_line *lines,
+                        double nodata, mhip_burn_result *results);
 
 #ifdef __cplusplus
 }

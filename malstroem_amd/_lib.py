@@ -19,6 +19,11 @@ STAT_DTYPE = np.dtype([("min", "<f8"), ("max", "<f8"), ("sum", "<f8"), ("count",
 INDEX_DTYPE = np.dtype([("value", "<f8"), ("row", "<i8"), ("col", "<i8")])                    # _label.pyx:26-28
 FINAL_DTYPE = np.dtype([("drawdown", "<f8"), ("dmax_final", "<f8"), ("qmodel", "<f8"), ("wet_cells", "<i8")])   # mhip_final_record
 
+# DEM adaptations (adaptations.py): mhip_burn_segment, mhip_burn_line, mhip_burn_result
+BURN_SEGMENT_DTYPE = np.dtype([("r0", "<i4"), ("c0", "<i4"), ("r1", "<i4"), ("c1", "<i4"), ("line", "<i4"), ("koff", "<i4")])
+BURN_LINE_DTYPE = np.dtype([("z0", "<f8"), ("z1", "<f8"), ("ntotal", "<i4"), ("flags", "<i4")])
+BURN_RESULT_DTYPE = np.dtype([("z0", "<f8"), ("z1", "<f8"), ("cells", "<i8"), ("status", "<i4"), ("pad", "<i4")])
+
 WETAT_MAX_EVENTS = 16     # MHIP_WETAT_MAX_EVENTS: most rain events of one wet_at call
 
 OK, EINVAL, EHIP, ENODEV, ELIMIT, ENOTCONV, ECOMM = 0, -1, -2, -3, -4, -5, -6
@@ -54,6 +59,7 @@ SYMBOLS = [
     "mhip_label_hyps_layout", "mhip_label_hyps_f32", "mhip_hyps_levels", "mhip_final_depths_f32", "mhip_ctx_hyps", "mhip_ctx_hyps_fetch",
     "mhip_ctx_final_depths", "mhip_label_wet_at_f32", "mhip_ctx_wet_at", "mhip_ctx_wet_at_rows",
     "mhip_flow_distance", "mhip_ctx_flow_distance", "mhip_ctx_flow_distance_rows", "mhip_ctx_flow_distance_records",
+    "mhip_burn_lines_f32", "mhip_ctx_burn_lines",
 ]
 
 _lib = None

@@ -87,7 +87,7 @@ def parse_filter(filter):
 
 
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
-                finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False):
+                finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -107,7 +107,12 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
 
     ``flowlength``: also write ``flowlength.tif`` -- per cell the distance in metres along the flow path to the bluespot it drains to
     (nodata -1) -- and give every pour point ``wshed_lfp`` / ``lfp_row`` / ``lfp_col``, the longest flow path of its local watershed
-    (``BluespotTool(output_flowlength_raster=...)``); the dict gains ``flowlength``.  Not on row bands yet."""
+    (``BluespotTool(output_flowlength_raster=...)``); the dict gains ``flowlength``.  Not on row bands yet.
+
+    ``adaptations``: the path of a GeoJSON file of culvert / dike lines (``adaptations.lines_from_features`` names the properties)
+    that are burnt into the DEM before anything is computed; also writes ``dem_adapted.tif`` and the vector layer ``adaptations``:
+    the lines with ``status``, ``z_from_used``, ``z_to_used`` and ``cells``; the dict gains ``dem_adapted`` and ``adaptations``.  Not
+    on row bands yet."""
     if vector:
         raise NotImplementedError("vectorisation of bluespots / watersheds (GDAL polygonize) is outside malstroem_amd's hot path")
     if (onset or not final_rasters) and not finalstate:
@@ -119,6 +124,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         if flowlength:
             raise NotImplementedError("flowlength on row bands: a flow path crosses the seams between the bands, and the walk over "
                                       "them is not built yet; run it on one context")
+        if adaptations is not None:
+            raise NotImplementedError("adaptations on row bands: a line crosses the seams between the bands, and its levels hang on "
+                                      "both of its ends, which is not built yet; run it on one context")
         return _process_all_bands(dem, outdir, rain, accum, filter, comm, device, nodatasubst, backend_factory)
     if not os.path.isdir(outdir) or os.listdir(outdir):
         raise ValueError("outdir isn't an empty directory")
@@ -138,7 +146,13 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     flowdir_writer = io.RasterWriter(os.path.join(outdir, 'flowdir.tif'), tr, crs)
     depths_writer = io.RasterWriter(os.path.join(outdir, 'bs_depths.tif'), tr, crs)
     accum_writer = io.RasterWriter(os.path.join(outdir, 'accum.tif'), tr, crs) if accum else None
-    pipe = DemTool(dem_reader, filled_writer, flowdir_writer, depths_writer, accum_writer, device=device).process(keep_pipeline=True)
+    adapt = {}
+    if adaptations is not None:
+        adapted_path = os.path.join(outdir, 'dem_adapted.tif')
+        report_writer = io.VectorWriter('GeoJSON', outvector, 'adaptations', None, None, crs)
+        adapt = dict(input_adaptations=io.VectorReader(adaptations), output_adapted=io.RasterWriter(adapted_path, tr, crs, nodatasubst),
+                     output_adaptation_report=report_writer)
+    pipe = DemTool(dem_reader, filled_writer, flowdir_writer, depths_writer, accum_writer, device=device, **adapt).process(keep_pipeline=True)
     try:
         # Process bluespots
         pourpoint_writer = io.VectorWriter('GeoJSON', outvector, 'pourpoints', None, None, crs)
@@ -165,6 +179,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                    nodes=nodes_writer.filepath, streams=streams_writer.filepath, pourpoints=pourpoint_writer.filepath)
         if flowlength:
             res["flowlength"] = flowlength_path
+        if adaptations is not None:
+            res.update(dem_adapted=adapted_path, adaptations=report_writer.filepath)
         if finalstate:
             # Final state of every event: the depths and the filtered labels are still on the device
             from .finalstate import FinalStateTool

@@ -1,6 +1,6 @@
 // api.hip -- the host-raster entry points of libmalstroem_hip.so (declared in include/malstroem_hip.h): upload -> stage -> download,
 // one per malstroem.algorithms stage function, over the device-pointer stage implementations (fill.hip, d8.hip, accum.hip, ccl.hip,
-// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
+// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
 #include <vector>
 
 #include "common.hpp"
@@ -404,6 +404,21 @@ int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H,
                              records ? d_rec.as<mhip_index_record>() : nullptr, unresolved, s));
     if (records) MH_HIP(hipMemcpyAsync(records, d_rec.p, sizeof(mhip_index_record) * (size_t)(nlab + 1), hipMemcpyDeviceToHost, s));
     return download(out_dist, d_out, n * 4, s);
+}
+
+int mhip_burn_lines_f32(float *dem, int64_t H, int64_t W, int64_t nseg, const mhip_burn_segment *segments, int64_t nline,
+                        const mhip_burn_line *lines, double nodata, mhip_burn_result *results)
+{
+    MH_ARG(dem && H >= 1 && W >= 1, "burn_lines_f32(dem, H>=1, W>=1, nseg, segments, nline, lines, nodata, results)");
+    MH_TRY(burn_check(nseg, segments, nline, lines, results));
+    if (nseg == 0) return burn_lines_dev(nullptr, H, W, 0, segments, nline, lines, nodata, results, 0);
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    const size_t n = (size_t)(H * W);
+    DevBuf d_dem;
+    MH_TRY(upload(d_dem, dem, n * 4, s));
+    MH_TRY(burn_lines_dev(d_dem.as<float>(), H, W, nseg, segments, nline, lines, nodata, results, s));
+    return download(dem, d_dem, n * 4, s);
 }
 
 int mhip_trace_downstream_i32(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, const int64_t *cells_rc, int64_t n,

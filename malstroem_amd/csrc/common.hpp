@@ -426,6 +426,12 @@ int wet_at_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t 
 bool flow_distance_scale_ok(double scale);      // finite and > 0
 int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int64_t W, double scale, int64_t nlab, float *d_out, mhip_index_record *d_rec,
                       int64_t *unresolved, hipStream_t s);
+// burn.hip: DEM adaptations.  burn_check: the argument rules of mhip_burn_lines_f32 on the host arrays (MHIP_EINVAL; no
+// device work).  burn_lines_dev: the checked lines into the float32 raster d_dem in place, the per-line records to `results` (host).
+// Synchronises.  nseg == 0 writes the records on the host and touches no device.
+int burn_check(int64_t nseg, const mhip_burn_segment *segs, int64_t nline, const mhip_burn_line *lines, const mhip_burn_result *results);
+int burn_lines_dev(float *d_dem, int64_t H, int64_t W, int64_t nseg, const mhip_burn_segment *segs, int64_t nline, const mhip_burn_line *lines,
+                   double nodata, mhip_burn_result *results, hipStream_t s);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,
                    bool band_mode = false, const unsigned int *d_known_interior_nodir = nullptr, const int32_t *d_src = nullptr, PourLink *pour = nullptr);

@@ -1,5 +1,5 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
-// getters, the per-label records, the label filter, hypsometry and final depths, and the one rule for what a write of a resident
+// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, and the one rule for what a write of a resident
 // raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
 #include <mutex>
 #include <string>
@@ -613,6 +613,20 @@ int mhip_ctx_flow_distance_records(mhip_ctx *c, mhip_index_record *records)
     MH_ARG(c && records, "ctx_flow_distance_records(ctx, records)");
     MH_ARG(c->fdist_unresolved >= 0 && c->fdist_rec.p, "ctx_flow_distance_records needs mhip_ctx_flow_distance on the resident flow directions and labels");
     return ctx_fetch(c, c->fdist_rec, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
+}
+
+/* ---- DEM adaptations: culvert and dike lines into the resident DEM (burn.hip) ---------------------------------------------------- */
+int mhip_ctx_burn_lines(mhip_ctx *c, int64_t nseg, const mhip_burn_segment *segments, int64_t nline, const mhip_burn_line *lines, double nodata,
+                        mhip_burn_result *results)
+{
+    MH_ARG(c, "ctx_burn_lines(ctx, nseg, segments, nline, lines, nodata, results)");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "DEM adaptations on a row band are not built (a line crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_DEM], "ctx_burn_lines needs the DEM raster");
+    MH_TRY(burn_check(nseg, segments, nline, lines, results));
+    if (nseg == 0) return burn_lines_dev(nullptr, c->H, c->W, 0, segments, nline, lines, nodata, results, nullptr);      // (the records; the context stays as it is)
+    MH_HIP(hipSetDevice(c->device));
+    ctx_wrote(c, MHIP_R_DEM, /*uploaded=*/true);
+    return burn_lines_dev(c->r[MHIP_R_DEM].as<float>(), c->H, c->W, nseg, segments, nline, lines, nodata, results, c->stream);
 }
 
 }  // extern "C"

@@ -17,14 +17,32 @@ class DemTool(object):
     ``write(array)``.  Input x, y, z must be in meters and cells must be square.
     """
 
-    def __init__(self, input_dem, output_filled, output_flowdir, output_depths, output_accum=None, device=0):
+    def __init__(self, input_dem, output_filled, output_flowdir, output_depths, output_accum=None, device=0, input_adaptations=None,
+                 output_adapted=None, output_adaptation_report=None):
         self.input_dem = input_dem
         self.output_filled = output_filled
         self.output_flowdir = output_flowdir
         self.output_depths = output_depths
         self.output_accum = output_accum
         self.device = device
+        # DEM adaptations (adaptations.py): a vector reader of culvert / dike lines burnt into the DEM before the fill, a raster writer
+        # for the adapted DEM, a vector writer for the lines with what became of them
+        self.input_adaptations = input_adaptations
+        self.output_adapted = output_adapted
+        self.output_adaptation_report = output_adaptation_report
         self.logger = logging.getLogger(__name__)
+
+    def _adapt(self, pipe, transform):
+        from .adaptations import lines_from_features, report_features
+        features = self.input_adaptations.read_geojson_features()
+        lines, segments, index = lines_from_features(features, transform, pipe.shape, with_index=True)
+        self.logger.info("Burning {} adaptation lines into the DEM".format(len(lines)))
+        nodata = getattr(self.input_dem, "nodatasubst", None)
+        results = pipe.burn_lines(lines, segments, nodata=nodata)
+        if self.output_adapted is not None:
+            pipe.download_to("dem", self.output_adapted)
+        if self.output_adaptation_report is not None:
+            self.output_adaptation_report.write_geojson_features(report_features(features, index, results))
 
     def process(self, keep_pipeline=False):
         streaming = hasattr(self.input_dem, "iter_windows") and hasattr(self.input_dem, "shape")
@@ -43,6 +61,8 @@ class DemTool(object):
                     pipe.upload_rows("dem", row0, window.astype(dtypes.DTYPE_DTM, casting='same_kind', copy=False))
             else:
                 pipe.upload("dem", dem)
+            if self.input_adaptations is not None:
+                self._adapt(pipe, transform)
             self.logger.info("Calculating filled DEM and bluespot depths")
             pipe.run("fill")
             pipe.download_to("filled", self.output_filled)

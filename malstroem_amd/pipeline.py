@@ -215,3 +215,15 @@ class HydroPipeline(CtxHandle):
     def download_flow_distance_to(self, writer, max_rows=4096):
         """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
         write_windows(writer, self.shape, np.float32, self.download_flow_distance_rows, max_rows)
+
+    # ---- DEM adaptations: culvert and dike lines into the resident DEM (adaptations.py; DESIGN.md 12) -----
+    def burn_lines(self, lines, segments, nodata=np.nan):
+        """Burn ``lines`` / ``segments`` (``adaptations.lines_from_features``) into the resident DEM in place: all lower lines, then all
+        raise lines.  Returns the per-line results (``_lib.BURN_RESULT_DTYPE``).  It is a write of the DEM: everything derived from
+        it is gone as after an upload, and the stages run again on the adapted DEM.  No segments: nothing changes."""
+        from .adaptations import check_lines, check_nodata
+        lines, segments = check_lines(lines, segments)
+        res = np.zeros(lines.size, dtype=_lib.BURN_RESULT_DTYPE)
+        _lib.call("mhip_ctx_burn_lines", self._ctx, _lib.i64(segments.size), _lib.ptr(segments), _lib.i64(lines.size), _lib.ptr(lines),
+                  ctypes.c_double(check_nodata(nodata)), _lib.ptr(res))
+        return res
