@@ -54,6 +54,14 @@ typedef struct { double z0, z1; int32_t ntotal, flags; } mhip_burn_line;
 typedef struct { double z0, z1; int64_t cells; int32_t status, pad; } mhip_burn_result;
 /* most rain events of one mhip_label_wet_at_f32 / mhip_ctx_wet_at call */
 #define MHIP_WETAT_MAX_EVENTS 16
+/* statistics of a float32 raster over one zone (mhip_zone_stats_f32 below): the largest value that is no NaN (-inf
+ * without one; a zero is +0.0), the smallest value > 0 (+inf without one), the cells, the cells > 0.  numpy
+ * [('vmax','<f8'),('vmin_pos','<f8'),('cells','<i8'),('pos','<i8')] */
+typedef struct { double vmax, vmin_pos; int64_t cells, pos; } mhip_zone_record;
+/* sources of mhip_ctx_zone_stats that are no member of enum mhip_raster: the raster of the last mhip_ctx_wet_at / of the last
+ * mhip_ctx_flow_distance */
+#define MHIP_ZSRC_WETAT 100
+#define MHIP_ZSRC_FLOWDIST 101
 
 /* ---- library / device ------------------------------------------------------------------------- */
 const char *mhip_last_error(void);
@@ -181,6 +189,24 @@ int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H,
  * explicit level that is infinite or beyond the float32 range, flags > 3, a negative count.  nseg == 0: nothing is burnt. */
 int mhip_burn_lines_f32(float *dem, int64_t H, int64_t W, int64_t nseg, const mhip_burn_segment *segments, int64_t nline,
                         const mhip_burn_line *lines, double nodata, mhip_burn_result *results);
+
+/* Polygons to a zone raster (no reference counterpart; the definition is tests/_zones.py).  xy[nvert][2]: (x, y) in
+ * cell coordinates, the centre of cell (r, c) is (c + 0.5, r + 0.5); ring_offsets[nring + 1]; ring_zone[nring] in 1 .. nzone: all
+ * rings of one id -- exterior rings, holes, parts -- form one object; a ring closes implicitly.  An edge, oriented so that y0 < y1
+ * (y0 == y1: never active), is active on row r when y0 <= r + 0.5 < y1 and crosses it at xc = x0 + (yc - y0) * (x1 - x0) / (y1 - y0)
+ * in float64, one rounding per operation; cf is the smallest integer c with c + 0.5 >= xc.  Cell (r, c) is inside zone z when the
+ * number of z's crossings on row r with cf <= c is odd (even-odd, top-left: an integer rectangle covers exactly its cells, two
+ * polygons that share an edge are watertight).  out_zones[H][W] (int32): the largest z a cell is inside, 0 for none; the result
+ * depends on no order of rings or vertices.  grow = 1: one step from that raster, a cell of zone 0 takes the largest zone among
+ * its 8 neighbours inside the raster.  MHIP_EINVAL before any device work: a coordinate that is not finite or beyond 2**29, offsets
+ * that do not start at 0, do not end at nvert or decrease, a ring of fewer than 3 vertices, a zone id outside [1, nzone], grow not
+ * in {0, 1}, a negative count.  nring == 0: the zero raster, no device is asked for.  MHIP_ELIMIT: more than 2**31 - 1 crossings
+ * within rows [0, H), or as many (zone, row) scanlines.  A row with k crossings of one zone costs k * k steps. */
+int mhip_rasterize_zones_i32(int64_t H, int64_t W, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
+                             const int32_t *ring_zone, int64_t nzone, int32_t grow, int32_t *out_zones);
+/* records[nzone + 1] of the n cells of `data` (rows of W; W = 0: a flat array) over `zones`; record 0 is the background.  Exact:
+ * there is no sum.  A NaN is neither positive nor a maximum.  MHIP_EINVAL: a zone id outside [0, nzone]. */
+int mhip_zone_stats_f32(const float *data, const int32_t *zones, int64_t n, int64_t W, int64_t nzone, mhip_zone_record *records);
 
 /* net.next_downstream_label(flowdir, labeled, cell, background_label, geometry) for a BATCH of cells -- what
  * net.pourpoint_network / geometric_pourpoint_network loop over (reference net.py:142-192, 195-224).  cells_rc: n (row, col)
@@ -487,6 +513,16 @@ int mhip_ctx_flow_distance_records(mhip_ctx *ctx, mhip_index_record *records);
  * DEM).  nseg == 0 leaves the context as it is. */
 int mhip_ctx_burn_lines(mhip_ctx *ctx, int64_t nseg, const mhip_burn_segment *segments, int64_t nline, const mhip_burn_line *lines,
                         double nodata, mhip_burn_result *results);
+/* mhip_rasterize_zones_i32 at the shape of an undivided context (a row band is refused): the zone raster and nzone stay in a buffer
+ * of the context (no member of enum mhip_raster).  The zones come from outside: no write of a raster drops them, a new rasterize
+ * replaces them.  zones_rows copies rows [row0, row0 + nrows) of the raster.  zone_stats: mhip_zone_stats_f32 of a resident
+ * float32 raster over the zones, records[nzone + 1]; source: MHIP_R_DEM, MHIP_R_FILLED, MHIP_R_DEPTHS, MHIP_R_FINALDEPTHS,
+ * MHIP_ZSRC_WETAT or MHIP_ZSRC_FLOWDIST; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
+ * without zones.  mhip_ctx_get_i64 "zones": nzone of the raster held, -1: none. */
+int mhip_ctx_rasterize_zones(mhip_ctx *ctx, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
+                             const int32_t *ring_zone, int64_t nzone, int32_t grow);
+int mhip_ctx_zones_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, int32_t *dst);
+int mhip_ctx_zone_stats(mhip_ctx *ctx, int32_t source, mhip_zone_record *records);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,10 @@ BURN_SEGMENT_DTYPE = np.dtype([("r0", "<i4"), ("c0", "<i4"), ("r1", "<i4"), ("c1
 BURN_LINE_DTYPE = np.dtype([("z0", "<f8"), ("z1", "<f8"), ("ntotal", "<i4"), ("flags", "<i4")])
 BURN_RESULT_DTYPE = np.dtype([("z0", "<f8"), ("z1", "<f8"), ("cells", "<i8"), ("status", "<i4"), ("pad", "<i4")])
 
+# object exposure (objects.py): mhip_zone_record; sources of mhip_ctx_zone_stats that are no member of mhip_raster
+ZONE_DTYPE = np.dtype([("vmax", "<f8"), ("vmin_pos", "<f8"), ("cells", "<i8"), ("pos", "<i8")])
+ZSRC_WETAT, ZSRC_FLOWDIST = 100, 101
+
 WETAT_MAX_EVENTS = 16     # MHIP_WETAT_MAX_EVENTS: most rain events of one wet_at call
 
 OK, EINVAL, EHIP, ENODEV, ELIMIT, ENOTCONV, ECOMM = 0, -1, -2, -3, -4, -5, -6
@@ -60,6 +64,7 @@ SYMBOLS = [
     "mhip_ctx_final_depths", "mhip_label_wet_at_f32", "mhip_ctx_wet_at", "mhip_ctx_wet_at_rows",
     "mhip_flow_distance", "mhip_ctx_flow_distance", "mhip_ctx_flow_distance_rows", "mhip_ctx_flow_distance_records",
     "mhip_burn_lines_f32", "mhip_ctx_burn_lines",
+    "mhip_rasterize_zones_i32", "mhip_zone_stats_f32", "mhip_ctx_rasterize_zones", "mhip_ctx_zones_rows", "mhip_ctx_zone_stats",
 ]
 
 _lib = None

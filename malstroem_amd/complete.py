@@ -87,7 +87,8 @@ def parse_filter(filter):
 
 
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
-                finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, adaptations=None):
+                finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
+                adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -112,7 +113,16 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     ``adaptations``: the path of a GeoJSON file of culvert / dike lines (``adaptations.lines_from_features`` names the properties)
     that are burnt into the DEM before anything is computed; also writes ``dem_adapted.tif`` and the vector layer ``adaptations``:
     the lines with ``status``, ``z_from_used``, ``z_to_used`` and ``cells``; the dict gains ``dem_adapted`` and ``adaptations``.  Not
-    on row bands yet."""
+    on row bands yet.
+
+    ``objects``: the path of a GeoJSON file of ``Polygon`` / ``MultiPolygon`` features -- buildings, parcels, road sections.  They are
+    rasterized on the device at the DEM's grid (``objects.rings_from_features``; ``objects_grow=1`` lets every object take the free
+    cells around it: where buildings stand as blocks in the DEM the water is beside the footprint), and the vector layer ``objects``
+    gives every feature ``cells``, ``bs_dmax`` (the largest bluespot depth on its cells) and ``bs_wet_cells`` (its cells inside a
+    bluespot), with ``onset`` ``wet_at_mm`` (the smallest rain that leaves water on one of its cells; null: none does) and with the
+    final rasters ``depth_<mm:g>`` (the largest final depth on its cells) per event; the dict gains ``objects``.  Every other output is
+    what it is without the argument.  Not on row bands yet.  (``objects``, ``objects_grow`` and ``adaptations`` are taken by keyword
+    only.)"""
     if vector:
         raise NotImplementedError("vectorisation of bluespots / watersheds (GDAL polygonize) is outside malstroem_amd's hot path")
     if (onset or not final_rasters) and not finalstate:
@@ -127,7 +137,12 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         if adaptations is not None:
             raise NotImplementedError("adaptations on row bands: a line crosses the seams between the bands, and its levels hang on "
                                       "both of its ends, which is not built yet; run it on one context")
+        if objects is not None:
+            raise NotImplementedError("objects on row bands: an object crosses the seams between the bands, and the zone raster of a "
+                                      "band is not built yet; run it on one context")
         return _process_all_bands(dem, outdir, rain, accum, filter, comm, device, nodatasubst, backend_factory)
+    if objects is not None and objects_grow not in (0, 1):
+        raise ValueError("objects_grow must be 0 or 1, got %r" % (objects_grow,))
     if not os.path.isdir(outdir) or os.listdir(outdir):
         raise ValueError("outdir isn't an empty directory")
     outvector = os.path.join(outdir, 'vector')
@@ -169,6 +184,19 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         nodes_writer = io.VectorWriter('GeoJSON', outvector, 'nodes', None, None, crs)
         streams_writer = io.VectorWriter('GeoJSON', outvector, 'streams', None, None, crs)
         StreamTool(pourpoints_reader, dem_reader, dem_reader, nodes_writer, streams_writer, pipeline=pipe).process()
+        object_features = None
+        if objects is not None:
+            # Objects: the zone raster stays on the device next to the depths (and, below, the final state)
+            from .objects import rings_from_features
+            object_features = [dict(f, properties=dict(f.get("properties") or {})) for f in io.VectorReader(objects).read_geojson_features()]
+            xy, ring_offsets, ring_zone, nzone = rings_from_features(object_features, tr)
+            logger.info("Rasterizing {} objects".format(nzone))
+            pipe.rasterize_zones(xy, ring_offsets, ring_zone, nzone, grow=objects_grow)
+            zrec = pipe.zone_stats("depths")
+            for k, f in enumerate(object_features):
+                # (an object that covers no cell centre has no largest depth: null)
+                f["properties"].update(cells=int(zrec["cells"][k + 1]), bs_dmax=float(zrec["vmax"][k + 1]) if zrec["cells"][k + 1] else None,
+                                       bs_wet_cells=int(zrec["pos"][k + 1]))
         if not finalstate:
             pipe.close()
         # Process rain events
@@ -188,6 +216,10 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
 
             def depths_writer_for(tag):
                 written[tag] = os.path.join(outdir, 'finaldepths_{}.tif'.format(tag))
+                if object_features is not None:      # (asked for when the event's depths are resident: the moment to reduce them)
+                    zrec = pipe.zone_stats("finaldepths")
+                    for k, f in enumerate(object_features):
+                        f["properties"]["depth_" + tag] = float(zrec["vmax"][k + 1]) if zrec["cells"][k + 1] else None
                 return io.RasterWriter(written[tag], tr, crs)
             final_writer = io.VectorWriter('GeoJSON', outvector, 'finalstate', None, None, crs)
             onset_path = os.path.join(outdir, 'wet_at.tif')
@@ -197,6 +229,14 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
             res.update(finalstate=final_writer.filepath, finaldepths=written)
             if onset:
                 res["wet_at"] = onset_path
+                if object_features is not None:
+                    zrec = pipe.zone_stats("wet_at") if pipe.get_int("wet_at_events") > 0 else None      # (None: a series of no event)
+                    for k, f in enumerate(object_features):
+                        f["properties"]["wet_at_mm"] = float(zrec["vmin_pos"][k + 1]) if zrec is not None and zrec["pos"][k + 1] else None
+        if object_features is not None:
+            objects_writer = io.VectorWriter('GeoJSON', outvector, 'objects', None, None, crs)
+            objects_writer.write_geojson_features(object_features)
+            res["objects"] = objects_writer.filepath
     finally:
         pipe.close()
         dem_reader.close()

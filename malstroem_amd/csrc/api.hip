@@ -1,6 +1,6 @@
 // api.hip -- the host-raster entry points of libmalstroem_hip.so (declared in include/malstroem_hip.h): upload -> stage -> download,
 // one per malstroem.algorithms stage function, over the device-pointer stage implementations (fill.hip, d8.hip, accum.hip, ccl.hip,
-// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
+// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, zones.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
 #include <vector>
 
 #include "common.hpp"
@@ -419,6 +419,37 @@ int mhip_burn_lines_f32(float *dem, int64_t H, int64_t W, int64_t nseg, const mh
     MH_TRY(upload(d_dem, dem, n * 4, s));
     MH_TRY(burn_lines_dev(d_dem.as<float>(), H, W, nseg, segments, nline, lines, nodata, results, s));
     return download(dem, d_dem, n * 4, s);
+}
+
+int mhip_rasterize_zones_i32(int64_t H, int64_t W, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
+                             const int32_t *ring_zone, int64_t nzone, int32_t grow, int32_t *out_zones)
+{
+    MH_ARG(out_zones, "rasterize_zones_i32(H, W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow, out)");
+    MH_TRY(zones_check(H, W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow));
+    const size_t n = (size_t)(H * W);
+    if (nring == 0) {
+        std::memset(out_zones, 0, 4 * n);
+        return MHIP_OK;
+    }
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    DevBuf d_out;
+    MH_TRY(d_out.alloc(4 * n));
+    MH_TRY(zones_rasterize_dev(d_out.as<int32_t>(), H, W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow, s));
+    return download(out_zones, d_out, 4 * n, s);
+}
+
+int mhip_zone_stats_f32(const float *data, const int32_t *zones, int64_t n, int64_t W, int64_t nzone, mhip_zone_record *records)
+{
+    MH_ARG(data && zones && records && n >= 1 && W >= 0 && nzone >= 0 && nzone <= 0x7fffffff, "zone_stats_f32(data, zones, n>=1, W>=0, 0<=nzone<2**31, records)");
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    DevBuf d_d, d_z, d_r;
+    MH_TRY(upload(d_d, data, (size_t)n * 4, s));
+    MH_TRY(upload(d_z, zones, (size_t)n * 4, s));
+    MH_TRY(d_r.alloc(sizeof(mhip_zone_record) * (size_t)(nzone + 1)));
+    MH_TRY(zone_stats_dev(d_d.as<float>(), d_z.as<int32_t>(), n, W, nzone, d_r.as<mhip_zone_record>(), s));
+    return download(records, d_r, sizeof(mhip_zone_record) * (size_t)(nzone + 1), s);
 }
 
 int mhip_trace_downstream_i32(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, const int64_t *cells_rc, int64_t n,

@@ -432,6 +432,15 @@ int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int6
 int burn_check(int64_t nseg, const mhip_burn_segment *segs, int64_t nline, const mhip_burn_line *lines, const mhip_burn_result *results);
 int burn_lines_dev(float *d_dem, int64_t H, int64_t W, int64_t nseg, const mhip_burn_segment *segs, int64_t nline, const mhip_burn_line *lines,
                    double nodata, mhip_burn_result *results, hipStream_t s);
+// zones.hip: object exposure.  zones_check: the argument rules of mhip_rasterize_zones_i32 on the host arrays
+// (MHIP_EINVAL; no device work).  zones_rasterize_dev: the checked polygons into the int32 raster d_out (every cell is written);
+// MHIP_ELIMIT: too many crossings.  zone_stats_dev: nzone + 1 records of d_data over d_zones; MHIP_EINVAL: a zone outside
+// [0, nzone].  Both synchronise.
+int zones_check(int64_t H, int64_t W, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets, const int32_t *ring_zone,
+                int64_t nzone, int grow);
+int zones_rasterize_dev(int32_t *d_out, int64_t H, int64_t W, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
+                        const int32_t *ring_zone, int64_t nzone, int grow, hipStream_t s);
+int zone_stats_dev(const float *d_data, const int32_t *d_zones, int64_t n, int64_t W, int64_t nzone, mhip_zone_record *d_rec, hipStream_t s);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,
                    bool band_mode = false, const unsigned int *d_known_interior_nodir = nullptr, const int32_t *d_src = nullptr, PourLink *pour = nullptr);

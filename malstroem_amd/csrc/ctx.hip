@@ -1,6 +1,6 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
-// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, and the one rule for what a write of a resident
-// raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
+// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, and the one
+// rule for what a write of a resident raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
 #include <mutex>
 #include <string>
 #include <vector>
@@ -408,6 +408,7 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
     else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels
     else if (k == "flow_distance_unresolved") *value = c->fdist_unresolved;   // -1: no result of mhip_ctx_flow_distance on the resident flow directions and labels
+    else if (k == "zones") *value = c->nzone;                        // -1: no zone raster of mhip_ctx_rasterize_zones
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
     else {
@@ -627,6 +628,62 @@ int mhip_ctx_burn_lines(mhip_ctx *c, int64_t nseg, const mhip_burn_segment *segm
     MH_HIP(hipSetDevice(c->device));
     ctx_wrote(c, MHIP_R_DEM, /*uploaded=*/true);
     return burn_lines_dev(c->r[MHIP_R_DEM].as<float>(), c->H, c->W, nseg, segments, nline, lines, nodata, results, c->stream);
+}
+
+/* ---- object exposure: polygons to a zone raster of the context, statistics of a resident raster per zone (zones.hip) -------------- */
+int mhip_ctx_rasterize_zones(mhip_ctx *c, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets, const int32_t *ring_zone,
+                             int64_t nzone, int32_t grow)
+{
+    MH_ARG(c, "ctx_rasterize_zones(ctx, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow)");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
+    MH_TRY(zones_check(c->H, c->W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow));
+    MH_HIP(hipSetDevice(c->device));
+    c->nzone = -1;
+    MH_TRY(c->zones.alloc(4 * (size_t)(c->H * c->W)));
+    if (nring == 0) {
+        MH_HIP(hipMemsetAsync(c->zones.p, 0, 4 * (size_t)(c->H * c->W), c->stream));
+        MH_HIP(stream_sync(c->stream));
+    } else {
+        MH_TRY(zones_rasterize_dev(c->zones.as<int32_t>(), c->H, c->W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow, c->stream));      // (synchronises)
+    }
+    c->nzone = nzone;
+    return MHIP_OK;
+}
+
+int mhip_ctx_zones_rows(mhip_ctx *c, int64_t row0, int64_t nrows, int32_t *dst)
+{
+    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_zones_rows(ctx, row0, nrows, dst)");
+    MH_ARG(c->nzone >= 0 && c->zones.p, "ctx_zones_rows needs mhip_ctx_rasterize_zones");
+    return ctx_copy_rows(c, c->zones.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+}
+
+int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
+{
+    MH_ARG(c && records, "ctx_zone_stats(ctx, source, records)");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
+    const float *src = nullptr;
+    switch (source) {
+    case MHIP_R_DEM: case MHIP_R_FILLED: case MHIP_R_DEPTHS: case MHIP_R_FINALDEPTHS:
+        MH_ARG(c->have[source], "raster has not been computed or uploaded");
+        src = c->r[source].as<float>();
+        break;
+    case MHIP_ZSRC_WETAT:
+        MH_ARG(c->wetat_events > 0 && c->wetat_out.p, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels");
+        src = c->wetat_out.as<float>();
+        break;
+    case MHIP_ZSRC_FLOWDIST:
+        MH_ARG(c->fdist_unresolved >= 0 && c->fdist_out.p, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels");
+        src = c->fdist_out.as<float>();
+        break;
+    default:
+        MH_ARG(false, "ctx_zone_stats: the source is no float32 raster of the context");
+    }
+    MH_ARG(c->nzone >= 0 && c->zones.p, "ctx_zone_stats needs mhip_ctx_rasterize_zones");
+    MH_HIP(hipSetDevice(c->device));
+    DevBuf d_rec;
+    MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(c->nzone + 1)));
+    MH_TRY(zone_stats_dev(src, c->zones.as<int32_t>(), c->H * c->W, c->W, c->nzone, d_rec.as<mhip_zone_record>(), c->stream));
+    return ctx_fetch(c, d_rec, sizeof(mhip_zone_record) * (size_t)(c->nzone + 1), records);
 }
 
 }  // extern "C"

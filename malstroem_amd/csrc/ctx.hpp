@@ -118,6 +118,10 @@ struct mhip_ctx {
     mh::DevBuf fdist_out, fdist_rec;
     std::atomic<int64_t> fdist_unresolved{-1};
     std::mutex fdist_mu;
+    // the zone raster (int32, H x W; not a member of mhip_raster) of the last mhip_ctx_rasterize_zones and its number of zones; -1:
+    // none.  It comes from outside: no write of a raster drops it
+    mh::DevBuf zones;
+    int64_t nzone = -1;
     double sh = 0, dg = 0;
     int32_t fill_rounds = 0, noflat_rounds = 0;
     mh::FillStats fill_st, noflat_st;

@@ -227,3 +227,42 @@ class HydroPipeline(CtxHandle):
         _lib.call("mhip_ctx_burn_lines", self._ctx, _lib.i64(segments.size), _lib.ptr(segments), _lib.i64(lines.size), _lib.ptr(lines),
                   ctypes.c_double(check_nodata(nodata)), _lib.ptr(res))
         return res
+
+    # ---- object exposure: polygons to a zone raster, a resident raster reduced per zone (objects.py) -----
+    ZONE_SOURCES = {"dem": _lib.R_DEM, "filled": _lib.R_FILLED, "depths": _lib.R_DEPTHS, "finaldepths": _lib.R_FINALDEPTHS,
+                    "wet_at": _lib.ZSRC_WETAT, "flow_distance": _lib.ZSRC_FLOWDIST}
+
+    def rasterize_zones(self, xy, ring_offsets, ring_zone, nzone, grow=0):
+        """Rasterize polygons (``objects.rings_from_features``) at the pipeline's shape; the zone raster stays on the device for
+        ``zone_stats`` and ``download_zones``.  The zones come from outside: no upload, stage or adaptation drops them, a new call
+        replaces them."""
+        from .objects import check_rings
+        xy, off, zone, nzone, grow = check_rings(xy, ring_offsets, ring_zone, nzone, grow)
+        _lib.call("mhip_ctx_rasterize_zones", self._ctx, _lib.i64(xy.shape[0]), _lib.ptr(xy), _lib.i64(zone.size), _lib.ptr(off), _lib.ptr(zone),
+                  _lib.i64(nzone), int(grow))
+
+    def zone_stats(self, source):
+        """``nzone + 1`` records (``_lib.ZONE_DTYPE``) of a resident float32 raster over the zones: ``source`` is ``"dem"``,
+        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"`` or ``"flow_distance"``.  ``ValueError`` without zones or when the
+        source has not been computed."""
+        if source not in self.ZONE_SOURCES:
+            raise ValueError("source must be one of %s, got %r" % (sorted(self.ZONE_SOURCES), source))
+        nzone = self.get_int("zones")
+        if nzone < 0:
+            raise ValueError("rasterize_zones() has not been run")
+        rec = np.zeros(nzone + 1, dtype=_lib.ZONE_DTYPE)
+        _lib.call("mhip_ctx_zone_stats", self._ctx, ctypes.c_int32(self.ZONE_SOURCES[source]), _lib.ptr(rec))
+        return rec
+
+    def download_zones_rows(self, row0, nrows):
+        out = np.empty((int(nrows), self.shape[1]), dtype=np.int32)
+        _lib.call("mhip_ctx_zones_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
+        return out
+
+    def download_zones(self):
+        """The zone raster of the last ``rasterize_zones`` (int32); ``ValueError`` when there is none."""
+        return self.download_zones_rows(0, self.shape[0])
+
+    def download_zones_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.int32, self.download_zones_rows, max_rows)
