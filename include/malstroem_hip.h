@@ -472,6 +472,9 @@ int mhip_ctx_stage_ms(mhip_ctx *ctx, int stage, float *ms);
 int mhip_ctx_kernel_ms(mhip_ctx *ctx, const char *kernel, float *ms_total, int32_t *launches);
 /* "nlabels_raw", "nlabels", "fill_rounds", "fill_launches", "fill_visits", "noflat_rounds", "noflat_visits", ... and which engine
  * the last run of a stage took: "fill_algorithm" (1 tiled priority-flood, 0 iterative schedule, 4 flood + iterative repair),
+ * "fill_overflow" (why a flood that was tried handed the raster to the iterative schedule, one bit per capacity: 1 basins per
+ * tile, 2 basin-pair hash, 4 seeds per tile, 8 seed-pair hash / spill edges per tile, 16 link hash / links per tile,
+ * 32 relaxations per block of 4 x 4 tiles, 64 halo links of a band's tile; 0: the flood ran through or was not tried),
  * "noflat_algorithm" (2 integer geodesic transform, 3 + float64 relaxation of irregular flats, 0 float64 relaxation; why a
  * transform was handed back: "noflat_reject*"), "pour_algorithm" (1 keys out of the accumulation's final pass, 0 a pass over
  * values + labels), "accum_algorithm" (row bands: 1 the second pass as a delta over the boundary pass's graph, 0 a full pass) */

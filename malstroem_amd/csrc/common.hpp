@@ -170,6 +170,8 @@ struct FillStats {
     int32_t hot_launches = 0;   // the ng_round_kernel launches (the span of the round loop: compaction launches and gaps included)
     int32_t algorithm = 0;  // 0: iterative tile schedule (fill.hip), 1: tiled priority-flood (pflood.hip; rounds = kernel launches),
                             // 2: integer geodesic transform (noflat_geo.hip)
+    uint32_t overflow = 0;  // plain fill: the capacities that gave out in the last attempt of the priority-flood (pflood.hip: PF_OV_*); 0: it
+                            // ran through, or was not tried
     // the priority-flood reads every DEM cell anyway: smallest / largest elevation of the local raster and "holds a NaN" ride along
     bool have_minmax = false, dem_nan = false;
     float dem_min = 0.0f, dem_max = 0.0f;
@@ -212,7 +214,8 @@ int fill_plain_dev(const float *d_dem, float *d_out, int64_t H, int64_t W, hipSt
 int fill_check_f32_dev(const float *d_dem, const float *d_filled, int64_t H, int64_t W, int fixed_top, int fixed_bot, hipStream_t s,
                        unsigned int *d_flag);
 // pflood.hip
-int fill_plain_pflood_dev(const float *d_dem, float *d_out, float *d_depths, int64_t H, int64_t W, hipStream_t s, FillStats *st, bool *violated = nullptr);
+int fill_plain_pflood_dev(const float *d_dem, float *d_out, float *d_depths, int64_t H, int64_t W, hipStream_t s, FillStats *st, bool *violated = nullptr,
+                          uint32_t *overflow = nullptr);
 // pflood.hip: the exact tiled priority-flood, resumable for row bands (whose halo rows of `out` carry the neighbours' current
 // estimates of their filled edge rows; this band's own edge rows in `out` are kept current for them)
 struct PfRun {
@@ -220,6 +223,7 @@ struct PfRun {
     float *out = nullptr;            // the filled surface
     int64_t H = 0, W = 0;
     int fixed_top = 0, fixed_bot = 0;
+    uint32_t overflow = 0;           // the capacities that gave out (the flags word as the last solve read it); begin / batch then return MHIP_ELIMIT
     struct Impl;
     Impl *impl;
     PfRun();

@@ -79,6 +79,7 @@ struct mhip_ctx {
     int ht = 0, hb = 0;     // 1 if a halo row (copy of the neighbouring band's edge row) sits above / below the owned rows
     mh::FillRun *run[2] = {nullptr, nullptr};   // resumable fill (plain, no-flats) in band mode
     mh::GeoRun *geo = nullptr;                  // ... and the geodesic no-flats fill
+    uint32_t pf_overflow = 0;                   // the capacities that sent this band's flood to the iterative schedule (fill_begin / fill_batch)
     mh::PfRun *pf = nullptr;                    // ... and the tiled priority-flood (plain fill)
     bool pf_done = false;                   // the flood's raster is written and proven (mhip_ctx_fill_certify); run[0] may follow it
     mh::DevBuf nodir_cnt;                   // interior NODIR cells of FLOWDIR, counted by the D8 kernel (the watersheds' fast-path test)

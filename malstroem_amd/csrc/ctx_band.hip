@@ -651,6 +651,7 @@ int mhip_ctx_fill_begin(mhip_ctx *c, int kind, double short_, double diag, int32
         c->pf = nullptr;
         c->pf_done = false;
         c->pf_depths = false;
+        c->pf_overflow = 0;
         if (!force_iter) {
             PfRun *p = new PfRun();
             p->dem = c->r[MHIP_R_DEM].as<float>();
@@ -663,6 +664,7 @@ int mhip_ctx_fill_begin(mhip_ctx *c, int kind, double short_, double diag, int32
                 *active = 0;
                 return MHIP_OK;
             }
+            c->pf_overflow = p->overflow;
             delete p;
             if (rc != MHIP_ELIMIT) return rc;
         }
@@ -732,6 +734,7 @@ int mhip_ctx_fill_batch(mhip_ctx *c, int kind, int32_t *active)
         if (rc != MHIP_ELIMIT) return rc;
         // a capacity gave out while the halo links were rebuilt: start the iterative schedule instead (its edge rows are upper
         // bounds of the final surface like the ones published so far: the neighbours' state stays valid)
+        c->pf_overflow = c->pf->overflow;
         delete c->pf;
         c->pf = nullptr;
         bool a0 = false;
@@ -816,7 +819,10 @@ int mhip_ctx_fill_end(mhip_ctx *c, int kind)
             st.algorithm = 4;
         }
     }
-    if (kind == 0) c->pf_done = false;
+    if (kind == 0) {
+        c->pf_done = false;
+        st.overflow = c->pf_overflow;
+    }
     if (kind) { c->noflat_rounds = st.rounds; c->noflat_st = st; ctx_wrote(c, MHIP_R_NOFLAT); c->have[MHIP_R_NOFLAT] = true; }
     else {
         c->fill_rounds = st.rounds; c->fill_st = st; c->have[MHIP_R_FILLED] = true;

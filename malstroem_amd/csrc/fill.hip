@@ -1042,9 +1042,10 @@ int fill_plain_dev(const float *d_dem, float *d_out, int64_t H, int64_t W, hipSt
 {
     const bool force_iter = [] { const char *e = dev_env("MHIP_FILL"); return e && std::string(e) == "iterative"; }();   // (development: engine selection for A/B runs and tests)
     if (depths_done) *depths_done = false;
+    uint32_t overflow = 0;      // the flood's capacities that gave out, if it was tried (FillStats::overflow)
     if (!force_iter && H >= 3 && W >= 3) {
         bool violated = false;
-        const int rc = fill_plain_pflood_dev(d_dem, d_out, d_depths, H, W, s, st, &violated);
+        const int rc = fill_plain_pflood_dev(d_dem, d_out, d_depths, H, W, s, st, &violated, &overflow);
         if (rc == MHIP_OK && !violated) {
             if (depths_done) *depths_done = d_depths != nullptr;
             if (st) st->algorithm = 1;
@@ -1073,7 +1074,9 @@ int fill_plain_dev(const float *d_dem, float *d_out, int64_t H, int64_t W, hipSt
     }
     FillRun f;
     f.noflat = false; f.dem = d_dem; f.out = d_out; f.H = H; f.W = W;
-    return fill_run_to_convergence(f, s, st);
+    MH_TRY(fill_run_to_convergence(f, s, st));
+    if (st) st->overflow = overflow;
+    return MHIP_OK;
 }
 
 // No-flats fill.  With `d_filled` (the plain fill F of the same DEM) the iteration starts from the pointwise

@@ -50,6 +50,9 @@ constexpr int LH = 1024;           // link hash entries
 constexpr uint32_t KINV = 0xFFFFFFFFu;   // key of a cell outside the raster (above +inf)
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 constexpr int OCEAN = 255, NOLAB = 254;
+// which capacity gave out, one bit each in flags[0] (the host only asks "any?"; the mask is reported as "fill_overflow"):
+// basins per tile | basin-pair hash | seeds per tile | seed-pair hash, spill edges | link hash, links | relaxations per block | halo links
+constexpr unsigned PF_OV_NB = 1u, PF_OV_PAIRS = 2u, PF_OV_NS = 4u, PF_OV_SPILL = 8u, PF_OV_LINKS = 16u, PF_OV_EMAX = 32u, PF_OV_HALO = 64u;
 constexpr uint8_t C_VALID = 1, C_BORDER = 2, C_RING = 4;
 
 struct PfArgs {
@@ -392,7 +395,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         NB += s_scan[w];
     }
     if (NB > NBMAX) {         // block-uniform
-        if (t == 0) atomicOr(a.flags, 1u);
+        if (t == 0) atomicOr(a.flags, PF_OV_NB);
         return;
     }
 #pragma unroll
@@ -569,7 +572,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 #endif
     }
     if (wg_or(overflow)) {
-        if (t == 0) atomicOr(a.flags, 1u);
+        if (t == 0) atomicOr(a.flags, PF_OV_PAIRS);
         return;
     }
     PF_STAMP(4);
@@ -681,7 +684,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     }
     __syncthreads();
     if (NS > NSMAX) {   // block-uniform
-        if (t == 0) atomicOr(a.flags, 1u);
+        if (t == 0) atomicOr(a.flags, PF_OV_NS);
         return;
     }
     for (int sI = t; sI < NB; sI += NT) {
@@ -732,7 +735,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         else ov2 = true;
     }
     if (wg_or(ov2)) {
-        if (t == 0) atomicOr(a.flags, 1u);
+        if (t == 0) atomicOr(a.flags, PF_OV_SPILL);
         return;
     }
     for (int i = s_cnt + t; i < SPMAX; i += NT) a.spill[(size_t)tile * SPMAX + i] = ~0ull;
@@ -768,9 +771,14 @@ __global__ __launch_bounds__(256) void pf_ring_kernel(PfArgs a)
         if (!(r <= 0 || r >= a.H - 1 || c <= 0 || c >= a.W - 1)) {          // inside the raster and not a raster border cell
             const int oi = (int)((r - 1) / TI), oj = (int)((c - 1) / TI);     // the tile that owns the cell
             const int ot = oi * a.ntc + oj;
-            const uint32_t labX = a.ringLab[(size_t)tile * 256 + t];
-            const int so = min((int)a.bslot[r * a.W + c], NBMAX - 1);          // (a tile that gave up on a capacity wrote no slots: stay inside the tables)
-            const uint32_t labO = a.tabL[(size_t)ot * NBMAX + so];
+            // (a tile that gave up on a capacity wrote no slots, left NOLAB in its ring labels and ring positions, 0xff or whatever
+            // the pool held in its seed table: the result is thrown away, but a label is an index into the 128 levels of a tile in
+            // the solve's LDS -- what is no compact seed index reads as OCEAN, which pf_link2_kernel / pf_pack_kernel never index with)
+            uint32_t labX = a.ringLab[(size_t)tile * 256 + t];
+            const int so = min((int)a.bslot[r * a.W + c], NBMAX - 1);          // (... stay inside the tables)
+            uint32_t labO = a.tabL[(size_t)ot * NBMAX + so];
+            labX = labX < (uint32_t)NSMAX ? labX : (uint32_t)OCEAN;
+            labO = labO < (uint32_t)NSMAX ? labO : (uint32_t)OCEAN;
             const uint32_t w = max(dem_key(a.dem[r * a.W + c]), a.tabV[(size_t)ot * NBMAX + so]);
             rec = ((unsigned long long)labX << 40) | ((unsigned long long)labO << 32) | w;
         }
@@ -841,7 +849,7 @@ __global__ __launch_bounds__(256) void pf_link2_kernel(PfArgs a)
         else ov = true;
     }
     if (__syncthreads_or(ov)) {
-        if (t == 0) atomicOr(a.flags, 1u);
+        if (t == 0) atomicOr(a.flags, PF_OV_LINKS);
         return;
     }
     for (int i = s_cnt + t; i < LMAX; i += 256) a.links[(size_t)tile * LMAX + i] = ~0ull;
@@ -913,7 +921,7 @@ __global__ __launch_bounds__(ST) void pf_pack_kernel(SolveArgs sa)
     }
     __syncthreads();
     if (s_seg[BT * BT] > EMAX) {   // block-uniform; more relaxations than a visit holds (6144 ~ 16 x 380): tell the caller to fall back
-        if (t == 0) atomicOr(a.flags, 1u);
+        if (t == 0) atomicOr(a.flags, PF_OV_EMAX);
         return;
     }
     if (t == 0 && sa.ecount) sa.ecount[blk] = s_seg[BT * BT];
@@ -1579,7 +1587,7 @@ __global__ __launch_bounds__(128) void pf_halo_links_kernel(PfArgs a, const floa
     if (t < NSMAX && minw[t] != EMPTY && minw[t] < f32_key(__builtin_inff())) {
         const int i = nl0 + atomicAdd(&s_n, 1);
         if (i < LMAX) a.links[(size_t)tile * LMAX + i] = ((unsigned long long)((uint32_t)t << 16 | 4u << 8 | (uint32_t)OCEAN) << 32) | minw[t];
-        else atomicOr(a.flags, 1u);
+        else atomicOr(a.flags, PF_OV_HALO);
     }
     __syncthreads();
     const int n = min(nl0 + s_n, LMAX);
@@ -1727,6 +1735,7 @@ int PfRun::solve(hipStream_t s)
         const PfQueue *hq = reinterpret_cast<const PfQueue *>(h_hdr);
         const unsigned int h_q[4] = {hq->head, hq->tail, hq->finished, hq->abort};
         h_flag = hq->flags[0];
+        overflow = h_flag;
         if (!m.mm_valid) { m.h_mm[0] = hq->mm[0]; m.h_mm[1] = hq->mm[1]; }
         m.mm_valid = true;
         m.solved_once = true;
@@ -1775,6 +1784,7 @@ int PfRun::solve(hipStream_t s)
         if (!m.mm_valid) MH_HIP(hipMemcpyAsync(m.h_mm, m.mmout, 8, hipMemcpyDeviceToHost, s));
         MH_HIP(stream_sync(s));
         m.mm_valid = true;
+        overflow = h_flag;
         if (h_flag) return MHIP_ELIMIT;
         if (dev_env("MHIP_PF_DEBUG")) {
             fprintf(stderr, "[pf_solve] rounds %d..%d appended work:", m.round, m.round + PF_BATCH - 1);
@@ -2054,11 +2064,14 @@ int PfRun::finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated)
 
 // Exact tiled priority-flood on one raster.  Returns MHIP_ELIMIT (without touching d_out) when a per-tile capacity was
 // exceeded: the caller then runs the iterative schedule.
-int fill_plain_pflood_dev(const float *d_dem, float *d_out, float *d_depths, int64_t H, int64_t W, hipStream_t s, FillStats *st, bool *violated)
+int fill_plain_pflood_dev(const float *d_dem, float *d_out, float *d_depths, int64_t H, int64_t W, hipStream_t s, FillStats *st, bool *violated,
+                          uint32_t *overflow)
 {
     PfRun f;
     f.dem = d_dem; f.out = d_out; f.H = H; f.W = W;
-    MH_TRY(f.begin(s));
+    const int rc = f.begin(s);
+    if (overflow) *overflow = f.overflow;
+    if (rc != MHIP_OK) return rc;
     return f.finish(s, d_depths, st, violated);
 }
 

@@ -28,6 +28,7 @@ def run_bands(dem, nbands, align=True):
             out[comm.rank]["short_diag"] = (p.short, p.diag)
             out[comm.rank]["exchanges"] = dict(p.exchanges)
             out[comm.rank]["engines"] = (p.band.get_int("fill_algorithm"), p.band.get_int("noflat_algorithm"))
+            out[comm.rank]["fill_overflow"] = p.band.get_int("fill_overflow")
             out[comm.rank].update(rec)
             p.close()
         except Exception as e:  # pragma: no cover

@@ -245,13 +245,16 @@ def test_priority_flood_and_its_fallback_give_the_same_fill(alg):
     pits = (1.0 + rng.random((300, 260))).astype(np.float32)
     pits[::2, ::2] = (rng.random((150, 130)) * 0.5).astype(np.float32)
     plateau = np.round(fbm(200, 330, beta=2.5, seed=13) / 4).astype(np.float32)     # integer steps: large plateaus
-    for dem, algorithm in ((smooth, 1), (pits, 0), (plateau, 1)):
+    # (fill_overflow of `pits`: corner and edge tiles hold more than 1024 basins, the tiles inside exactly 1024 and more basin pairs
+    # than the hash takes -- 1 | 2, as tests/_pflood_model.py computes it for this field)
+    for dem, algorithm, overflow in ((smooth, 1, 0), (pits, 0, 3), (plateau, 1, 0)):
         with HydroPipeline(dem.shape) as pipe:
             pipe.upload("dem", dem)
             pipe.run("fill")
             pipe.sync()
             got, dep = pipe.download("filled"), pipe.download("depths")
             assert pipe.get_int("fill_algorithm") == algorithm
+            assert pipe.get_int("fill_overflow") == overflow
         want = oracle.fill_terrain(dem)
         assert np.array_equal(got, want)
         assert np.array_equal(dep, oracle.depths(want, dem))
