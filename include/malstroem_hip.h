@@ -527,6 +527,30 @@ int mhip_ctx_rasterize_zones(mhip_ctx *ctx, int64_t nvert, const double *xy, int
 int mhip_ctx_zones_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, int32_t *dst);
 int mhip_ctx_zone_stats(mhip_ctx *ctx, int32_t source, mhip_zone_record *records);
 
+/* The outlines of the regions of a label raster as rings of lattice vertices (the reference hands this to GDAL, vector.py:70-74 with
+ * 8CONNECTED=8; the definition is tests/_polygonize.py).  labels[H][W] int32, 0 the background; vertex (x, y), x in
+ * [0, W], y in [0, H], cell (r, c) has the corners (c, r) .. (c + 1, r + 1) -- the cell coordinates of the zones above.  Every side of a
+ * cell of label l != 0 whose neighbour across it has another value or lies outside is a directed unit edge of l with the cell on its
+ * right (y down): top (c, r) -> (c + 1, r), right, bottom, left.  At the end vertex of an edge the next one is the first that exists
+ * among the edges of l that start there, in the order left turn, straight on, right turn: cells of l that touch by a corner alone are
+ * joined, an 8-connected region has ONE exterior ring, its holes are the 4-connected components of what it encloses.  A ring keeps
+ * the vertices where the heading changes, starts at its smallest vertex by (y, x), runs in edge order and is not closed; exterior
+ * rings have positive shoelace area in these coordinates, holes negative.  Rings are ordered by start vertex (y, x); an exterior ring
+ * comes before the hole that shares its start vertex.  The result -- xy[nvert][2] int32, ring_offsets[nring + 1], ring_label[nring] --
+ * depends on nothing but the raster, and rasterizing it (ring_label as the zones) gives the raster back.
+ * The result is a snapshot behind an opaque handle, in device buffers of its own: sizes, then fetch into arrays of those sizes
+ * (ring_offsets nring + 1 entries; one copy straight into the caller's arrays), then free; it outlives the context and every later
+ * run, and holds 8 B a vertex + 12 B a ring of device memory until it is freed.  MHIP_EINVAL: a negative label; MHIP_ELIMIT: more than 2**32 - 1 edges.
+ * An all-zero raster gives 0 rings and asks for no device.
+ * On a context: source MHIP_R_LABELS (the filtered labels, as mhip_ctx_stats wants them) or MHIP_R_WATERSHEDS of an undivided context (a
+ * row band is refused); a source that is not valid is MHIP_EINVAL as from its own getter.  No raster leaves the device. */
+typedef struct mhip_polygons mhip_polygons;
+int mhip_polygonize_i32(const int32_t *labels, int64_t H, int64_t W, mhip_polygons **out);
+int mhip_ctx_polygonize(mhip_ctx *ctx, int32_t source, mhip_polygons **out);
+int mhip_polygons_sizes(const mhip_polygons *p, int64_t *nring, int64_t *nvert);
+int mhip_polygons_fetch(const mhip_polygons *p, int32_t *xy, int64_t *ring_offsets, int32_t *ring_label);
+void mhip_polygons_free(mhip_polygons *p);
+
 #ifdef __cplusplus
 }
 #endif

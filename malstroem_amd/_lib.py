@@ -65,6 +65,7 @@ SYMBOLS = [
     "mhip_flow_distance", "mhip_ctx_flow_distance", "mhip_ctx_flow_distance_rows", "mhip_ctx_flow_distance_records",
     "mhip_burn_lines_f32", "mhip_ctx_burn_lines",
     "mhip_rasterize_zones_i32", "mhip_zone_stats_f32", "mhip_ctx_rasterize_zones", "mhip_ctx_zones_rows", "mhip_ctx_zone_stats",
+    "mhip_polygonize_i32", "mhip_ctx_polygonize", "mhip_polygons_sizes", "mhip_polygons_fetch", "mhip_polygons_free",
 ]
 
 _lib = None

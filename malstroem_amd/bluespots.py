@@ -1,9 +1,9 @@
 """BluespotTool -- mirror of ``malstroem.bluespots`` (reference bluespots.py:23-216) on the device pipeline.
 
 ``filterbluespots`` and ``assemble_pourpoints`` keep the reference's record layout (pour point fields
-of bluespots.py:75-82).  Vectorisation of rasters (GDAL polygonize) is outside the hot path and is not
-provided here; pass the reference's vector writers if you need them and call the reference's
-``vectorize_labels_file`` yourself.
+of bluespots.py:75-82).  The outlines of the bluespots and of the watersheds (the reference's GDAL polygonize,
+bluespots.py:176-178, 187-189) are computed on the device from the resident rasters (``vector.py``) when
+``output_labeled_vector`` / ``output_watersheds_vector`` are given: one feature per bluespot, attribute ``bspot_id``.
 """
 import logging
 
@@ -11,6 +11,7 @@ import numpy as np
 
 from .algorithms import speedups
 from .pipeline import HydroPipeline
+from .vector import features_from_rings, transform_cell_to_world  # noqa: F401  (transform_cell_to_world lives in vector.py, as in the reference)
 
 
 def filterbluespots(filterfunction, cell_area, raw_bluespot_stats):
@@ -26,14 +27,6 @@ def filterbluespots(filterfunction, cell_area, raw_bluespot_stats):
         d['area'] = s['count'] * cell_area
         keepers.append(filterfunction(d))
     return keepers
-
-
-def transform_cell_to_world(cell, transform):
-    """Centre of cell (row, col) in world coordinates for a GDAL geotransform (reference vector.py:21-39)."""
-    row, col = cell[0] + 0.5, cell[1] + 0.5
-    x = transform[0] + col * transform[1] + row * transform[2]
-    y = transform[3] + col * transform[4] + row * transform[5]
-    return x, y
 
 
 POURPOINT_DTYPE = np.dtype([("bspot_id", "<i8"), ("cell_row", "<i8"), ("cell_col", "<i8"), ("bspot_dmax", "<f8"), ("bspot_area", "<f8"),
@@ -99,6 +92,10 @@ class BluespotTool(object):
     distance in metres along the flow path to the bluespot it drains to (to the raster edge or a sink where it drains to none; nodata
     -1 on a flow cycle).  Every pour point then also carries ``wshed_lfp``, the length in metres of the longest flow path of the
     bluespot's local watershed, and ``lfp_row`` / ``lfp_col``, the cell that path starts at.  Without it the layer is unchanged.
+
+    ``output_labeled_vector`` / ``output_watersheds_vector``: vector writers for the outlines of the bluespots / of their local
+    watersheds, written after the respective raster from the resident rasters: one ``Polygon`` per bluespot with
+    the attribute ``bspot_id``, as the reference's (bluespots.py:176-178, 187-189).  Without them every output is what it was.
     """
 
     def __init__(self, input_depths, input_flowdir, input_bluespot_filter_function,
@@ -119,8 +116,6 @@ class BluespotTool(object):
         self.device = device
         self.output_flowlength_raster = output_flowlength_raster
         assert self.input_accum or self.input_dem or pipeline, "Either input_dem or input_accum must be specified"
-        if output_labeled_vector or output_watersheds_vector:
-            raise NotImplementedError("vectorisation (GDAL polygonize) is outside malstroem_amd's hot path")
         self.logger = logging.getLogger(__name__)
 
     def process(self):
@@ -155,11 +150,17 @@ class BluespotTool(object):
             bluespot_stats = pipe.stats()
             self.logger.info("Number of bluespots left after filtering: {}".format(nlabels))
             self.output_labeled_raster.write(pipe.download("labels"))
+            if self.output_labeled_vector:
+                self.logger.info("Vectorizing bluespots")
+                self.output_labeled_vector.write_geojson_features(features_from_rings(*pipe.polygonize("labels"), transform, 'bspot_id'))
             self.logger.info("Calculating watersheds and pour points")
             pipe.run("watershed", "pourpoints")
             watershed_stats = pipe.watershed_counts()
             if self.output_watersheds_raster:
                 self.output_watersheds_raster.write(pipe.download("watersheds"))
+            if self.output_watersheds_vector:
+                self.logger.info("Vectorizing watersheds")
+                self.output_watersheds_vector.write_geojson_features(features_from_rings(*pipe.polygonize("watersheds"), transform, 'bspot_id'))
             pp_pix = pipe.pourpoints()
             self.logger.info("Writing {} pour points".format(len(pp_pix)))
             pour_points = assemble_pourpoints(transform, pp_pix, bluespot_stats, watershed_stats)

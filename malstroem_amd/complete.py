@@ -7,7 +7,8 @@ scripts/complete.py:70-117).  Here ONE device pipeline stays resident from the D
 ``BandPipeline`` per rank when the DEM is cut into row bands (``comm`` given) -- and files are written for the user only.
 Outputs carry the reference's names: ``filled.tif``, ``flowdir.tif``, ``bs_depths.tif``, ``accum.tif`` (with ``accum``),
 ``bluespots.tif``, ``watersheds.tif`` and the vector layers ``pourpoints``, ``nodes``, ``streams``, ``events`` under
-``<outdir>/vector`` (GeoJSON here; OGR formats need the reference's ``io.VectorWriter``).
+``<outdir>/vector``, with ``vector`` also ``bluespots`` and ``watersheds`` (GeoJSON here; OGR formats need the reference's
+``io.VectorWriter``).
 """
 import ast
 import logging
@@ -97,6 +98,10 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     in mm; ``accum``: also compute the accumulated flow (pour points then sit at its maximum, bluespots.py:195-200);
     ``filter``: bluespot filter expression.  Returns a dict with the paths written and the counts the reference logs.
 
+    ``vector``: also write the vector layers ``bluespots`` and ``watersheds`` -- the outlines of the (filtered) bluespots and of their
+    local watersheds, one polygon per bluespot with the attribute ``bspot_id`` (scripts/complete.py:88-95) -- computed on the device
+    from the resident rasters (``vector.py``); the dict gains ``bluespots_vector`` and ``watersheds_vector``.  Not on row bands yet.
+
     ``finalstate``: also write, for every rain event, the raster of the water depths the event leaves behind
     (``finaldepths_<mm:g>.tif``; ``finalstate.FinalStateTool`` on the pipeline the bluespots were computed on, hypsometry tables at
     ``hyps_resolution`` metres) and the vector layer ``finalstate``: the events with water level, largest depth and wet area per
@@ -123,11 +128,12 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     final rasters ``depth_<mm:g>`` (the largest final depth on its cells) per event; the dict gains ``objects``.  Every other output is
     what it is without the argument.  Not on row bands yet.  (``objects``, ``objects_grow`` and ``adaptations`` are taken by keyword
     only.)"""
-    if vector:
-        raise NotImplementedError("vectorisation of bluespots / watersheds (GDAL polygonize) is outside malstroem_amd's hot path")
     if (onset or not final_rasters) and not finalstate:
         raise ValueError("onset and final_rasters belong to the final state: pass finalstate=True")
     if comm is not None and comm.size > 1:
+        if vector:
+            raise NotImplementedError("vector on row bands: an outline crosses the seams between the bands, and joining the rings of "
+                                      "the bands there is not built yet; run it on one context")
         if finalstate:
             raise NotImplementedError("finalstate on row bands: the hypsometry tables of the bands add up (counts and sums of a global "
                                       "label), which is not built yet; run it on one context")
@@ -174,9 +180,12 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         watershed_writer = io.RasterWriter(os.path.join(outdir, 'watersheds.tif'), tr, crs, 0)
         labeled_writer = io.RasterWriter(os.path.join(outdir, 'bluespots.tif'), tr, crs, 0)
         flowlength_path = os.path.join(outdir, 'flowlength.tif')
+        labeled_vector_writer = io.VectorWriter('GeoJSON', outvector, 'bluespots', None, None, crs) if vector else None
+        watershed_vector_writer = io.VectorWriter('GeoJSON', outvector, 'watersheds', None, None, crs) if vector else None
         BluespotTool(input_depths=dem_reader, input_flowdir=dem_reader, input_bluespot_filter_function=filter_function,
                      input_accum=None, input_dem=dem_reader, output_labeled_raster=labeled_writer, output_pourpoints=pourpoint_writer,
                      output_watersheds_raster=watershed_writer, pipeline=pipe, device=device,
+                     output_labeled_vector=labeled_vector_writer, output_watersheds_vector=watershed_vector_writer,
                      output_flowlength_raster=io.RasterWriter(flowlength_path, tr, crs, -1) if flowlength else None).process()
         nlabels = pipe.get_int("nlabels")
         # Process pourpoints: the walk runs on the resident flow directions and labels
@@ -205,6 +214,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         RainTool(nodes_reader, events_writer, rain).process()
         res = dict(outdir=outdir, vector=outvector, nlabels=nlabels, events=events_writer.filepath,
                    nodes=nodes_writer.filepath, streams=streams_writer.filepath, pourpoints=pourpoint_writer.filepath)
+        if vector:
+            res.update(bluespots_vector=labeled_vector_writer.filepath, watersheds_vector=watershed_vector_writer.filepath)
         if flowlength:
             res["flowlength"] = flowlength_path
         if adaptations is not None:

@@ -1,6 +1,7 @@
 // api.hip -- the host-raster entry points of libmalstroem_hip.so (declared in include/malstroem_hip.h): upload -> stage -> download,
 // one per malstroem.algorithms stage function, over the device-pointer stage implementations (fill.hip, d8.hip, accum.hip, ccl.hip,
-// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, zones.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
+// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, zones.hip, polygonize.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
+#include <new>
 #include <vector>
 
 #include "common.hpp"
@@ -450,6 +451,54 @@ int mhip_zone_stats_f32(const float *data, const int32_t *zones, int64_t n, int6
     MH_TRY(d_r.alloc(sizeof(mhip_zone_record) * (size_t)(nzone + 1)));
     MH_TRY(zone_stats_dev(d_d.as<float>(), d_z.as<int32_t>(), n, W, nzone, d_r.as<mhip_zone_record>(), s));
     return download(records, d_r, sizeof(mhip_zone_record) * (size_t)(nzone + 1), s);
+}
+
+int mhip_polygonize_i32(const int32_t *labels, int64_t H, int64_t W, mhip_polygons **out)
+{
+    MH_ARG(labels && out, "polygonize_i32(labels, H, W, out)");
+    MH_TRY(polygonize_check(H, W));
+    const size_t n = (size_t)(H * W);
+    size_t first = 0;      // (a raster without a label: no ring, no device)
+    while (first < n && labels[first] == 0) ++first;
+    if (first < n) MH_TRY(require_device());
+    mhip_polygons *p = new (std::nothrow) mhip_polygons();
+    if (!p) {
+        set_error("polygonize: out of host memory");
+        return MHIP_EHIP;
+    }
+    if (first < n) {
+        hipStream_t s = 0;
+        DevBuf d_lab;
+        int rc = hipGetDevice(&p->device) == hipSuccess ? MHIP_OK : MHIP_EHIP;
+        if (rc == MHIP_OK) rc = upload(d_lab, labels, 4 * n, s);
+        if (rc == MHIP_OK) rc = polygonize_dev(d_lab.as<int32_t>(), H, W, p->xy, p->ring_offsets, p->ring_label, &p->nring, &p->nvert, s);
+        if (rc != MHIP_OK) {
+            delete p;
+            return rc;
+        }
+    }
+    *out = p;
+    return MHIP_OK;
+}
+
+int mhip_polygons_sizes(const mhip_polygons *p, int64_t *nring, int64_t *nvert)
+{
+    MH_ARG(p && nring && nvert, "polygons_sizes(polygons, nring, nvert)");
+    *nring = p->nring;
+    *nvert = p->nvert;
+    return MHIP_OK;
+}
+
+int mhip_polygons_fetch(const mhip_polygons *p, int32_t *xy, int64_t *ring_offsets, int32_t *ring_label)
+{
+    MH_ARG(p && ring_offsets && (xy || p->nvert == 0) && (ring_label || p->nring == 0), "polygons_fetch(polygons, xy, ring_offsets, ring_label)");
+    return polygons_fetch_dev(p, xy, ring_offsets, ring_label);
+}
+
+void mhip_polygons_free(mhip_polygons *p)
+{
+    if (p && p->device >= 0) (void)hipSetDevice(p->device);
+    delete p;
 }
 
 int mhip_trace_downstream_i32(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, const int64_t *cells_rc, int64_t n,

@@ -9,6 +9,8 @@
 
 #include "../../include/malstroem_hip.h"
 
+struct mhip_polygons;
+
 namespace mh {
 
 // ---- error plumbing --------------------------------------------------------------------------
@@ -445,6 +447,13 @@ int zones_check(int64_t H, int64_t W, int64_t nvert, const double *xy, int64_t n
 int zones_rasterize_dev(int32_t *d_out, int64_t H, int64_t W, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
                         const int32_t *ring_zone, int64_t nzone, int grow, hipStream_t s);
 int zone_stats_dev(const float *d_data, const int32_t *d_zones, int64_t n, int64_t W, int64_t nzone, mhip_zone_record *d_rec, hipStream_t s);
+// polygonize.hip: the outlines of the regions of an int32 label raster.  polygonize_check: the argument rules on the
+// shape (MHIP_EINVAL; no device work).  polygonize_dev: the rings of d_lab into three buffers it allocates -- xy int32 [nvert][2],
+// ring_offsets int64 [nring + 1], ring_label int32 [nring].  Synchronises.  MHIP_EINVAL: a negative label; MHIP_ELIMIT: more than
+// 2**32 - 1 edges.  The handle of the C-ABI keeps the three buffers; polygons_fetch_dev copies them to the caller's arrays.
+int polygonize_check(int64_t H, int64_t W);
+int polygons_fetch_dev(const mhip_polygons *p, int32_t *xy, int64_t *ring_offsets, int32_t *ring_label);
+int polygonize_dev(const int32_t *d_lab, int64_t H, int64_t W, DevBuf &d_xy, DevBuf &d_off, DevBuf &d_rl, int64_t *nring, int64_t *nvert, hipStream_t s);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,
                    bool band_mode = false, const unsigned int *d_known_interior_nodir = nullptr, const int32_t *d_src = nullptr, PourLink *pour = nullptr);
@@ -549,3 +558,9 @@ struct WgVote {
 #endif
 
 }  // namespace mh
+
+struct mhip_polygons {      // a result of mhip_polygonize_i32 / mhip_ctx_polygonize: a snapshot in buffers of its own on `device`
+    mh::DevBuf xy, ring_offsets, ring_label;      // (none for a raster without a label: nring == 0 and no device was asked for)
+    int64_t nring = 0, nvert = 0;
+    int device = -1;
+};

@@ -1,7 +1,8 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
-// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, and the one
+// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, and the one
 // rule for what a write of a resident raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -685,6 +686,31 @@ int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
     MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(c->nzone + 1)));
     MH_TRY(zone_stats_dev(src, c->zones.as<int32_t>(), c->H * c->W, c->W, c->nzone, d_rec.as<mhip_zone_record>(), c->stream));
     return ctx_fetch(c, d_rec, sizeof(mhip_zone_record) * (size_t)(c->nzone + 1), records);
+}
+
+/* ---- the outlines of the resident labels or watersheds (polygonize.hip): a snapshot in buffers of the handle, no raster leaves the device */
+int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
+{
+    MH_ARG(c && out, "ctx_polygonize(ctx, source, out)");
+    MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS, "ctx_polygonize: the source is MHIP_R_LABELS or MHIP_R_WATERSHEDS");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "outlines on a row band are not built (a ring crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[source], "raster has not been computed or uploaded");
+    if (source == MHIP_R_LABELS) MH_ARG(c->labels_filtered && !c->ccl_pending, "ctx_polygonize needs mhip_ctx_apply_keep after the LABEL run");
+    MH_TRY(polygonize_check(c->H, c->W));
+    MH_HIP(hipSetDevice(c->device));
+    mhip_polygons *p = new (std::nothrow) mhip_polygons();
+    if (!p) {
+        set_error("ctx_polygonize: out of host memory");
+        return MHIP_EHIP;
+    }
+    p->device = c->device;
+    const int rc = polygonize_dev(c->r[source].as<int32_t>(), c->H, c->W, p->xy, p->ring_offsets, p->ring_label, &p->nring, &p->nvert, c->stream);      // (synchronises)
+    if (rc != MHIP_OK) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return MHIP_OK;
 }
 
 }  // extern "C"

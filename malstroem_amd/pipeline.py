@@ -266,3 +266,16 @@ class HydroPipeline(CtxHandle):
     def download_zones_to(self, writer, max_rows=4096):
         """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
         write_windows(writer, self.shape, np.int32, self.download_zones_rows, max_rows)
+
+    # ---- outlines of the resident labels / watersheds (vector.py; DESIGN.md 14) ----------------------------------------
+    POLYGON_SOURCES = {"labels": _lib.R_LABELS, "watersheds": _lib.R_WATERSHEDS}
+
+    def polygonize(self, source="labels"):
+        """``(xy, ring_offsets, ring_label)`` of the resident (filtered) labels or of the watersheds, as ``vector.polygonize`` gives
+        them for the downloaded raster; no raster leaves the device.  The arrays are a snapshot: a later run does not change them."""
+        from .vector import take_polygons
+        if source not in self.POLYGON_SOURCES:
+            raise ValueError("source must be one of %s, got %r" % (sorted(self.POLYGON_SOURCES), source))
+        handle = ctypes.c_void_p()
+        _lib.call("mhip_ctx_polygonize", self._ctx, ctypes.c_int32(self.POLYGON_SOURCES[source]), ctypes.byref(handle))
+        return take_polygons(handle)
