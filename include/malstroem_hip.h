@@ -551,6 +551,42 @@ int mhip_polygons_sizes(const mhip_polygons *p, int64_t *nring, int64_t *nvert);
 int mhip_polygons_fetch(const mhip_polygons *p, int32_t *xy, int64_t *ring_offsets, int32_t *ring_label);
 void mhip_polygons_free(mhip_polygons *p);
 
+/* Flow paths: the stream network above an accumulation threshold as lines (ours; the definition is tests/_flowpaths.py).
+ * flowdir[H][W] uint8 AGNPS codes 0..7 (a code > 7: no direction), accum[H][W] float64 (any values), labels[H][W] int32 or NULL (all 0).
+ * A cell is a STREAM CELL when accum >= threshold (NaN: it is not) and its label is 0.  down(c): the neighbour its code points at, none
+ * for a code > 7 or outside the raster; indeg(c): the stream cells n with down(n) == c.  A stream cell is a HEAD with indeg 0, a
+ * CONFLUENCE with indeg >= 2, FIRST when it is either.  A REACH is the chain c0 .. ck of stream cells, c0 first, c(i+1) = down(ci), no
+ * other first cell in it; down(ck) is none, no stream cell, or a confluence.  Every stream cell lies in exactly one reach, except the
+ * cells of a cycle of the mask that nothing flows into: they are counted in `unresolved`.  Reaches are ordered by the raster-order
+ * index of c0.  end_kind: 0 down(ck) is a confluence (to_reach: the reach that starts there), 1 ck points outside the raster, 2 the
+ * code of ck is > 7, 3 down(ck) carries a label (to_label), 4 down(ck) is an unlabelled cell below the threshold.  The path of a reach
+ * is c0 .. ck, and e = down(ck) behind it for the kinds 0 and 3; its vertices (col, row) are the first point, the last point and every
+ * point between them where the step changes.
+ * The result is a snapshot behind an opaque handle, in device buffers of its own, as mhip_polygons: sizes, then fetch into arrays of
+ * those sizes (xy[nvert][2] int32, reach_offsets[nreach + 1] int64, records[nreach]; one copy per array, then the Strahler orders on
+ * the host), then free; it outlives the context and every later run.  MHIP_EINVAL: a threshold that is not finite and >= 1, a negative
+ * label, H or W < 1; MHIP_ELIMIT: more than 2**31 - 1 stream cells.  An empty mask gives 0 reaches.
+ * On a context: the resident MHIP_R_FLOWDIR and MHIP_R_ACCUM of an undivided context (a row band is refused), with stop_at_labels the
+ * filtered MHIP_R_LABELS as mhip_ctx_stats wants them; a raster that is not valid is MHIP_EINVAL as from its own getter.  No raster
+ * leaves the device. */
+typedef struct mhip_reach_record {
+    int64_t first_cell, last_cell;   /* row * W + col of c0 and of ck */
+    int64_t end_cell;                /* down(ck) for the kinds 0, 3 and 4, else -1 */
+    double up_cells, down_cells;     /* accum[c0], accum[ck] */
+    int32_t n_orth, n_diag;          /* orthogonal and diagonal steps of the path, the step to an appended e included */
+    int32_t end_kind, to_reach;      /* to_reach: -1 unless kind 0 */
+    int32_t to_label, from_label;    /* to_label: 0 unless kind 3; from_label: the label of the labelled neighbour n of c0 with down(n) == c0 and
+                                        accum[n] >= threshold of the largest accum (the first of the directions U .. UL from c0 among equals), 0: none */
+    int32_t order;                   /* Strahler: 1 at a head; at a confluence the largest order m that arrives, m + 1 when two arrive with it; 0: a reach on a cycle */
+    int32_t reserved;                /* 0 */
+} mhip_reach_record;
+typedef struct mhip_flowpaths mhip_flowpaths;
+int mhip_flowpaths_f64(const uint8_t *flowdir, const double *accum, const int32_t *labels, int64_t H, int64_t W, double threshold, mhip_flowpaths **out);
+int mhip_ctx_flowpaths(mhip_ctx *ctx, double threshold, int32_t stop_at_labels, mhip_flowpaths **out);
+int mhip_flowpaths_sizes(const mhip_flowpaths *p, int64_t *nreach, int64_t *nvert, int64_t *unresolved);
+int mhip_flowpaths_fetch(const mhip_flowpaths *p, int32_t *xy, int64_t *reach_offsets, mhip_reach_record *records);
+void mhip_flowpaths_free(mhip_flowpaths *p);
+
 #ifdef __cplusplus
 }
 #endif

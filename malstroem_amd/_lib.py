@@ -28,7 +28,13 @@ BURN_RESULT_DTYPE = np.dtype([("z0", "<f8"), ("z1", "<f8"), ("cells", "<i8"), ("
 ZONE_DTYPE = np.dtype([("vmax", "<f8"), ("vmin_pos", "<f8"), ("cells", "<i8"), ("pos", "<i8")])
 ZSRC_WETAT, ZSRC_FLOWDIST = 100, 101
 
-WETAT_MAX_EVENTS = 16     # MHIP_WETAT_MAX_EVENTS: most rain events of one wet_at call
+# flow paths (flowpaths.py): mhip_reach_record; the end kinds of a reach
+REACH_DTYPE = np.dtype([("first_cell", "<i8"), ("last_cell", "<i8"), ("end_cell", "<i8"), ("up_cells", "<f8"), ("down_cells", "<f8"),
+                        ("n_orth", "<i4"), ("n_diag", "<i4"), ("end_kind", "<i4"), ("to_reach", "<i4"), ("to_label", "<i4"),
+                        ("from_label", "<i4"), ("order", "<i4"), ("reserved", "<i4")])
+REACH_END = ("confluence", "edge", "sink", "bluespot", "below_threshold")
+
+WETAT_MAX_EVENTS = 16    # MHIP_WETAT_MAX_EVENTS: most rain events of one wet_at call
 
 OK, EINVAL, EHIP, ENODEV, ELIMIT, ENOTCONV, ECOMM = 0, -1, -2, -3, -4, -5, -6
 
@@ -66,6 +72,7 @@ SYMBOLS = [
     "mhip_burn_lines_f32", "mhip_ctx_burn_lines",
     "mhip_rasterize_zones_i32", "mhip_zone_stats_f32", "mhip_ctx_rasterize_zones", "mhip_ctx_zones_rows", "mhip_ctx_zone_stats",
     "mhip_polygonize_i32", "mhip_ctx_polygonize", "mhip_polygons_sizes", "mhip_polygons_fetch", "mhip_polygons_free",
+    "mhip_flowpaths_f64", "mhip_ctx_flowpaths", "mhip_flowpaths_sizes", "mhip_flowpaths_fetch", "mhip_flowpaths_free",
 ]
 
 _lib = None

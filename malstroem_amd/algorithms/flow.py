@@ -211,3 +211,10 @@ def assign_watersheds_upstream(flowdir, labelled, cell, unassigned):
         if lbl == unassigned:
             labelled[r, c] = lbl = below
         stack.extend((u[0], u[1], lbl) for u in upstream_cells(flowdir, (r, c)))
+
+
+def flow_paths(flowdir, accum, threshold, labelled=None):
+    """The stream network of ``accum >= threshold`` as reaches: ``(xy, reach_offsets, records, unresolved)`` -- ``flowpaths.extract``
+    (ours: the reference has no counterpart)."""
+    from ..flowpaths import extract
+    return extract(flowdir, accum, threshold, labelled)

@@ -11,6 +11,7 @@ import numpy as np
 
 from .algorithms import speedups
 from .pipeline import HydroPipeline
+from .flowpaths import check_threshold, features_from_reaches
 from .vector import features_from_rings, transform_cell_to_world  # noqa: F401  (transform_cell_to_world lives in vector.py, as in the reference)
 
 
@@ -96,12 +97,19 @@ class BluespotTool(object):
     ``output_labeled_vector`` / ``output_watersheds_vector``: vector writers for the outlines of the bluespots / of their local
     watersheds, written after the respective raster from the resident rasters: one ``Polygon`` per bluespot with
     the attribute ``bspot_id``, as the reference's (bluespots.py:176-178, 187-189).  Without them every output is what it was.
+
+    ``output_flowpaths`` (no reference counterpart): a vector writer for the layer of the flow paths -- the stream
+    network of the cells with at least ``flowpaths_threshold`` cells upstream, one ``LineString`` per reach with its upstream area
+    (``flowpaths.features_from_reaches``), written after the pour points are taken, from the resident rasters; with
+    ``flowpaths_stop_at_bluespots`` a reach ends where it runs into a (filtered) bluespot.  ``flowpaths_run_accum``: the pipeline
+    holds no accumulated flow yet and the stage runs first -- after the pour points, which stay where they are without it.
     """
 
     def __init__(self, input_depths, input_flowdir, input_bluespot_filter_function,
                  output_labeled_raster, output_pourpoints, output_watersheds_raster,
                  input_accum=None, input_dem=None, output_labeled_vector=None, output_watersheds_vector=None,
-                 pipeline=None, device=0, output_flowlength_raster=None):
+                 pipeline=None, device=0, output_flowlength_raster=None, output_flowpaths=None, flowpaths_threshold=None,
+                 flowpaths_stop_at_bluespots=True, flowpaths_run_accum=False):
         self.input_depths = input_depths
         self.input_flowdir = input_flowdir
         self.input_bluespot_filter_function = input_bluespot_filter_function
@@ -115,6 +123,11 @@ class BluespotTool(object):
         self.pipeline = pipeline
         self.device = device
         self.output_flowlength_raster = output_flowlength_raster
+        self.output_flowpaths = output_flowpaths
+        self.flowpaths_stop_at_bluespots = flowpaths_stop_at_bluespots
+        self.flowpaths_run_accum = flowpaths_run_accum
+        if output_flowpaths is not None:
+            self.flowpaths_threshold = check_threshold(flowpaths_threshold)
         assert self.input_accum or self.input_dem or pipeline, "Either input_dem or input_accum must be specified"
         self.logger = logging.getLogger(__name__)
 
@@ -173,6 +186,15 @@ class BluespotTool(object):
                 for feature, lfp in zip(pour_points, pipe.flow_distance_records()):
                     feature['properties'].update(wshed_lfp=float(lfp['value']), lfp_row=int(lfp['row']), lfp_col=int(lfp['col']))
             self.output_pourpoints.write_geojson_features(dict(type="FeatureCollection", features=pour_points))
+            if self.output_flowpaths is not None:
+                if self.flowpaths_run_accum or (own and not self.input_accum):
+                    self.logger.info("Calculating flow accumulation")
+                    pipe.run("accum")
+                self.logger.info("Extracting flow paths")
+                xy, offsets, reaches, unresolved = pipe.flow_paths(self.flowpaths_threshold, self.flowpaths_stop_at_bluespots)
+                if unresolved:
+                    self.logger.warning("{} stream cells lie on a cycle that nothing flows into: no flow path".format(unresolved))
+                self.output_flowpaths.write_geojson_features(features_from_reaches(xy, offsets, reaches, transform, cell_width))
             self.logger.info("Done")
         finally:
             if own:

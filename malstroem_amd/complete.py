@@ -89,7 +89,7 @@ def parse_filter(filter):
 
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
                 finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
-                adaptations=None):
+                flowpaths=None, flowpaths_stop_at_bluespots=True, adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -127,7 +127,18 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     bluespot), with ``onset`` ``wet_at_mm`` (the smallest rain that leaves water on one of its cells; null: none does) and with the
     final rasters ``depth_<mm:g>`` (the largest final depth on its cells) per event; the dict gains ``objects``.  Every other output is
     what it is without the argument.  Not on row bands yet.  (``objects``, ``objects_grow`` and ``adaptations`` are taken by keyword
-    only.)"""
+    only.)
+
+    ``flowpaths`` (keyword only): the smallest number of upstream cells of a stream cell.  Also writes the vector layer ``flowpaths``
+    -- where the water runs: the network of the cells with at least that many cells upstream, one ``LineString`` per reach with
+    ``up_area`` / ``down_area``, ``length``, Strahler ``order``, ``to_reach``, ``to_bspot`` / ``from_bspot`` and ``end``
+    (``flowpaths.features_from_reaches``), computed on the device from the resident rasters after the watersheds; with
+    ``flowpaths_stop_at_bluespots`` (the default) a reach ends where it runs into a (filtered) bluespot.  The accumulated flow is
+    computed for it even with ``accum=False`` (``accum.tif`` is written with ``accum`` only; the pour points stay where they are
+    without ``accum``).  The dict gains ``flowpaths``.  Not on row bands yet."""
+    if flowpaths is not None:
+        from .flowpaths import check_threshold
+        flowpaths = check_threshold(flowpaths)
     if (onset or not final_rasters) and not finalstate:
         raise ValueError("onset and final_rasters belong to the final state: pass finalstate=True")
     if comm is not None and comm.size > 1:
@@ -143,6 +154,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         if adaptations is not None:
             raise NotImplementedError("adaptations on row bands: a line crosses the seams between the bands, and its levels hang on "
                                       "both of its ends, which is not built yet; run it on one context")
+        if flowpaths is not None:
+            raise NotImplementedError("flowpaths on row bands: a reach crosses the seams between the bands, and joining the chains of "
+                                      "the bands there is not built yet; run it on one context")
         if objects is not None:
             raise NotImplementedError("objects on row bands: an object crosses the seams between the bands, and the zone raster of a "
                                       "band is not built yet; run it on one context")
@@ -182,11 +196,14 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         flowlength_path = os.path.join(outdir, 'flowlength.tif')
         labeled_vector_writer = io.VectorWriter('GeoJSON', outvector, 'bluespots', None, None, crs) if vector else None
         watershed_vector_writer = io.VectorWriter('GeoJSON', outvector, 'watersheds', None, None, crs) if vector else None
+        flowpaths_writer = io.VectorWriter('GeoJSON', outvector, 'flowpaths', None, None, crs) if flowpaths is not None else None
         BluespotTool(input_depths=dem_reader, input_flowdir=dem_reader, input_bluespot_filter_function=filter_function,
                      input_accum=None, input_dem=dem_reader, output_labeled_raster=labeled_writer, output_pourpoints=pourpoint_writer,
                      output_watersheds_raster=watershed_writer, pipeline=pipe, device=device,
                      output_labeled_vector=labeled_vector_writer, output_watersheds_vector=watershed_vector_writer,
-                     output_flowlength_raster=io.RasterWriter(flowlength_path, tr, crs, -1) if flowlength else None).process()
+                     output_flowlength_raster=io.RasterWriter(flowlength_path, tr, crs, -1) if flowlength else None,
+                     output_flowpaths=flowpaths_writer, flowpaths_threshold=flowpaths, flowpaths_stop_at_bluespots=flowpaths_stop_at_bluespots,
+                     flowpaths_run_accum=not accum).process()
         nlabels = pipe.get_int("nlabels")
         # Process pourpoints: the walk runs on the resident flow directions and labels
         pourpoints_reader = io.VectorReader(outvector, pourpoint_writer.layername)
@@ -218,6 +235,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
             res.update(bluespots_vector=labeled_vector_writer.filepath, watersheds_vector=watershed_vector_writer.filepath)
         if flowlength:
             res["flowlength"] = flowlength_path
+        if flowpaths is not None:
+            res["flowpaths"] = flowpaths_writer.filepath
         if adaptations is not None:
             res.update(dem_adapted=adapted_path, adaptations=report_writer.filepath)
         if finalstate:

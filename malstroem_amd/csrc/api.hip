@@ -1,6 +1,6 @@
 // api.hip -- the host-raster entry points of libmalstroem_hip.so (declared in include/malstroem_hip.h): upload -> stage -> download,
 // one per malstroem.algorithms stage function, over the device-pointer stage implementations (fill.hip, d8.hip, accum.hip, ccl.hip,
-// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, zones.hip, polygonize.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
+// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, zones.hip, polygonize.hip, flowpaths.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
 #include <new>
 #include <vector>
 
@@ -496,6 +496,53 @@ int mhip_polygons_fetch(const mhip_polygons *p, int32_t *xy, int64_t *ring_offse
 }
 
 void mhip_polygons_free(mhip_polygons *p)
+{
+    if (p && p->device >= 0) (void)hipSetDevice(p->device);
+    delete p;
+}
+
+int mhip_flowpaths_f64(const uint8_t *flowdir, const double *accum, const int32_t *labels, int64_t H, int64_t W, double threshold, mhip_flowpaths **out)
+{
+    MH_ARG(flowdir && accum && out, "flowpaths_f64(flowdir, accum, labels, H, W, threshold, out)");
+    MH_TRY(flowpaths_check(H, W, threshold));
+    MH_TRY(require_device());
+    mhip_flowpaths *p = new (std::nothrow) mhip_flowpaths();
+    if (!p) {
+        set_error("flowpaths: out of host memory");
+        return MHIP_EHIP;
+    }
+    const size_t n = (size_t)(H * W);
+    hipStream_t s = 0;
+    DevBuf d_fd, d_acc, d_lab;
+    int rc = hipGetDevice(&p->device) == hipSuccess ? MHIP_OK : MHIP_EHIP;
+    if (rc == MHIP_OK) rc = upload(d_fd, flowdir, n, s);
+    if (rc == MHIP_OK) rc = upload(d_acc, accum, 8 * n, s);
+    if (rc == MHIP_OK && labels) rc = upload(d_lab, labels, 4 * n, s);
+    if (rc == MHIP_OK) rc = flowpaths_dev(d_fd.as<uint8_t>(), d_acc.as<double>(), labels ? d_lab.as<int32_t>() : nullptr, H, W, threshold, p, s);
+    if (rc != MHIP_OK) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return MHIP_OK;
+}
+
+int mhip_flowpaths_sizes(const mhip_flowpaths *p, int64_t *nreach, int64_t *nvert, int64_t *unresolved)
+{
+    MH_ARG(p && nreach && nvert && unresolved, "flowpaths_sizes(flowpaths, nreach, nvert, unresolved)");
+    *nreach = p->nreach;
+    *nvert = p->nvert;
+    *unresolved = p->unresolved;
+    return MHIP_OK;
+}
+
+int mhip_flowpaths_fetch(const mhip_flowpaths *p, int32_t *xy, int64_t *reach_offsets, mhip_reach_record *records)
+{
+    MH_ARG(p && reach_offsets && (xy || p->nvert == 0) && (records || p->nreach == 0), "flowpaths_fetch(flowpaths, xy, reach_offsets, records)");
+    return flowpaths_fetch_dev(p, xy, reach_offsets, records);
+}
+
+void mhip_flowpaths_free(mhip_flowpaths *p)
 {
     if (p && p->device >= 0) (void)hipSetDevice(p->device);
     delete p;

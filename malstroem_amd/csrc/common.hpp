@@ -10,6 +10,7 @@
 #include "../../include/malstroem_hip.h"
 
 struct mhip_polygons;
+struct mhip_flowpaths;
 
 namespace mh {
 
@@ -454,6 +455,14 @@ int zone_stats_dev(const float *d_data, const int32_t *d_zones, int64_t n, int64
 int polygonize_check(int64_t H, int64_t W);
 int polygons_fetch_dev(const mhip_polygons *p, int32_t *xy, int64_t *ring_offsets, int32_t *ring_label);
 int polygonize_dev(const int32_t *d_lab, int64_t H, int64_t W, DevBuf &d_xy, DevBuf &d_off, DevBuf &d_rl, int64_t *nring, int64_t *nvert, hipStream_t s);
+// flowpaths.hip: the stream network above an accumulation threshold as lines.  flowpaths_check: the argument rules
+// (MHIP_EINVAL; no device work).  flowpaths_dev: the reaches of d_fd / d_acc / d_lab (nullptr: no labels) into the buffers of the
+// handle, which it allocates -- xy int32 [nvert][2], reach_offsets int64 [nreach + 1], records [nreach] without their orders.
+// Synchronises.  MHIP_EINVAL: a negative label; MHIP_ELIMIT: more than 2**31 - 1 stream cells.  flowpaths_fetch_dev copies the three
+// buffers to the caller's arrays and computes the Strahler orders there.
+int flowpaths_check(int64_t H, int64_t W, double threshold);
+int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, mhip_flowpaths *p, hipStream_t s);
+int flowpaths_fetch_dev(const mhip_flowpaths *p, int32_t *xy, int64_t *reach_offsets, mhip_reach_record *records);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,
                    bool band_mode = false, const unsigned int *d_known_interior_nodir = nullptr, const int32_t *d_src = nullptr, PourLink *pour = nullptr);
@@ -562,5 +571,11 @@ struct WgVote {
 struct mhip_polygons {      // a result of mhip_polygonize_i32 / mhip_ctx_polygonize: a snapshot in buffers of its own on `device`
     mh::DevBuf xy, ring_offsets, ring_label;      // (none for a raster without a label: nring == 0 and no device was asked for)
     int64_t nring = 0, nvert = 0;
+    int device = -1;
+};
+
+struct mhip_flowpaths {     // a result of mhip_flowpaths_f64 / mhip_ctx_flowpaths: a snapshot in buffers of its own on `device`
+    mh::DevBuf xy, reach_offsets, records;        // (none without a reach)
+    int64_t nreach = 0, nvert = 0, unresolved = 0;
     int device = -1;
 };

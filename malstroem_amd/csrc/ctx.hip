@@ -1,5 +1,5 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
-// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, and the one
+// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, the flow paths, and the one
 // rule for what a write of a resident raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
 #include <mutex>
 #include <new>
@@ -705,6 +705,34 @@ int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
     }
     p->device = c->device;
     const int rc = polygonize_dev(c->r[source].as<int32_t>(), c->H, c->W, p->xy, p->ring_offsets, p->ring_label, &p->nring, &p->nvert, c->stream);      // (synchronises)
+    if (rc != MHIP_OK) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return MHIP_OK;
+}
+
+/* ---- the flow paths of the resident flow directions and accumulation (flowpaths.hip): a snapshot in buffers of the handle */
+int mhip_ctx_flowpaths(mhip_ctx *c, double threshold, int32_t stop_at_labels, mhip_flowpaths **out)
+{
+    MH_ARG(c && out, "ctx_flowpaths(ctx, threshold, stop_at_labels, out)");
+    MH_TRY(flowpaths_check(c->H, c->W, threshold));
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "flow paths on a row band are not built (a reach crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_ACCUM], "raster has not been computed or uploaded");
+    if (stop_at_labels) {
+        MH_ARG(c->have[MHIP_R_LABELS], "raster has not been computed or uploaded");
+        MH_ARG(c->labels_filtered && !c->ccl_pending, "ctx_flowpaths needs mhip_ctx_apply_keep after the LABEL run");
+    }
+    MH_HIP(hipSetDevice(c->device));
+    mhip_flowpaths *p = new (std::nothrow) mhip_flowpaths();
+    if (!p) {
+        set_error("ctx_flowpaths: out of host memory");
+        return MHIP_EHIP;
+    }
+    p->device = c->device;
+    const int rc = flowpaths_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_ACCUM].as<double>(), stop_at_labels ? c->r[MHIP_R_LABELS].as<int32_t>() : nullptr,
+                                 c->H, c->W, threshold, p, c->stream);      // (synchronises)
     if (rc != MHIP_OK) {
         delete p;
         return rc;

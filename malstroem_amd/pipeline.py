@@ -279,3 +279,14 @@ class HydroPipeline(CtxHandle):
         handle = ctypes.c_void_p()
         _lib.call("mhip_ctx_polygonize", self._ctx, ctypes.c_int32(self.POLYGON_SOURCES[source]), ctypes.byref(handle))
         return take_polygons(handle)
+
+    # ---- flow paths of the resident flow directions and accumulation (flowpaths.py) ----------------------
+    def flow_paths(self, threshold, stop_at_bluespots=False):
+        """``(xy, reach_offsets, records, unresolved)`` of the stream network of ``accum >= threshold`` on the resident flow
+        directions and accumulated flow, as ``flowpaths.extract`` gives them for the downloaded rasters; with ``stop_at_bluespots``
+        the (filtered or uploaded) labels end the reaches.  No raster leaves the device.  The arrays are a snapshot."""
+        from .flowpaths import check_threshold, take_flowpaths
+        thr = check_threshold(threshold)
+        handle = ctypes.c_void_p()
+        _lib.call("mhip_ctx_flowpaths", self._ctx, ctypes.c_double(thr), ctypes.c_int32(1 if stop_at_bluespots else 0), ctypes.byref(handle))
+        return take_flowpaths(handle)
