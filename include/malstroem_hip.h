@@ -418,7 +418,6 @@ int mhip_ctx_band_relabel_sparse(mhip_ctx *ctx, int64_t nlocal, int64_t offset, 
 int mhip_ctx_band_ccl_begin(mhip_ctx *ctx, int64_t *nlocal);
 int mhip_ctx_band_ccl_finish(mhip_ctx *ctx, int64_t offset, const int32_t *dropped, const int32_t *target, int64_t ndropped,
                              int64_t nlabels_global, int with_stats);
-/* watersheds on a band: local pointer jumping with pseudo labels on the halo rows, then a boundary LUT */
 /* the bluespot filter on a band (bluespots.py:165-172 as a rank relabel): labels in [lo, hi] (numbered by this band) -> lut[l - lo]
  * (0 = dropped); a label another band numbered -> fnew[k] where fid[k] == l (fid sorted, unique); nlabels_new = the global count */
 int mhip_ctx_band_relabel_range(mhip_ctx *ctx, int64_t lo, int64_t hi, const int32_t *lut, const int32_t *fid, const int32_t *fnew, int64_t nf,
@@ -430,7 +429,22 @@ int mhip_ctx_band_relabel_range(mhip_ctx *ctx, int64_t lo, int64_t hi, const int
 int mhip_ctx_band_trace(mhip_ctx *ctx, const int64_t *cells_rc, const int32_t *src_label, int64_t n, int use_background, int32_t background,
                         int32_t *out_label, int32_t *out_status, int32_t *out_src, int64_t *out_exit_rc, int64_t *out_len, const int64_t *offsets,
                         int64_t *out_cells);
+/* The rule of flow.watersheds_from_labels (flow.py:398-412, _flow.pyx:276-314: an upstream search from the RASTER's edge cells): a
+ * cell takes the first label on its downstream path if that labelled cell's own path (the cell included) contains a raster edge
+ * cell -- the label is ROOTED --, otherwise it stays unassigned; labelled cells keep their label.  A band cannot see whether a path
+ * that leaves it through a halo row ever reaches the raster's edge.
+ * _local: the local pass for flow directions whose every path leaves the raster (the library's own D8: edges outward, no sinks, no
+ * cycles), where every label is rooted: WATERSHEDS = the first label downstream, a halo cell counting as labelled with its pseudo
+ * label -(1 + column) (top) / -(1 + W + column) (bottom); the launcher resolves the pseudo labels over the seams
+ * (mhip_band_ws_publish / _ws_lut) and writes them back with _apply_neg_lut.  It refuses an interior NODIR cell.
+ * _rooted: the same for flow directions of any origin (uploaded: interior sinks, cycles, inward edges, codes above 8), in three
+ * steps with a seam resolution + _apply_neg_lut on WATERSHEDS after step 1 and after step 2.  step 1: the local pass over a label
+ * raster that holds one label on the raster's edge cells -- resolved, WATERSHEDS says for every cell whether its path meets an edge
+ * cell.  step 2: the local pass over LABELS with the rootless labels replaced by the sentinel 2^31 - 1 (they still end the paths
+ * that reach them).  step 3: the sentinel -> the cell's own label, or unassigned.  distributed.BandPipeline.watershed takes
+ * _local when mhip_ctx_get_i64("flowdir_computed") is 1 on the band and _rooted otherwise. */
 int mhip_ctx_band_watershed_local(mhip_ctx *ctx);
+int mhip_ctx_band_watershed_rooted(mhip_ctx *ctx, int step);
 int mhip_ctx_band_apply_neg_lut(mhip_ctx *ctx, int which, const int32_t *lut, int64_t n);
 /* Two host threads per band (the labelling branch next to no-flats fill -> D8 -> accumulation, like the stage DAG of
  * mhip_ctx_run): the thread that drives the labelling branch calls _side_begin after the plain fill has been issued and
@@ -477,7 +491,8 @@ int mhip_ctx_kernel_ms(mhip_ctx *ctx, const char *kernel, float *ms_total, int32
  * 32 relaxations per block of 4 x 4 tiles, 64 halo links of a band's tile; 0: the flood ran through or was not tried),
  * "noflat_algorithm" (2 integer geodesic transform, 3 + float64 relaxation of irregular flats, 0 float64 relaxation; why a
  * transform was handed back: "noflat_reject*"), "pour_algorithm" (1 keys out of the accumulation's final pass, 0 a pass over
- * values + labels), "accum_algorithm" (row bands: 1 the second pass as a delta over the boundary pass's graph, 0 a full pass) */
+ * values + labels), "accum_algorithm" (row bands: 1 the second pass as a delta over the boundary pass's graph, 0 a full pass),
+ * "flowdir_computed" (1 the resident flow directions are the library's own D8, 0 they were uploaded or there are none) */
 int mhip_ctx_get_i64(mhip_ctx *ctx, const char *key, int64_t *value);
 int mhip_ctx_get_f64(mhip_ctx *ctx, const char *key, double *value);  /* "short", "diag" */
 /* label filter between MHIP_STAGE_LABEL and MHIP_STAGE_WATERSHED (reference bluespots.py:165-172):

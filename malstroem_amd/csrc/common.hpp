@@ -470,6 +470,11 @@ int pour_finish_dev(unsigned long long *d_key, const unsigned long long *d_tile_
                     hipStream_t s);
 int band_pseudo_labels_dev(int32_t *d_ws, int64_t H, int64_t W, int top, int bottom, hipStream_t s);
 int negative_lut_dev(int32_t *d_lab, int64_t n, const int32_t *d_lut, int64_t nlut, hipStream_t s);
+// the rootedness passes of a band's watersheds (watershed.hip; mhip_ctx_band_watershed_rooted)
+constexpr int32_t BAND_ROOT = 1, BAND_ROOTLESS = 0x7fffffff;
+int band_root_labels_dev(int32_t *d_out, int64_t H, int64_t W, int64_t row_off, int64_t Hg, hipStream_t s);
+int band_hide_rootless_dev(const int32_t *d_lab, const int32_t *d_rooted, int32_t *d_out, int64_t n, hipStream_t s);
+int band_show_rootless_dev(int32_t *d_ws, const int32_t *d_lab, int64_t n, hipStream_t s);
 
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

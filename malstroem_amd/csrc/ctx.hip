@@ -48,6 +48,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
         break;
     case MHIP_R_FLOWDIR:
         c->nodir_valid = false;
+        c->flowdir_own = false;
         c->acc_keep.valid = false;
         drop_flow_distance(c);
         break;
@@ -352,6 +353,7 @@ int mhip_ctx_kernel_ms(mhip_ctx *c, const char *kernel, float *ms_total, int32_t
         MH_HIP(hipEventElapsedTime(ms_total, t->a, t->b));
         c->have[MHIP_R_FLOWDIR] = true;
         c->nodir_valid = true;
+        c->flowdir_own = true;
         *launches = REPS;
         return MHIP_OK;
     }
@@ -398,6 +400,7 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "fill_hot_launches") *value = c->fill_st.hot_launches;
     else if (k == "noflat_hot_launches") *value = c->noflat_st.hot_launches;
     else if (k == "accum_algorithm") *value = c->accum_algorithm;   // 0 full accumulation, 1 a row band's second pass as a delta over the boundary pass's graph
+    else if (k == "flowdir_computed") *value = (c->have[MHIP_R_FLOWDIR] && c->flowdir_own) ? 1 : 0;   // 1 the library's D8 wrote FLOWDIR, 0 it was uploaded
     else if (k == "pour_algorithm") *value = c->pour_algorithm;   // 0 a pass over values + labels (label_ops.hip), 1 keys out of the accumulation's final pass (PourLink)
     else if (k == "noflat_algorithm") *value = c->noflat_st.algorithm;   // 0 float64 relaxation (fill.hip), 2 integer geodesic transform (noflat_geo.hip)
     else if (k == "noflat_visits") *value = c->noflat_st.visits;

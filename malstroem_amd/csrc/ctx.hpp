@@ -84,6 +84,7 @@ struct mhip_ctx {
     bool pf_done = false;                   // the flood's raster is written and proven (mhip_ctx_fill_certify); run[0] may follow it
     mh::DevBuf nodir_cnt;                   // interior NODIR cells of FLOWDIR, counted by the D8 kernel (the watersheds' fast-path test)
     bool nodir_valid = false;
+    bool flowdir_own = false;               // FLOWDIR is the library's own D8 (edges outward, no cycles, no sinks), not an upload: ctx_get_i64 "flowdir_computed"
     int device = 0, rank = 0, nranks = 1;
     hipStream_t stream = nullptr;
     mh::DevBuf r[MHIP_R_COUNT_];

@@ -472,6 +472,42 @@ int mhip_ctx_band_watershed_local(mhip_ctx *c)
     return MHIP_OK;
 }
 
+/* The band watersheds for flow directions of ANY origin (see include/malstroem_hip.h), in three steps around two seam resolutions:
+ * 1: "does my path meet a raster edge cell" as a local pass over a label raster that holds BAND_ROOT on the raster's edge cells;
+ * 2: the local pass over the labels with the rootless ones hidden behind BAND_ROOTLESS (WATERSHEDS holds step 1's resolved answer);
+ * 3: BAND_ROOTLESS -> the cell's own label (0: none).  The local passes run the plain rule "first label downstream" -- a path that
+ * ends in a sink or a cycle inside the band takes nothing -- whatever the field holds: they vouch for "no interior NODIR" themselves. */
+int mhip_ctx_band_watershed_rooted(mhip_ctx *c, int step)
+{
+    MH_ARG(c && step >= 1 && step <= 3 && c->have[MHIP_R_LABELS] && c->have[MHIP_R_FLOWDIR],
+           "ctx_band_watershed_rooted(ctx, step 1..3) needs labels and flow directions");
+    MH_ARG(step == 1 || c->r[MHIP_R_WATERSHEDS].p, "ctx_band_watershed_rooted: step 1 first");
+    MH_HIP(hipSetDevice(c->device));
+    MH_TRY(ctx_raster(c, MHIP_R_WATERSHEDS));
+    ctx_wrote(c, MHIP_R_WATERSHEDS);
+    hipStream_t s = cs(c);
+    const int64_t n = c->H * c->W;
+    int32_t *ws = c->r[MHIP_R_WATERSHEDS].as<int32_t>();
+    const int32_t *lab = c->r[MHIP_R_LABELS].as<int32_t>();
+    if (step == 3) {
+        MH_TRY(band_show_rootless_dev(ws, lab, n, s));
+        MH_HIP(stream_sync(s));
+        c->have[MHIP_R_WATERSHEDS] = true;
+        return MHIP_OK;
+    }
+    c->have[MHIP_R_WATERSHEDS] = false;
+    DevBuf tmp, zero;
+    MH_TRY(tmp.alloc(4 * (size_t)n));
+    MH_TRY(zero.alloc(4));
+    MH_HIP(hipMemsetAsync(zero.p, 0, 4, s));
+    if (step == 1) MH_TRY(band_root_labels_dev(tmp.as<int32_t>(), c->H, c->W, c->row0 - c->ht, c->H_global, s));
+    else MH_TRY(band_hide_rootless_dev(lab, ws, tmp.as<int32_t>(), n, s));
+    MH_TRY(band_pseudo_labels_dev(tmp.as<int32_t>(), c->H, c->W, c->ht, c->hb, s));
+    MH_TRY(watersheds_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), ws, c->H, c->W, 0, s, true, zero.as<unsigned int>(), tmp.as<int32_t>(), nullptr));
+    MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
 /* raster[i] = lut[-raster[i]-1] wherever raster[i] < 0 (resolves the pseudo labels once the boundary system is solved) */
 int mhip_ctx_band_apply_neg_lut(mhip_ctx *c, int which, const int32_t *lut, int64_t n)
 {
@@ -536,6 +572,11 @@ int mhip_ctx_band_records(mhip_ctx *c, int which)
         MH_ARG(c->have[MHIP_R_DEPTHS], "label_stats needs the depths");
         MH_TRY(label_stats_dev(c->r[MHIP_R_DEPTHS].as<float>() + off, c->r[MHIP_R_LABELS].as<int32_t>() + off, n, c->nlabels,
                                buf.as<mhip_stat_record>(), cs(c), c->W, c->labels_components));
+        // labels that were uploaded may hold cells of depth +0.0 and -0.0 (a bluespot of the library's own labelling has depth > 0):
+        // which zero a record reports is the label's first one in raster order, like the standalone label_stats
+        if (!c->labels_components)
+            MH_TRY(label_stats_zero_sign_dev(c->r[MHIP_R_DEPTHS].as<float>() + off, c->r[MHIP_R_LABELS].as<int32_t>() + off, n, c->nlabels,
+                                             buf.as<mhip_stat_record>(), cs(c)));
     } else if (which == 1) {
         MH_ARG(c->have[MHIP_R_WATERSHEDS], "watershed counts need the watersheds");
         MH_TRY(label_count_dev(c->r[MHIP_R_WATERSHEDS].as<int32_t>() + off, n, c->nlabels, buf.as<int64_t>(), cs(c), c->W));

@@ -97,6 +97,7 @@ static int stage_flowdir(mhip_ctx *c, hipStream_t s)
                   c->H_global, c->nodir_cnt.as<unsigned int>()));
     MH_TRY(stage_end(c, MHIP_STAGE_FLOWDIR, s));
     c->have[MHIP_R_FLOWDIR] = true;
+    c->flowdir_own = true;
     c->nodir_valid = !c->ht && !c->hb;     // (a band's halo rows are computed from clamped data: their codes do not count)
     return MHIP_OK;
 }
@@ -109,6 +110,7 @@ static int stage_flowdir_fused(mhip_ctx *c, hipStream_t s)
     ctx_wrote(c, MHIP_R_FLOWDIR);
     c->have[MHIP_R_FLOWDIR] = true;
     c->nodir_valid = true;
+    c->flowdir_own = true;
     return MHIP_OK;
 }
 

@@ -438,6 +438,31 @@ __global__ void ws_pseudo_kernel(int32_t *ws, int64_t H, int64_t W, int top, int
     if (top) ws[c] = -(int32_t)(1 + c);
     if (bottom) ws[(H - 1) * W + c] = -(int32_t)(1 + W + c);
 }
+// ---- rootedness on a band (uploaded flow directions: interior sinks, cycles, inward edges) -----------------------------------
+// Step 1 labels the cells of the RASTER's edge with BAND_ROOT (row_off: global row of local row 0); "first label downstream" on
+// that raster answers, per cell, "does my path meet an edge cell".  Step 2 hides the labels whose path does not behind
+// BAND_ROOTLESS (a label no raster holds: labels are <= nlabels < 2**31 - 1) so that they still stop the paths that reach them;
+// step 3 gives a labelled cell its own label back and leaves the cells that drained to a rootless label unassigned.
+__global__ __launch_bounds__(256) void ws_root_labels_kernel(int32_t *out, int64_t H, int64_t W, int64_t row_off, int64_t Hg)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H * W) return;
+    const int64_t r = i / W, c = i - r * W, gr = r + row_off;
+    out[i] = (gr == 0 || gr == Hg - 1 || c == 0 || c == W - 1) ? BAND_ROOT : 0;
+}
+__global__ __launch_bounds__(256) void ws_hide_rootless_kernel(const int32_t *__restrict__ lab, const int32_t *__restrict__ rooted,
+                                                              int32_t *__restrict__ out, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t l = lab[i];
+    out[i] = (l == 0 || rooted[i] == BAND_ROOT) ? l : BAND_ROOTLESS;
+}
+__global__ __launch_bounds__(256) void ws_show_rootless_kernel(int32_t *__restrict__ ws, const int32_t *__restrict__ lab, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && ws[i] == BAND_ROOTLESS) ws[i] = lab[i];      // (0 where the cell has no label of its own)
+}
 // (four cells per thread where the raster allows 16-byte accesses; the store only where a pseudo label was resolved)
 __global__ __launch_bounds__(256) void ws_neg_lut_kernel(int32_t *lab, int64_t n, const int32_t *__restrict__ lut, int64_t nlut)
 {
@@ -458,6 +483,27 @@ __global__ __launch_bounds__(256) void ws_neg_lut_kernel(int32_t *lab, int64_t n
 int band_pseudo_labels_dev(int32_t *d_ws, int64_t H, int64_t W, int top, int bottom, hipStream_t s)
 {
     hipLaunchKernelGGL(ws_pseudo_kernel, dim3((unsigned)cdiv(W, 256)), dim3(256), 0, s, d_ws, H, W, top, bottom);
+    MH_HIP(hipGetLastError());
+    return MHIP_OK;
+}
+
+int band_root_labels_dev(int32_t *d_out, int64_t H, int64_t W, int64_t row_off, int64_t Hg, hipStream_t s)
+{
+    hipLaunchKernelGGL(ws_root_labels_kernel, dim3((unsigned)cdiv(H * W, 256)), dim3(256), 0, s, d_out, H, W, row_off, Hg);
+    MH_HIP(hipGetLastError());
+    return MHIP_OK;
+}
+
+int band_hide_rootless_dev(const int32_t *d_lab, const int32_t *d_rooted, int32_t *d_out, int64_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(ws_hide_rootless_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, d_lab, d_rooted, d_out, n);
+    MH_HIP(hipGetLastError());
+    return MHIP_OK;
+}
+
+int band_show_rootless_dev(int32_t *d_ws, const int32_t *d_lab, int64_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(ws_show_rootless_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, d_ws, d_lab, n);
     MH_HIP(hipGetLastError());
     return MHIP_OK;
 }
@@ -552,7 +598,8 @@ int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W,
     MH_HIP(stream_sync(s));
     uint32_t *q = nullptr;
     if (interior_nodir && band_mode) {
-        set_error("watersheds on a row band need every flow path to leave the raster (interior NODIR cell found)");
+        set_error("watersheds on a row band in one local pass need every flow path to leave the raster (interior NODIR cell found): "
+                  "mhip_ctx_band_watershed_rooted takes any flow directions");
         return MHIP_EINVAL;
     }
     // The fast path takes "the first labelled cell downstream" without asking whether that cell's own path meets an edge cell: true

@@ -915,6 +915,11 @@ class HipBand(CtxHandle):
     def watershed_local(self):
         _lib.call("mhip_ctx_band_watershed_local", self._ctx)
 
+    def watershed_rooted(self, step):
+        """the local steps of the watersheds on flow directions of any origin (include/malstroem_hip.h: 1 rootedness pass, 2 the
+        pass over the labels with the rootless ones hidden, 3 the sentinel back to the cell's own label)"""
+        _lib.call("mhip_ctx_band_watershed_rooted", self._ctx, int(step))
+
     def apply_neg_lut(self, name, lut):
         lut = np.ascontiguousarray(lut, dtype=np.int32)
         _lib.call("mhip_ctx_band_apply_neg_lut", self._ctx, RASTERS[name], _lib.ptr(lut), _lib.i64(lut.size))
@@ -1469,12 +1474,30 @@ class BandPipeline(object):
         through the neighbours' edge rows.  Neighbours trade their edge rows (RCCL): most paths end at a label right there.  What
         is left are paths that bounce back or cross a whole band; only the edge cells on such paths are gathered -- a cell is
         published when the neighbour points at it or when its own target is unresolved as well -- and every rank follows the
-        chains to their end (``mhip_band_ws_resolve``; a flow cycle across bands stays unassigned like in _flow.pyx:276-314)."""
+        chains to their end (``mhip_band_ws_resolve``; a flow cycle across bands stays unassigned like in _flow.pyx:276-314).
+
+        The reference searches upstream from the RASTER's edge cells: a label whose own downstream path never meets one labels
+        nothing but its own cells.  The library's D8 (edges outward, strictly descending) has no such label and takes the one pass
+        above.  Flow directions that were uploaded (``get_int("flowdir_computed")`` is 0 on this band; every rank uploads or none
+        does: SPMD) may end in interior sinks or cycles behind a seam, which no band can see from its halo row: they take the pass
+        twice -- first over a label raster that holds one label on the raster's edge cells, which tells every cell whether its path is
+        ROOTED, then over the labels with the rootless ones hidden behind a sentinel (``watershed_rooted``)."""
+        b = self.band
+        # (a stand-in backend that has no rooted steps keeps the one pass: exact where every path leaves the raster)
+        if int(b.get_int("flowdir_computed")) == 1 or not hasattr(b, "watershed_rooted"):
+            self._watershed_pass(b.watershed_local)
+            return
+        self._watershed_pass(lambda: b.watershed_rooted(1))
+        self._watershed_pass(lambda: b.watershed_rooted(2))
+        self._local(b.watershed_rooted, 3)
+
+    def _watershed_pass(self, local_pass):
+        """one local pass + the seam system that resolves its pseudo labels (see ``watershed``)"""
         b, comm, W, me = self.band, self._cur_comm(), self.W, self.comm.rank
         lap = _Lap("watershed", comm.rank)
 
         def local_part():
-            b.watershed_local()
+            local_pass()
             return b.get_edge_row("watersheds", 0), b.get_edge_row("watersheds", 1)
         first, last = self._local(local_part)
         lap.lap("watershed_local + edge rows")
@@ -1643,7 +1666,9 @@ class BandPipeline(object):
             take = owned(all_ex[:, 0])
             ids, cur_src, cur_cells = all_ids[take], all_src[take], all_ex[take]
             hop += 1
-            if hop > self.H * self.W:       # (a walker bouncing forever between two bands: a flow cycle across a seam)
+            # every hop puts a walker on a cell of a first / last owned row next to a seam -- 2 W (size - 1) cells in all -- and an
+            # acyclic walk stands on a cell once: a walker that has hopped more often is on a flow cycle across a seam
+            if hop > 2 * self.W * (self.comm.size - 1):
                 for wid in all_ids.tolist():
                     results.setdefault(wid, None)
                 break

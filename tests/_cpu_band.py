@@ -89,6 +89,8 @@ class CpuBand(object):
 
     def upload(self, name, arr):
         self._raster(name)[self.ht:self.ht + self.nrows] = arr
+        if name == "flowdir":
+            self._flowdir_computed = False
 
     def download(self, name):
         return self.r[name][self.ht:self.ht + self.nrows].copy()
@@ -282,6 +284,7 @@ class CpuBand(object):
             fd[gr == maxr, 0] = 5
             fd[gr == maxr, maxc] = 3
         self._raster("flowdir")[...] = fd
+        self._flowdir_computed = True
 
     def zero_raster(self, name):
         self._raster(name)[...] = 0
@@ -425,7 +428,9 @@ class CpuBand(object):
             if 0 <= gr < self.Hg and 0 <= c < self.W and own0 <= r < own1:
                 if s_ < 0:
                     s_ = int(lab[r, c])
-                for _ in range(self.Hg * self.W):
+                seen = set()
+                while (r, c) not in seen:       # (a walker back on a cell of this leg is on a flow cycle inside the band: the HIP
+                    seen.add((r, c))            # band walks on until its cut after H * W cells and ends the same way, without a label)
                     g.append((r + row_lo) * self.W + c)
                     l = int(lab[r, c])
                     if l != s_ and (background_label is None or l != background_label):
@@ -445,35 +450,59 @@ class CpuBand(object):
             geoms.append(np.asarray(g, dtype=np.int64))
         return out_lab, status, src_out, exits, (geoms if geometry else [None] * n)
 
-    def watershed_local(self):
-        ws = self._raster("watersheds")
-        ws[...] = self.r["labels"]
+    ROOT, ROOTLESS = 1, 0x7fffffff       # the labels of the rootedness passes (mhip_ctx_band_watershed_rooted)
+
+    def _first_label_downstream(self, lab):
+        """the plain rule of the HIP band's local pass: every unlabelled cell takes the first label on its downstream path inside the
+        local raster (the halo rows' pseudo labels included), 0 where the path leaves the raster or ends in a sink or on a cycle
+        without meeting one.  Pointer doubling over all cells at once; node n stands for "nowhere"."""
+        fd = self.r["flowdir"].astype(np.int64)
+        H, W = lab.shape
+        n = H * W
+        rr, cc = np.divmod(np.arange(n), W)
+        k = np.minimum(fd.ravel(), 7)
+        DR = np.array([-1, -1, 0, 1, 1, 1, 0, -1])
+        DC = np.array([0, 1, 1, 1, 0, -1, -1, -1])
+        nr, nc = rr + DR[k], cc + DC[k]
+        flows = (fd.ravel() <= 7) & (nr >= 0) & (nr < H) & (nc >= 0) & (nc < W)
+        flat = lab.ravel()
+        P = np.where(flat != 0, np.arange(n), np.where(flows, nr * W + nc, n))
+        P = np.append(P, n)
+        for _ in range(int(n).bit_length() + 1):
+            P = P[P]
+        end = np.append(flat, 0)[P[:n]]          # a cell on a cycle ends on an unlabelled cell of that cycle: 0
+        return end.reshape(H, W).astype(np.int32)
+
+    def _with_pseudo(self, lab):
+        lab = lab.copy()
         if self.ht:
-            ws[0] = -(1 + np.arange(self.W))
+            lab[0] = -(1 + np.arange(self.W))
         if self.hb:
-            ws[-1] = -(1 + self.W + np.arange(self.W))
-        # nearest labelled cell downstream (labels incl. the negative pseudo labels are terminals), 0 when the path leaves
-        fd = self.r["flowdir"]
-        DR = [-1, -1, 0, 1, 1, 1, 0, -1]
-        DC = [0, 1, 1, 1, 0, -1, -1, -1]
-        out = ws.copy()
-        for r in range(self.H):
-            for c in range(self.W):
-                if ws[r, c] != 0:
-                    continue
-                pr, pc, res = r, c, 0
-                for _ in range(self.H * self.W):
-                    d = fd[pr, pc]
-                    if d > 7:
-                        break
-                    pr, pc = pr + DR[d], pc + DC[d]
-                    if not (0 <= pr < self.H and 0 <= pc < self.W):
-                        break
-                    if ws[pr, pc] != 0:
-                        res = ws[pr, pc]
-                        break
-                out[r, c] = res
-        ws[...] = out
+            lab[-1] = -(1 + self.W + np.arange(self.W))
+        return lab
+
+    def watershed_local(self):
+        """library-made flow directions (every path leaves the raster): the reference's search on the local raster, the halo rows
+        holding their pseudo labels"""
+        ws = self._with_pseudo(self.r["labels"])
+        oracle.watersheds_from_labels(self.r["flowdir"], ws, 0)
+        self._raster("watersheds")[...] = ws
+
+    def watershed_rooted(self, step):
+        ws = self._raster("watersheds")
+        lab = self.r["labels"]
+        if step == 1:
+            gr = np.arange(self.H) + (self.row0 - self.ht)
+            roots = np.zeros((self.H, self.W), np.int32)
+            roots[(gr == 0) | (gr == self.Hg - 1), :] = self.ROOT
+            roots[:, 0] = roots[:, -1] = self.ROOT
+            ws[...] = self._first_label_downstream(self._with_pseudo(roots))
+        elif step == 2:
+            hidden = np.where((lab == 0) | (ws == self.ROOT), lab, self.ROOTLESS).astype(np.int32)
+            ws[...] = self._first_label_downstream(self._with_pseudo(hidden))
+        else:
+            sel = ws == self.ROOTLESS
+            ws[sel] = lab[sel]
 
     def apply_neg_lut(self, name, lut):
         a = self.r[name]
@@ -481,6 +510,8 @@ class CpuBand(object):
         a[neg] = np.asarray(lut)[-a[neg] - 1]
 
     def get_int(self, key):
+        if key == "flowdir_computed":
+            return 1 if getattr(self, "_flowdir_computed", False) else 0
         return 0
 
     def _owned(self, name):
