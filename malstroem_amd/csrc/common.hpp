@@ -246,15 +246,21 @@ struct PfRun {
 // a call-back fired once, on the stage's stream, at a chosen point of a stage (mhip_ctx_run starts the label branch when the
 // no-flats fill has left its throughput-bound first rounds: see ctx_run.hip)
 struct StageHook {
+    enum Point { TAIL_ROUNDS = 1, FINISH = 3 };      // (the values of MHIP_LABEL_START that arm a hook)
     void (*fn)(void *, hipStream_t) = nullptr;
     void *arg = nullptr;
     bool fired = false;
+    int at = TAIL_ROUNDS;           // the point of the no-flats fill the hook is armed for
     void fire(hipStream_t s)
     {
         if (fn && !fired) {
             fired = true;
             fn(arg, s);
         }
+    }
+    void fire_at(int point, hipStream_t s)      // from inside a stage: only the point the hook was armed for fires it
+    {
+        if (point == at) fire(s);
     }
 };
 
@@ -269,7 +275,7 @@ struct GeoRun {
     bool allow_partial = false;                       // flats of irregular levels: leave them to the caller (else: not applicable)
     double seed_add = 0;                              // ... with the upper bound F + seed_add in `out`
     bool partial = false;                             // set by end(): `out` still needs the float64 relaxation on those flats
-    StageHook *tail_hook = nullptr;                   // fired when the first batch of rounds has been launched
+    StageHook *tail_hook = nullptr;                   // fired where it is armed for: behind the first batch of rounds (batch), or in front of the finishing pass (end)
     uint8_t *d8_out = nullptr;                        // optional: end() also writes the flow directions of the surface (one context, no halo rows)
     unsigned int *d8_nodir = nullptr;                 // ... and sets this word when an interior cell has none
     bool d8_done = false;                             // set by end(): d8_out holds the directions of the verified surface

@@ -8,6 +8,8 @@
 
 using namespace mh;
 
+constexpr int LABEL_START_DEFAULT = 3;      // chosen by measurement: DESIGN 4.5
+
 static int stage_depths(mhip_ctx *c, hipStream_t s)
 {
     MH_ARG(c->have[MHIP_R_FILLED] && c->have[MHIP_R_DEM], "depths need the filled surface");
@@ -234,6 +236,14 @@ static int stage_pourpoints(mhip_ctx *c, hipStream_t s, PourLink *pour = nullptr
     return MHIP_OK;
 }
 
+// where the label branch of a request starts.  0: with the no-flats fill, 1: at its tail rounds, 2: after it, 3: at its finishing pass
+static int label_start_env()
+{
+    const char *e = dev_env("MHIP_LABEL_START");
+    const int v = e ? atoi(e) : LABEL_START_DEFAULT;
+    return v >= 0 && v <= 3 ? v : LABEL_START_DEFAULT;
+}
+
 // Stage DAG:  FILL -> NOFLAT -> FLOWDIR -> ACCUM ------.
 //                \-> LABEL ----------\-> WATERSHED ----+-> POURPOINTS
 // A request that holds both sides runs the bluespot branch (LABEL, WATERSHED) on a second stream driven by a
@@ -251,7 +261,8 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
         MH_ARG((mask & ~(MHIP_STAGE_FLOWDIR | MHIP_STAGE_ACCUM)) == 0,
                "this stage runs through the band entry points on a row band (mhip_ctx_fill_*, mhip_ctx_band_*)");
     }
-    static const bool serial_env = [] { const char *e = dev_env("MHIP_SERIAL"); return e && e[0] == '1'; }();
+    // (development knobs are read per request: a test switches them between two requests of one process)
+    const bool serial_env = [] { const char *e = dev_env("MHIP_SERIAL"); return e && e[0] == '1'; }();
     const int side_a = mask & (MHIP_STAGE_NOFLAT | MHIP_STAGE_FLOWDIR | MHIP_STAGE_ACCUM);
     const int side_b = mask & (MHIP_STAGE_LABEL | MHIP_STAGE_WATERSHED);
     const bool overlap = side_a && side_b && !serial_env;
@@ -294,10 +305,12 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     // hand-overs between the two host threads (each value is an error code)
     std::promise<int> fill_done, shdg_done, flowdir_ready, label_ready, tail_reached;
     std::future<int> fill_fut = fill_done.get_future(), shdg_fut = shdg_done.get_future(), tail_fut = tail_reached.get_future();
-    // The label branch does not start with the no-flats fill but behind it (ev_tail).  Measured at 16384^2 (ms per step): label
+    // The label branch does not start with the no-flats fill but at its end (ev_tail).  Measured at 16384^2 (ms per step): label
     // next to the whole no-flats fill 38.0 (the fill's rounds 14.6 instead of 9.8: every one of its ~85 small launches queues behind
     // the labelling's long workgroups), from the fill's latency-bound tail rounds on 37.4, behind the fill 36.7 -- then labelling and
-    // watersheds run next to D8 + accumulation.  MHIP_LABEL_START = 0 / 1 / 2 selects (development knob).
+    // watersheds run next to D8 + accumulation.  MHIP_LABEL_START = 0 / 1 / 2 / 3 selects (development knob).  3: at the fill's
+    // finishing pass (GeoRun::end) -- one launch, no LDS: the default since round 5 (21.87 -> 21.51 ms per step; DESIGN 4.5 has the
+    // table, and the terrain on which 2 is the better choice).  Engines without such a pass fire behind the stage, like 2.
     struct TailCtx {
         mhip_ctx *c;
         std::promise<int> *p;
@@ -387,11 +400,13 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
             if (c->fill_st.have_minmax) short_diag_from_minmax(c->fill_st.dem_min, c->fill_st.dem_max, c->fill_st.dem_nan, &c->sh, &c->dg);
             else MH_TRY(short_diag_dev(c->r[MHIP_R_DEM].as<float>(), c->H * c->W, &c->sh, &c->dg, s));
         }
-        static const int label_start = [] { const char *e = dev_env("MHIP_LABEL_START"); return e ? atoi(e) : 2; }();   // 0: with the no-flats fill, 1: at its tail, 2: after it
+        const int label_start = label_start_env();
         if (label_start == 0) tail_hook.fire(s);
+        tail_hook.at = label_start;
+        const bool armed = label_start == StageHook::TAIL_ROUNDS || label_start == StageHook::FINISH;
         bool fd_done = false;
         if (mask & MHIP_STAGE_NOFLAT)
-            MH_TRY(stage_noflat(c, s, /*shdg_done=*/true, label_start == 1 ? &tail_hook : nullptr, (mask & MHIP_STAGE_FLOWDIR) != 0, &fd_done));
+            MH_TRY(stage_noflat(c, s, /*shdg_done=*/true, armed ? &tail_hook : nullptr, (mask & MHIP_STAGE_FLOWDIR) != 0, &fd_done));
         if (mask & MHIP_STAGE_FLOWDIR) {
             MH_TRY(fd_done ? stage_flowdir_fused(c, s) : stage_flowdir(c, s));
             MH_HIP(hipEventRecord(c->ev_flowdir, s));

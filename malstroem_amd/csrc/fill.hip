@@ -1106,7 +1106,9 @@ int fill_noflat_dev(const float *d_dem, double *d_out, int64_t H, int64_t W, dou
     bool partial = false;
     const double seed_add = 1.01 * (double)(H * W) * dg;      // see noflat_seed()
     const int rc = fill_noflat_geodesic_dev(d_dem, d_filled, d_out, H, W, sh, dg, seed_add, s, st, &partial, tail_hook, d8);
-    if (tail_hook) tail_hook->fire(s);      // (not applicable: the relaxation below is throughput bound all the way)
+    // (not applicable: the relaxation below is throughput bound all the way.  A hook armed for the finishing pass is left alone: no
+    // other engine has such a pass, it fires behind the stage -- at the latest by fire_at_exit)
+    if (tail_hook) tail_hook->fire_at(StageHook::TAIL_ROUNDS, s);
     if (rc != MHIP_ELIMIT && !(rc == MHIP_OK && partial)) return rc;
     if (rc == MHIP_OK) {
         // hybrid: exact everywhere but on the flats of irregular levels (a sea at elevation 0, ...), which hold the upper bound

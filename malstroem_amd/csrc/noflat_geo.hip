@@ -1233,6 +1233,114 @@ __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict_
     if (D8 && __any(anynodir != 0u) && lane == 0) *nodir = 1u;      // ("none" / "some": a plain store of the same value)
 }
 
+// The pass of a whole request (FLOWDIR in the same request: D8 above) has a body of its own -- the same values into the same
+// arithmetic, the same stores in the same order, another schedule of the loads.  Above, a row costs two dependent round trips (F
+// and d of row r + 1, a wait, the DEM of row r, a wait) with at most two loads in flight per wavefront: the pass lives on its
+// occupancy (alone, 16384^2: 1.25 ms at 8 wavefronts per SIMD, 1.45 at 6, 1.95 at 4).  Here F, d and the DEM of a row are loaded
+// together, without a branch around them, one row before they are used; the wait sits behind the row's arithmetic.
+// NG_FINISH_AHEAD=0 (build-time, A/B runs): the body above for this pass too.
+// NG_FINISH_WAVES < 8 (build-time) bounds the residency of the pass -- the register allocation is rounded up to match -- for the
+// label branch that may start beside it (mhip_ctx_run, MHIP_LABEL_START=3).  What was measured: DESIGN 4.5.
+#ifndef NG_FINISH_AHEAD
+#define NG_FINISH_AHEAD 1
+#endif
+#ifndef NG_FINISH_WAVES
+#define NG_FINISH_WAVES 8
+#endif
+#if NG_FINISH_WAVES < 8
+#define NG_FINISH_RESIDENCY __attribute__((amdgpu_waves_per_eu(1, NG_FINISH_WAVES)))
+#else
+#define NG_FINISH_RESIDENCY
+#endif
+#if NG_FINISH_AHEAD
+template <>
+__global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true>(const float *__restrict__ F, const uint32_t *__restrict__ d,
+                                                                                  const float *__restrict__ dem, double *__restrict__ G, int64_t H, int64_t W,
+                                                                                  double sh, double dg, double seed_add, int fixed_top, int fixed_bot,
+                                                                                  unsigned long long *counters, uint8_t *__restrict__ flowdir,
+                                                                                  unsigned int *nodir)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t c = ((int64_t)blockIdx.x * 4 + wave) * TI + lane - 1;
+    const int64_t rb = (int64_t)blockIdx.y * FRB;
+    const bool col_in = c >= 0 && c < W;
+    const int64_t cc = c < 0 ? 0 : (c < W ? c : W - 1);
+    const bool mine = lane >= 1 && lane <= TI && col_in;                // this lane writes (and checks) its column
+    const bool inner_col = c > 0 && c + 1 < W;
+    const double PINF = __builtin_inf();
+    unsigned unreached = 0, bad = 0, anynodir = 0;
+    struct Row {
+        float f, z;         // filled surface, DEM
+        uint32_t dd;
+    };
+    // from a cell of the raster whatever r and c are: value() knows which rows count, and the DEM is used where this lane writes
+    // (there cc == c)
+    auto load = [&](int64_t r) -> Row {
+        const int64_t at = (r < 0 ? 0 : (r < H ? r : H - 1)) * W + cc;
+        return Row{F[at], dem[at], d[at]};
+    };
+    auto value = [&](int64_t r, const Row &x) -> double {
+        if (!(r >= 0 && r < H && col_in)) return PINF;
+        if (x.dd == D_IRR) return (double)x.f + seed_add;               // (ng_assemble_kernel)
+        if (x.dd >= 0x80000000u) {
+            unreached += mine && r >= rb && r < rb + FRB ? 1u : 0u;
+            return (double)x.f + seed_add;
+        }
+        return x.dd ? (double)x.f + (double)x.dd * class_ulp(class_above(x.f)) : (double)x.f;
+    };
+    const Row xa = load(rb - 1), xb = load(rb);
+    Row x0 = load(rb + 1), x1{0.0f, 0.0f, 0u};
+    double a = value(rb - 1, xa), b = value(rb, xb);
+    double dvb = (double)xb.z;                  // the DEM at (r, c): converted where its row is waited for, so that no loaded word
+                                                // has to be copied (a copy would be a wait for the loads just issued)
+    // one row.  `xn`: the words of row r + 1, loaded a row ago; `xnn`: those of row r + 2, fetched now if another row follows in this
+    // block (`more` is a type, not a value: a branch around the loads, even a uniform one, makes the compiler wait for them where
+    // they are issued).  The rows alternate between two sets of registers: a copy from one to the other would be a wait again
+    auto row = [&](int i, const Row &xn, Row &xnn, auto more) {
+        const int64_t r = rb + i;
+        const double dv = dvb;
+        if (decltype(more)::value) xnn = load(r + 2);
+        const double n = value(r + 1, xn);
+        dvb = (double)xn.z;
+        asm volatile("" : "+v"(dvb));           // (here, not at the end of the row: the word's register is free for the next load)
+        const double al = dleft(a), ar = dright(a), bl = dleft(b), br = dright(b), nl = dleft(n), nr = dright(n);
+        if (mine && r < H) {
+            double want = dv;
+            if (r > 0 && r < H - 1 && inner_col) {
+                const double md = fmin(fmin(al, ar), fmin(nl, nr)) + dg;
+                const double me = fmin(fmin(a, bl), fmin(br, n)) + sh;
+                want = fmax(fmin(md, me), dv);
+            }
+            const bool halo = (r == 0 && fixed_top) || (r == H - 1 && fixed_bot);   // the neighbouring band checks its own rows
+            bad += (b == want || halo) ? 0u : 1u;                                    // NaN anywhere fails too
+            G[r * W + c] = b;
+            unsigned code;
+            if (r == 0 || r == H - 1 || c == 0 || c == W - 1) code = edge_code(r, c, H - 1, W - 1);
+            else {
+                code = d8_code(b, a, ar, br, nr, n, nl, bl, al);
+                anynodir |= code == 8u ? 1u : 0u;      // an interior cell without a downslope neighbour (d8.hip: the watersheds' fast-path test)
+            }
+            flowdir[r * W + c] = (uint8_t)code;
+        }
+        a = b;
+        b = n;
+    };
+    static_assert(FRB % 2 == 0, "rows in pairs");
+    int i = 0;
+    for (; i < FRB - 2 && rb + i < H; i += 2) {     // (an odd H: the second row of the raster's last pair writes nothing)
+        row(i, x0, x1, std::true_type());
+        row(i + 1, x1, x0, std::true_type());
+    }
+    if (i == FRB - 2 && rb + i < H) {
+        row(i, x0, x1, std::true_type());
+        row(i + 1, x1, x0, std::false_type());
+    }
+    if (unreached) atomicAdd(&counters[C_UNREACHED], (unsigned long long)unreached);
+    if (bad) atomicAdd(&counters[C_MISMATCH], (unsigned long long)bad);
+    if (__any(anynodir != 0u) && lane == 0) *nodir = 1u;      // ("none" / "some": a plain store of the same value)
+}
+#endif
+
 // rn(eps / 2**(E - 52)) for the binade class e (E = e - 127) with eps = M * 2**q exactly; 0: no integer weight in (0, 2**28)
 uint32_t class_weight(double eps, int e)
 {
@@ -1330,7 +1438,7 @@ int GeoRun::launch_rounds(hipStream_t s, int nb)
             a.list_next = odd ? m.d_list : m.d_list2;
             a.count_next = m.d_any + m.round + 1;
         }
-        if (m.light && tail_hook)      // (the label branch runs beside these rounds: one wavefront per workgroup, see round_body)
+        if (m.light && tail_hook && tail_hook->at == StageHook::TAIL_ROUNDS)      // (the label branch runs beside these rounds: one wavefront per workgroup, see round_body)
             hipLaunchKernelGGL(ng_round_w1_kernel, dim3((unsigned)std::min<int64_t>(m.nt, 2048)), dim3(64), (WN * (WN + 1) + 512) * sizeof(uint32_t), s, a);
         else
             hipLaunchKernelGGL(ng_round_kernel, dim3(grid), dim3(256), m.lds, s, a);
@@ -1437,7 +1545,7 @@ int GeoRun::batch(hipStream_t s, bool *active)
             return MHIP_ENOTCONV;
         }
         MH_TRY(launch_rounds(s, nb));
-        if (tail_hook) tail_hook->fire(s);      // the throughput-bound rounds are behind this point of the stream
+        if (tail_hook) tail_hook->fire_at(StageHook::TAIL_ROUNDS, s);      // the throughput-bound rounds are behind this point of the stream
         uint32_t h_any[BATCH];
         MH_HIP(hipMemcpyAsync(h_any, m.d_any + (m.round - nb), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, s));
         MH_HIP(stream_sync(s));
@@ -1475,6 +1583,9 @@ int GeoRun::end(hipStream_t s, bool *ok, FillStats *st)
         MH_HIP(hipMemsetAsync(dist + (H / 2) * W + 1, 0x01, 4 * (size_t)(W - 2), s));   // below has to catch them and send the raster to the relaxation
     d8_done = false;
     const bool with_d8 = !partial && d8_out && d8_nodir && !fixed_top && !fixed_bot;
+    // every round (and the test hook's memset) is behind this point of the stream: what follows is one launch, a pure stream over
+    // HBM that leaves the LDS alone -- the label branch may run beside it (mhip_ctx_run, MHIP_LABEL_START=3)
+    if (tail_hook) tail_hook->fire_at(StageHook::FINISH, s);
     if (with_d8)
         hipLaunchKernelGGL(ng_finish_kernel<true>, dim3((unsigned)((W + 4 * TI - 1) / (4 * TI)), (unsigned)((H + FRB - 1) / FRB)), dim3(256), 0, s, filled, dist, dem,
                            out, H, W, sh, dg, seed_add, fixed_top, fixed_bot, m.d_cnt, d8_out, d8_nodir);
