@@ -149,6 +149,12 @@ __host__ __device__ inline float key_f32(uint32_t k)
     memcpy(&f, &u, 4);
     return f;
 }
+// the flood's key of an elevation (pflood.hip; the fused first visit of noflat_geo.hip computes the same surface from it)
+__device__ __forceinline__ uint32_t dem_key(float v)
+{
+    if (v != v) return f32_key(__builtin_inff());   // a NaN cell never wins a comparison (_fill.pyx:22): like +inf
+    return f32_key(v + 0.0f);                        // -0.0 -> +0.0: the two compare equal in the reference
+}
 __host__ __device__ inline uint64_t f64_key(double f)
 {
     uint64_t u;
@@ -211,14 +217,42 @@ struct FillRun {
     int finish(hipStream_t s, FillStats *st);
 };
 void noflat_seed(FillRun &f, const float *d_filled, double sh, double dg, int64_t ncells_global);
+// The hand-over of the flood's last pass to the no-flats fill's first visit (one request holds both: mhip_ctx_run).  The flood
+// stops behind pf_final_kernel and keeps its workspace: `pending`.  The geodesic transform's first visit (noflat_geo.hip:
+// ng_handover_kernel) then computes F of every window from dem + basin slots + final levels, writes `filled` and `depths` and
+// evaluates the flood's proof on the way: `queued`; the workspace goes back to the pool behind the stream sync of GeoRun::begin,
+// which reads the proof flag with its own counters.  A failed proof there (`suspect`) keeps the workspace: like a transform that
+// does not run at all it leaves `pending` set, and fill_handover_complete() -- the flood's own last pass and proof, late -- writes
+// and decides; a surface that fails there too (`violated`) is an upper bound: fill_handover_repair().
+struct PfRun;
+struct FillHandover {
+    PfRun *run = nullptr;               // owns the flood's workspace while pending
+    const float *dem = nullptr;
+    float *filled = nullptr, *depths = nullptr;
+    int64_t H = 0, W = 0;
+    const uint16_t *bslot = nullptr;    // device pointers into the flood's workspace
+    const uint32_t *tabV = nullptr;
+    int ntr = 0, ntc = 0;
+    bool pending = false, queued = false, violated = false, repaired = false;
+    bool suspect = false;               // the proof failed in the fused visit: the flood's own last pass decides (and is what ran last)
+    FillStats st_repair;                // the relaxation that repaired a surface whose proof failed
+    FillHandover() = default;
+    FillHandover(const FillHandover &) = delete;
+    FillHandover &operator=(const FillHandover &) = delete;
+    ~FillHandover();
+    void release();                     // the flood's workspace goes back to the pool (the stream has been synchronised)
+};
+int fill_handover_complete(FillHandover *ho, hipStream_t s);   // pflood.hip + fill.hip: K4 and the proof as PfRun::finish runs them; repairs
+int fill_handover_repair(FillHandover *ho, hipStream_t s);     // fill.hip: FillRun::attach + certify on `filled`, then the depths
+// ho (optional): the flood may stop behind pf_final_kernel (ho->pending; *depths_done is set: the pass that writes them is owed)
 int fill_plain_dev(const float *d_dem, float *d_out, int64_t H, int64_t W, hipStream_t s, FillStats *st, float *d_depths = nullptr,
-                   bool *depths_done = nullptr);
+                   bool *depths_done = nullptr, FillHandover *ho = nullptr);
 // check.hip: *d_flag (zeroed by the caller) = 1 when `filled` is not a fixed point of the plain fill with border == dem
 int fill_check_f32_dev(const float *d_dem, const float *d_filled, int64_t H, int64_t W, int fixed_top, int fixed_bot, hipStream_t s,
                        unsigned int *d_flag);
 // pflood.hip
 int fill_plain_pflood_dev(const float *d_dem, float *d_out, float *d_depths, int64_t H, int64_t W, hipStream_t s, FillStats *st, bool *violated = nullptr,
-                          uint32_t *overflow = nullptr);
+                          uint32_t *overflow = nullptr, FillHandover *ho = nullptr);
 // pflood.hip: the exact tiled priority-flood, resumable for row bands (whose halo rows of `out` carry the neighbours' current
 // estimates of their filled edge rows; this band's own edge rows in `out` are kept current for them)
 struct PfRun {
@@ -238,7 +272,11 @@ struct PfRun {
     int batch(hipStream_t s);                     // MHIP_ELIMIT as above
     // writes the raster, then proves it (check.hip); *violated: the surface is not the fixed point (it still is an upper bound of
     // it): the caller lets the iterative schedule finish the job (FillRun::attach + certify)
-    int finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated = nullptr);
+    // ho: the deferred form -- pf_final_kernel only, the workspace is kept and *ho points into it (ho->pending); finish_late() is
+    // the rest of finish() for a hand-over nobody took
+    int finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated = nullptr, FillHandover *ho = nullptr);
+    int finish_late(hipStream_t s, float *d_depths, bool *violated);
+    int proof_flag(hipStream_t s, unsigned int *h_flag);      // reads the proof's flag back (synchronises)
     int solve(hipStream_t s);
     int pack(hipStream_t s, int row0, int nrows);
     int publish_edges(hipStream_t s);
@@ -246,7 +284,7 @@ struct PfRun {
 // a call-back fired once, on the stage's stream, at a chosen point of a stage (mhip_ctx_run starts the label branch when the
 // no-flats fill has left its throughput-bound first rounds: see ctx_run.hip)
 struct StageHook {
-    enum Point { TAIL_ROUNDS = 1, FINISH = 3 };      // (the values of MHIP_LABEL_START that arm a hook)
+    enum Point { FIRST_VISIT = 0, TAIL_ROUNDS = 1, FINISH = 3 };      // (the values of MHIP_LABEL_START that arm a hook; 0 only with a hand-over: behind the visit that writes the depths)
     void (*fn)(void *, hipStream_t) = nullptr;
     void *arg = nullptr;
     bool fired = false;
@@ -279,6 +317,7 @@ struct GeoRun {
     uint8_t *d8_out = nullptr;                        // optional: end() also writes the flow directions of the surface (one context, no halo rows)
     unsigned int *d8_nodir = nullptr;                 // ... and sets this word when an interior cell has none
     bool d8_done = false;                             // set by end(): d8_out holds the directions of the verified surface
+    FillHandover *handover = nullptr;                 // pending: begin() computes, writes and proves `filled` (and the depths) in its first visit
     struct Impl;
     Impl *impl;
     GeoRun();
@@ -300,11 +339,13 @@ struct D8Sink {
     bool done = false;
 };
 int fill_noflat_geodesic_dev(const float *d_dem, const float *d_filled, double *d_out, int64_t H, int64_t W, double sh, double dg, double seed_add,
-                             hipStream_t s, FillStats *st, bool *partial, StageHook *tail_hook = nullptr, D8Sink *d8 = nullptr);
+                             hipStream_t s, FillStats *st, bool *partial, StageHook *tail_hook = nullptr, D8Sink *d8 = nullptr, FillHandover *ho = nullptr);
 int noflat_verify_dev(const float *d_dem, const double *d_out, int64_t H, int64_t W, double sh, double dg, hipStream_t s, bool *ok, int fixed_top = 0,
                       int fixed_bot = 0);
+// ho (optional, pending): d_filled is still owed by the flood -- whatever engine runs, it holds the plain fill before it is read
 int fill_noflat_dev(const float *d_dem, double *d_out, int64_t H, int64_t W, double sh, double dg, hipStream_t s,
-                    FillStats *st = nullptr, const float *d_filled = nullptr, StageHook *tail_hook = nullptr, D8Sink *d8 = nullptr);
+                    FillStats *st = nullptr, const float *d_filled = nullptr, StageHook *tail_hook = nullptr, D8Sink *d8 = nullptr,
+                    FillHandover *ho = nullptr);
 int short_diag_dev(const float *d_dem, int64_t n, double *sh, double *dg, hipStream_t s);
 int depths_dev(const float *d_filled, const float *d_dem, float *d_out, int64_t n, hipStream_t s);
 // d8.hip

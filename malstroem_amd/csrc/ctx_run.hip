@@ -9,6 +9,15 @@
 using namespace mh;
 
 constexpr int LABEL_START_DEFAULT = 3;      // chosen by measurement: DESIGN 4.5
+constexpr int FILL_HANDOVER_DEFAULT = 1;    // chosen by measurement: DESIGN 7
+
+// MHIP_FILL_HANDOVER = 0 | 1 (development knob, read per request): may a request that holds FILL and NOFLAT leave the flood's
+// last pass and its proof to the first visit of the no-flats fill?
+static bool fill_handover_env()
+{
+    const char *e = dev_env("MHIP_FILL_HANDOVER");
+    return e ? e[0] != '0' : FILL_HANDOVER_DEFAULT != 0;
+}
 
 static int stage_depths(mhip_ctx *c, hipStream_t s)
 {
@@ -21,7 +30,9 @@ static int stage_depths(mhip_ctx *c, hipStream_t s)
 }
 
 // with_depths == false: the caller computes the bluespot depths on another stream (stage DAG)
-static int stage_fill(mhip_ctx *c, hipStream_t s, bool with_depths = true)
+// ho: the flood may leave FILLED and DEPTHS to the no-flats stage of the same request (ho->pending on return; neither raster is
+// marked resident before that stage has queued the pass that writes them); the stage's time then ends behind pf_final_kernel
+static int stage_fill(mhip_ctx *c, hipStream_t s, bool with_depths = true, FillHandover *ho = nullptr)
 {
     const int64_t H = c->H, W = c->W;
     MH_ARG(c->have[MHIP_R_DEM], "FILL needs the DEM");
@@ -31,11 +42,12 @@ static int stage_fill(mhip_ctx *c, hipStream_t s, bool with_depths = true)
     FillStats st;
     bool depths_done = false;   // the priority-flood's last pass writes filled - dem next to the filled surface
     MH_TRY(fill_plain_dev(c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_FILLED].as<float>(), H, W, s, &st, c->r[MHIP_R_DEPTHS].as<float>(),
-                          &depths_done));
+                          &depths_done, ho));
     ctx_wrote(c, MHIP_R_FILLED);
     ctx_wrote(c, MHIP_R_DEPTHS);
-    c->have[MHIP_R_FILLED] = true;
-    c->have[MHIP_R_DEPTHS] = depths_done;
+    const bool owed = ho && ho->pending;
+    c->have[MHIP_R_FILLED] = !owed;
+    c->have[MHIP_R_DEPTHS] = depths_done && !owed;
     if (with_depths && !depths_done) MH_TRY(stage_depths(c, s));
     MH_TRY(stage_end(c, MHIP_STAGE_FILL, s));
     c->fill_rounds = st.rounds;
@@ -46,8 +58,26 @@ static int stage_fill(mhip_ctx *c, hipStream_t s, bool with_depths = true)
 // shdg_done: minimum_safe_short_and_diag of the current DEM is already in c->sh / c->dg (computed next to the fill)
 // with_flowdir: FLOWDIR is part of the same request -- the geodesic transform's finishing pass writes the directions as well when
 // it can (one context, regular surface); *flowdir_done then tells the caller that stage_flowdir has nothing left to do
+// ho (pending): FILLED and DEPTHS are still owed by the flood of this request; they become resident when the pass that writes
+// them has been queued (ctx_handover_settled: from the hook that starts the label branch, and behind the stage)
+static void ctx_handover_settled(mhip_ctx *c, FillHandover *ho)
+{
+    if (!ho || ho->pending || c->have[MHIP_R_FILLED]) return;
+    c->have[MHIP_R_FILLED] = true;
+    c->have[MHIP_R_DEPTHS] = true;
+    c->fill_handover = ho->queued ? 1 : 0;
+    if (ho->suspect) ++c->fill_handover_rechecks;
+    if (ho->repaired) {      // the proof failed in the fused visit: flood + repair (fill_plain_dev reports the same)
+        c->fill_st.algorithm = 4;
+        c->fill_st.rounds += ho->st_repair.rounds;
+        c->fill_st.visits += ho->st_repair.visits;
+        c->fill_st.cycles += ho->st_repair.cycles;
+        c->fill_rounds = c->fill_st.rounds;
+    }
+}
+
 static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, StageHook *tail_hook = nullptr, bool with_flowdir = false,
-                        bool *flowdir_done = nullptr)
+                        bool *flowdir_done = nullptr, FillHandover *ho = nullptr)
 {
     const int64_t H = c->H, W = c->W, n = H * W;
     MH_ARG(c->have[MHIP_R_DEM], "NOFLAT needs the DEM");
@@ -56,11 +86,11 @@ static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, Stag
     if (!shdg_done) {
         // (the flood of THIS DEM has folded its extremes on the way: a request without the bluespot branch -- BASELINE configs[1] -- used
         // to run the reduction over the DEM all the same, 0.38 ms of its 2.15 ms step)
-        if (c->have[MHIP_R_FILLED] && c->fill_st.have_minmax) short_diag_from_minmax(c->fill_st.dem_min, c->fill_st.dem_max, c->fill_st.dem_nan, &c->sh, &c->dg);
+        if ((c->have[MHIP_R_FILLED] || (ho && ho->pending)) && c->fill_st.have_minmax) short_diag_from_minmax(c->fill_st.dem_min, c->fill_st.dem_max, c->fill_st.dem_nan, &c->sh, &c->dg);
         else MH_TRY(short_diag_dev(c->r[MHIP_R_DEM].as<float>(), n, &c->sh, &c->dg, s));
     }
     FillStats st;
-    if (!c->have[MHIP_R_FILLED]) {  // the plain fill seeds the no-flats iteration (fill_noflat_dev)
+    if (!c->have[MHIP_R_FILLED] && !(ho && ho->pending)) {  // the plain fill seeds the no-flats iteration (fill_noflat_dev)
         MH_TRY(ctx_raster(c, MHIP_R_FILLED));
         FillStats st0;
         MH_TRY(fill_plain_dev(c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_FILLED].as<float>(), H, W, s, &st0));
@@ -76,8 +106,10 @@ static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, Stag
         d8.flowdir = c->r[MHIP_R_FLOWDIR].as<uint8_t>();
         d8.nodir = c->nodir_cnt.as<unsigned int>();
     }
-    MH_TRY(fill_noflat_dev(c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_NOFLAT].as<double>(), H, W, c->sh, c->dg, s, &st,
-                           c->r[MHIP_R_FILLED].as<float>(), tail_hook, d8.flowdir ? &d8 : nullptr));
+    const int rc_nf = fill_noflat_dev(c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_NOFLAT].as<double>(), H, W, c->sh, c->dg, s, &st,
+                                      c->r[MHIP_R_FILLED].as<float>(), tail_hook, d8.flowdir ? &d8 : nullptr, ho);
+    ctx_handover_settled(c, ho);
+    MH_TRY(rc_nf);
     if (flowdir_done) *flowdir_done = d8.done;
     MH_TRY(stage_end(c, MHIP_STAGE_NOFLAT, s));
     c->noflat_rounds = st.rounds;
@@ -266,11 +298,19 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     const int side_a = mask & (MHIP_STAGE_NOFLAT | MHIP_STAGE_FLOWDIR | MHIP_STAGE_ACCUM);
     const int side_b = mask & (MHIP_STAGE_LABEL | MHIP_STAGE_WATERSHED);
     const bool overlap = side_a && side_b && !serial_env;
+    // FILL and NOFLAT in one request on one undivided raster: the flood may stop behind its final levels and leave the raster, the
+    // depths and its proof to the first visit of the no-flats fill (common.hpp: FillHandover).  Whether that visit runs at all is
+    // known only in the stage itself (the epsilons, the engine knobs): a hand-over nobody takes is completed there by the flood's
+    // own last pass.
+    FillHandover handover;
+    FillHandover *const ho =
+        ((mask & MHIP_STAGE_FILL) && (mask & MHIP_STAGE_NOFLAT) && c->nranks == 1 && !c->ht && !c->hb && fill_handover_env()) ? &handover : nullptr;
+    c->fill_handover = 0;
 
     if (!overlap) {
-        if (mask & MHIP_STAGE_FILL) MH_TRY(stage_fill(c, s));
+        if (mask & MHIP_STAGE_FILL) MH_TRY(stage_fill(c, s, true, ho));
         bool fd_done = false;
-        if (mask & MHIP_STAGE_NOFLAT) MH_TRY(stage_noflat(c, s, false, nullptr, (mask & MHIP_STAGE_FLOWDIR) != 0, &fd_done));
+        if (mask & MHIP_STAGE_NOFLAT) MH_TRY(stage_noflat(c, s, false, nullptr, (mask & MHIP_STAGE_FLOWDIR) != 0, &fd_done, ho));
         if (mask & MHIP_STAGE_FLOWDIR) MH_TRY(fd_done ? stage_flowdir_fused(c, s) : stage_flowdir(c, s));
         if (mask & MHIP_STAGE_ACCUM) MH_TRY(stage_accum(c, s));
         if (mask & MHIP_STAGE_LABEL) MH_TRY(stage_label(c, s));
@@ -314,11 +354,13 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     struct TailCtx {
         mhip_ctx *c;
         std::promise<int> *p;
-    } tail_ctx{c, &tail_reached};
+        FillHandover *ho;
+    } tail_ctx{c, &tail_reached, ho};
     StageHook tail_hook;
     tail_hook.arg = &tail_ctx;
     tail_hook.fn = [](void *arg, hipStream_t st) {
         TailCtx *t = static_cast<TailCtx *>(arg);
+        ctx_handover_settled(t->c, t->ho);      // (the other thread reads have[DEPTHS] behind this event)
         t->p->set_value(hipEventRecord(t->c->ev_tail, st) == hipSuccess ? MHIP_OK : MHIP_EHIP);
     };
     std::future<int> flowdir_fut = flowdir_ready.get_future(), label_fut = label_ready.get_future();
@@ -388,7 +430,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
         pour_link.notify(pour_link.arg, 0);       // (no candidates if the watersheds never got that far: nobody is left waiting)
     });
     int rc_a = MHIP_OK;
-    if (do_fill) rc_a = stage_fill(c, s, /*with_depths=*/false);
+    if (do_fill) rc_a = stage_fill(c, s, /*with_depths=*/false, ho);
     if (rc_a == MHIP_OK && hipEventRecord(c->ev_fork, s) != hipSuccess) rc_a = MHIP_EHIP;
     fill_done.set_value(rc_a);            // releases the other thread in either case
     const int rc_e = shdg_fut.get();
@@ -401,12 +443,14 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
             else MH_TRY(short_diag_dev(c->r[MHIP_R_DEM].as<float>(), c->H * c->W, &c->sh, &c->dg, s));
         }
         const int label_start = label_start_env();
-        if (label_start == 0) tail_hook.fire(s);
+        // (0 with a hand-over pending: the depths the label branch reads are written by the stage's first visit -- the hook fires behind it)
+        const bool owed = ho && ho->pending;
+        if (label_start == 0 && !owed) tail_hook.fire(s);
         tail_hook.at = label_start;
-        const bool armed = label_start == StageHook::TAIL_ROUNDS || label_start == StageHook::FINISH;
+        const bool armed = label_start == StageHook::TAIL_ROUNDS || label_start == StageHook::FINISH || (label_start == StageHook::FIRST_VISIT && owed);
         bool fd_done = false;
         if (mask & MHIP_STAGE_NOFLAT)
-            MH_TRY(stage_noflat(c, s, /*shdg_done=*/true, armed ? &tail_hook : nullptr, (mask & MHIP_STAGE_FLOWDIR) != 0, &fd_done));
+            MH_TRY(stage_noflat(c, s, /*shdg_done=*/true, armed ? &tail_hook : nullptr, (mask & MHIP_STAGE_FLOWDIR) != 0, &fd_done, ho));
         if (mask & MHIP_STAGE_FLOWDIR) {
             MH_TRY(fd_done ? stage_flowdir_fused(c, s) : stage_flowdir(c, s));
             MH_HIP(hipEventRecord(c->ev_flowdir, s));

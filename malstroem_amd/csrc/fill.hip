@@ -1038,14 +1038,29 @@ static int fill_run_to_convergence(FillRun &f, hipStream_t s, FillStats *st)
 // of this file takes over when a tile exceeds one of the flood's capacities, for rasters without an interior, and when
 // MHIP_FILL=iterative is set.  d_depths (optional): filled - dem, written by the flood's last pass (*depths_done = true) --
 // the iterative path leaves it to the caller.
-int fill_plain_dev(const float *d_dem, float *d_out, int64_t H, int64_t W, hipStream_t s, FillStats *st, float *d_depths, bool *depths_done)
+// the surface in ho->filled failed the flood's proof (it still is an upper bound): the iterative schedule finishes the job from
+// there, as fill_plain_dev does for a surface that fails in the flood's own last pass; the depths are recomputed
+int fill_handover_repair(FillHandover *ho, hipStream_t s)
+{
+    FillRun h;
+    h.noflat = false; h.dem = ho->dem; h.out = ho->filled; h.H = ho->H; h.W = ho->W;
+    MH_TRY(h.attach(s));
+    for (bool changed = true; changed;) MH_TRY(h.certify(s, &changed));
+    MH_TRY(h.finish(s, &ho->st_repair));
+    if (ho->depths) MH_TRY(depths_dev(ho->filled, ho->dem, ho->depths, ho->H * ho->W, s));
+    ho->repaired = true;
+    return MHIP_OK;
+}
+
+int fill_plain_dev(const float *d_dem, float *d_out, int64_t H, int64_t W, hipStream_t s, FillStats *st, float *d_depths, bool *depths_done,
+                   FillHandover *ho)
 {
     const bool force_iter = [] { const char *e = dev_env("MHIP_FILL"); return e && std::string(e) == "iterative"; }();   // (development: engine selection for A/B runs and tests)
     if (depths_done) *depths_done = false;
     uint32_t overflow = 0;      // the flood's capacities that gave out, if it was tried (FillStats::overflow)
     if (!force_iter && H >= 3 && W >= 3) {
         bool violated = false;
-        const int rc = fill_plain_pflood_dev(d_dem, d_out, d_depths, H, W, s, st, &violated, &overflow);
+        const int rc = fill_plain_pflood_dev(d_dem, d_out, d_depths, H, W, s, st, &violated, &overflow, ho);
         if (rc == MHIP_OK && !violated) {
             if (depths_done) *depths_done = d_depths != nullptr;
             if (st) st->algorithm = 1;
@@ -1094,7 +1109,7 @@ void noflat_seed(FillRun &f, const float *d_filled, double sh, double dg, int64_
 }
 
 int fill_noflat_dev(const float *d_dem, double *d_out, int64_t H, int64_t W, double sh, double dg, hipStream_t s,
-                    FillStats *st, const float *d_filled, StageHook *tail_hook, D8Sink *d8)
+                    FillStats *st, const float *d_filled, StageHook *tail_hook, D8Sink *d8, FillHandover *ho)
 {
     if (d8) d8->done = false;
     struct FireAtExit {     // whatever path is taken, the hook fires (at the latest when the stage is done)
@@ -1105,7 +1120,9 @@ int fill_noflat_dev(const float *d_dem, double *d_out, int64_t H, int64_t W, dou
     // the integer geodesic transform of noflat_geo.hip first; it hands back MHIP_ELIMIT for what it does not cover
     bool partial = false;
     const double seed_add = 1.01 * (double)(H * W) * dg;      // see noflat_seed()
-    const int rc = fill_noflat_geodesic_dev(d_dem, d_filled, d_out, H, W, sh, dg, seed_add, s, st, &partial, tail_hook, d8);
+    // (a pending hand-over: the transform's first visit takes it, or -- not applicable before any launch -- completes the flood's last pass)
+    const int rc = fill_noflat_geodesic_dev(d_dem, d_filled, d_out, H, W, sh, dg, seed_add, s, st, &partial, tail_hook, d8, ho);
+    if (ho && ho->pending) MH_TRY(fill_handover_complete(ho, s));      // (the transform returned early with an error code of its own)
     // (not applicable: the relaxation below is throughput bound all the way.  A hook armed for the finishing pass is left alone: no
     // other engine has such a pass, it fires behind the stage -- at the latest by fire_at_exit)
     if (tail_hook) tail_hook->fire_at(StageHook::TAIL_ROUNDS, s);

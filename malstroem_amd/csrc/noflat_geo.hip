@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "handover_addr.hpp"
 
 namespace mh {
 
@@ -63,7 +64,8 @@ constexpr int DPP_WF_SR1 = 0x138;          // lane i <- lane i-1
 #ifndef NG_MAXCYC
 #define NG_MAXCYC 1      // local (down, up, right, left) cycles per visit; a visit that is cut off re-queues its own tile
 #endif
-enum { C_IRREGULAR = 0, C_UNREACHED = 1, C_MISMATCH = 2, C_FATAL = 3, C_STATS = 8 };   // counters[]; C_STATS: 64 x {visits, cycles}
+enum { C_IRREGULAR = 0, C_UNREACHED = 1, C_MISMATCH = 2, C_FATAL = 3, C_PROOF = 4, C_STATS = 8 };   // counters[]; C_PROOF: the flood's surface failed its proof (ng_handover_kernel); C_STATS: 64 x {visits, cycles}
+static_assert(WN == ho::WN && TI == ho::TI, "handover_addr.hpp cuts the raster like this file");
 
 __device__ __forceinline__ uint32_t from_left(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, DPP_WF_SR1, 0xf, 0xf, true); }
 __device__ __forceinline__ uint32_t from_right(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, DPP_WF_SL1, 0xf, 0xf, true); }
@@ -112,6 +114,11 @@ struct GeoArgs {
     int *list_next;
     uint32_t *count_next;
     int fixed_top, fixed_bot;       // row band: local row 0 / H - 1 is a halo row of the neighbouring band (not a raster border, not mine)
+    // ng_handover_kernel: the plain fill is not read but computed -- and written, and proven -- from what the flood left behind
+    const float *ho_dem;
+    const uint16_t *ho_bslot;       // [H * W] basin slot of every interior cell
+    const uint32_t *ho_tabV;        // [nt * NBMAX] final level keys (behind pf_final_kernel)
+    float *ho_F, *ho_depths;        // outputs: the filled surface, filled - dem (may be null)
 };
 
 // 64 x 64 transpose of 32-bit words through a wave-private LDS scratch [64][65].  The DS instructions are written out: one
@@ -131,6 +138,13 @@ template <int R0, int N> __device__ __forceinline__ void lds_put_rows(uint32_t a
     if constexpr (N > 0) {
         lds_put<R0 * (WN + 1) * 4>(addr, x[R0]);
         lds_put_rows<R0 + 1, N - 1>(addr, x);
+    }
+}
+template <int R0, int N> __device__ __forceinline__ void lds_get_rows(uint32_t addr, uint32_t (&x)[WN])
+{
+    if constexpr (N > 0) {
+        x[R0] = lds_get<R0 * (WN + 1) * 4>(addr);
+        lds_get_rows<R0 + 1, N - 1>(addr, x);
     }
 }
 template <int C0, int N> __device__ __forceinline__ void lds_get_cols(uint32_t addr, uint32_t (&x)[WN])
@@ -600,7 +614,7 @@ __device__ __forceinline__ void relax_open(uint32_t (&d)[WN], const uint32_t S, 
 // with a header word (seams, class, "holds a flat cell at all"); distances start from the classification alone.  Later visits
 // (ng_round_kernel) load header, block and distances and go straight to the passes.
 constexpr uint32_t HDR_ACTIVE = 1u << 31, HDR_UNIFORM = 1u << 9, HDR_OPEN = 1u << 10, HDR_TWO = 1u << 11;   // (HDR_TWO: bits 24..30 = second class - first + 64)
-template <bool FIRST>
+template <bool FIRST, bool HANDOVER = false>
 __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *tab_l, uint32_t scr_b, int lane, unsigned &visits, unsigned &cycles)
 {
 #ifdef NG_PROFILE
@@ -639,6 +653,7 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
         const float PINF = __builtin_inff();
         const int border_row = (int)(H - 1 - r0 < 2 * WN ? H - 1 - r0 : 2 * WN);   // window row of the raster's last row (or beyond the window)
         uint32_t lake_any = 0, nirr = 0, nfatal = 0;
+        uint32_t proof_bad = 0;      // HANDOVER: the flood's proof failed at a cell of this window
         // INNER: the window lies inside the raster and touches none of its border rows / columns (all tiles but the outermost ring): no
         // clamped row offsets, no border tests -- each of them a scalar compare and a live SGPR pair per row of a loop that is short of
         // SGPRs (the compiler parks them in VGPR lanes: 1200 v_readlane / v_writelane in the general version)
@@ -646,11 +661,106 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
             constexpr bool INNER = decltype(inner_tag)::value;
             const bool lane_in_c = INNER ? ((lane >= 1) & (lane <= TI)) : lane_in;
             float f[WN];
-            int so = 0;
+            uint32_t raised[2] = {0u, 0u};      // HANDOVER: bit r & 31 of word r >> 5 = "F > dem" at window row r
+            if constexpr (!HANDOVER) {
+                int so = 0;
 #pragma unroll
-            for (int r = 0; r < WN; ++r) {
-                f[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rf, (int)((INNER ? (uint32_t)lane : lane_c) * 4u), INNER ? r * Wi * 4 : so * 4, 0));
-                so = r < last_row ? so + Wi : so;
+                for (int r = 0; r < WN; ++r) {
+                    f[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rf, (int)((INNER ? (uint32_t)lane : lane_c) * 4u), INNER ? r * Wi * 4 : so * 4, 0));
+                    so = r < last_row ? so + Wi : so;
+                }
+            } else {
+                // ---- the flood's last pass for this window (pflood.hip: pf_row_finish): F = max(dem, final level of the cell's basin), a
+                // raster border cell keeps its elevation bit for bit.  Per row: elevation + basin slot, then the level (a gather from a
+                // table that lives in L2), then F, its proof bits ("raised": F > dem, kept for the classification's `lower`; "below":
+                // F < dem, a violation wherever it is) and the stores of F and F - dem; F goes on to the classification through the
+                // wave's LDS scratch.  Addresses: handover_addr.hpp (checked on the host by tools/handover_addr_check.cpp).
+                const ho::Win w = ho::window(H, W, a.ntr, a.ntc, ti, tj);
+                const int64_t tab0 = ho::tab_origin(w), tab_left = ho::tab_words_behind_origin(w) * 4;
+                const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ho_dem + org), 0, 0x7fffffff, 0x00020000);
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ho_bslot + org), 0, 0x7fffffff, 0x00020000);
+                const __amdgpu_buffer_rsrc_t rt =
+                    __builtin_amdgcn_make_buffer_rsrc((void *)(a.ho_tabV + tab0), 0, (int)(tab_left < 0x7fffffff ? tab_left : 0x7fffffff), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc((void *)(a.ho_F + org), 0, 0x7fffffff, 0x00020000);
+                // (no depths wanted: a buffer of no records, whose stores the bounds check drops -- no branch around 62 stores)
+                const __amdgpu_buffer_rsrc_t rD =
+                    __builtin_amdgcn_make_buffer_rsrc((void *)(a.ho_depths ? a.ho_depths + org : a.ho_F), 0, a.ho_depths ? 0x7fffffff : 0, 0x00020000);
+                const uint32_t col_read = INNER ? (uint32_t)lane : (uint32_t)ho::col_of(w, lane);
+                const bool bcol = INNER ? false : ho::border_col(w, lane);
+                const uint32_t lane_bytes = ho::tab_lane_words(w, lane) * 4u;
+                const int row_bytes_top = (int)(ho::tab_row_words(w, 0) * 4u), row_bytes_mid = (int)(ho::tab_row_words(w, 1) * 4u),
+                          row_bytes_bot = (int)(ho::tab_row_words(w, WN - 1) * 4u);
+                const bool ocol = INNER ? lane_in_c : ho::own_col(w, lane);
+                volatile __attribute__((address_space(3))) uint32_t *const scr_p = (volatile __attribute__((address_space(3))) uint32_t *)(uintptr_t)scr_b + lane;
+                uint32_t below = 0u;
+                // sixteen rows a batch, three batches in flight (loads of q + 2, gathers of q + 1, arithmetic of q): all 64 rows at once
+                // are 128 registers of loaded words next to what the tile loop keeps, and the register allocator spilled them
+                constexpr int QR = 16;
+                uint32_t sl[WN];
+                auto load_q = [&](int q) {
+#pragma unroll
+                    for (int r = q * QR; r < (q + 1) * QR; ++r) {
+                        const int so = INNER ? r * Wi : (r < last_row ? r : last_row) * Wi;
+                        f[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(re, (int)(col_read * 4u), so * 4, 0));
+                        sl[r] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)(col_read * 2u), so * 2, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                auto gather_q = [&](int q) {
+#pragma unroll
+                    for (int r = q * QR; r < (q + 1) * QR; ++r) {
+                        const bool border = INNER ? false : (bcol | ho::border_row(w, r));
+                        // (a border cell's slot was never written: selected away, not branched around)
+                        sl[r] = __builtin_amdgcn_raw_buffer_load_b32(rt, (int)(lane_bytes + ho::tab_slot(sl[r], border) * 4u),
+                                                                     r == 0 ? row_bytes_top : (r == WN - 1 ? row_bytes_bot : row_bytes_mid), 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                auto finish_q = [&](int q) {
+#pragma unroll
+                    for (int r = q * QR; r < (q + 1) * QR; ++r) {
+                        const bool border = INNER ? false : (bcol | ho::border_row(w, r));
+                        const float e = f[r];
+                        const float lev = key_f32(max(dem_key(e), sl[r]));
+                        const float v = border ? e : lev;
+                        raised[r >> 5] |= v > e ? 1u << (r & 31) : 0u;
+                        below |= v < e ? 1u : 0u;              // anywhere in the window: a ring cell's F is what its owner computes
+                        asm volatile("" : "+v"(below), "+v"(raised[r >> 5]));      // (accumulated row by row: a reassociated OR tree keeps all 64 comparisons alive)
+                        if ((INNER ? (r >= 1 && r <= TI) : ho::own_row(w, r)) && ocol) {
+                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rF, lane * 4, r * Wi * 4, 0);
+                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v - e), rD, lane * 4, r * Wi * 4, 0);      // (NaN for a NaN cell)
+                        }
+                        scr_p[r * (WN + 1)] = __float_as_uint(v);
+                        __builtin_amdgcn_sched_barrier(0);     // row by row (see the classification below): the row's values end here
+                    }
+                };
+                load_q(0);
+                load_q(1);
+                gather_q(0);
+                load_q(2);
+                gather_q(1);
+                finish_q(0);
+                load_q(3);
+                gather_q(2);
+                finish_q(1);
+                gather_q(3);
+                finish_q(2);
+                finish_q(3);
+                proof_bad |= below;
+                // (two words from here on: seen through, `raised & bit` is the row's own comparison again, and all 64 stay live)
+                asm volatile("" : "+v"(raised[0]), "+v"(raised[1]));
+                // (F comes back from the wave's LDS scratch under new names: elevations, slots, levels and depths all end here -- as one
+                // live range from the loads to the classification's last row the register allocator spilled a hundred of them)
+                lds_wait();
+                __builtin_amdgcn_sched_barrier(0);
+                lds_get_rows<0, WN>(scr_b + 4u * lane, sl);
+                lds_wait();
+#pragma unroll
+                for (int r = 0; r < WN; ++r) {
+                    asm volatile("" : "+v"(sl[r]));
+                    f[r] = __uint_as_float(sl[r]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
             float upl = PINF, up = PINF, upr = PINF, cul = fleft(f[0]), cur = fright(f[0]);
             float h_up = PINF, h_cu = fminf(fminf(cul, f[0]), cur);      // minimum of a row's three cells around this column: row r - 1, row r
@@ -684,6 +794,8 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
                 const bool irregular = flat & !regular & !nan;     // a level without integer weights: left to the float64 relaxation
                 nirr += irregular ? 1u : 0u;
                 nfatal += nan ? 1u : 0u;                            // NaN cells: not for this path at all
+                // the flood's proof (check.hip): a raised cell has no neighbour below its level (a NaN neighbour is no minimum: +inf)
+                if constexpr (HANDOVER) proof_bad |= (cell & lower) ? raised[r >> 5] & (1u << (r & 31)) : 0u;
                 const uint32_t w = regular ? (adj | (e << 8)) : (irregular ? M_IRR : M_NOFLAT);
                 lake_any |= w;
                 ni[r] = w;
@@ -747,6 +859,9 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
             for (int o = 32; o >= 1; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
             if ((tot & 0xffffu) && lane == 0) atomicAdd(&a.counters[C_IRREGULAR], (unsigned long long)(tot & 0xffffu));
             if ((tot >> 16) && lane == 0) atomicAdd(&a.counters[C_FATAL], (unsigned long long)(tot >> 16));
+        }
+        if constexpr (HANDOVER) {
+            if (__any(proof_bad != 0u) && lane == 0) a.counters[C_PROOF] = 1ull;      // (a plain store of the same value)
         }
         // the raster border cells inside this window are sources: their distance 0 is read by every later visit (and by
         // ng_assemble), so somebody has to write it
@@ -1017,7 +1132,7 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
 // waves only fits a CU from which half of the labelling's workgroups have gone -- and the dispatcher refills every gap with the
 // labelling's small ones first, because THEY fit (no-flats stage 6.8 -> 9.5 ms in round 3 and again in round 4) --, a single wave with
 // 18.7 KB fits as soon as one of them leaves.
-template <bool FIRST, int WPB = 4>
+template <bool FIRST, int WPB = 4, bool HANDOVER = false>
 __device__ __forceinline__ void round_body(const GeoArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -1039,7 +1154,7 @@ __device__ __forceinline__ void round_body(const GeoArgs &a)
     unsigned visits = 0, cycles = 0;
     for (int i = gw; i < n; i += nwaves) {
         const int t = FIRST ? i : __builtin_amdgcn_readfirstlane(i == gw ? t_first : a.list[i]);
-        visit<FIRST>(a, t, tab_l, scr_b, lane, visits, cycles);
+        visit<FIRST, HANDOVER>(a, t, tab_l, scr_b, lane, visits, cycles);
     }
     if (lane == 0 && visits) {
         unsigned long long *st = a.counters + C_STATS + 2 * (gw & 63);
@@ -1050,6 +1165,8 @@ __device__ __forceinline__ void round_body(const GeoArgs &a)
 __global__ __launch_bounds__(256, 2) void ng_first_kernel(GeoArgs a) { round_body<true>(a); }
 __global__ __launch_bounds__(256, 2) void ng_round_kernel(GeoArgs a) { round_body<false>(a); }
 __global__ __launch_bounds__(64, 2) void ng_round_w1_kernel(GeoArgs a) { round_body<false, 1>(a); }
+// the first visit of a request that holds the plain fill as well: the flood's last pass and its proof ride on the classification
+__global__ __launch_bounds__(256, 2) void ng_handover_kernel(GeoArgs a) { round_body<true, 4, true>(a); }
 
 // ---- the marks of one round -> the tile list of the next (clears the marks) --------------------------------------------------
 // The mark bytes are read as 64-bit words (the array is padded to a multiple of 8 bytes), one word per thread; the order of the
@@ -1417,10 +1534,20 @@ int GeoRun::launch_rounds(hipStream_t s, int nb)
     a.H = H; a.W = W; a.ntr = m.ntr; a.ntc = m.ntc; a.nt = (int)m.nt; a.F = filled; a.d = dist; a.tab = m.d_tab; a.counters = m.d_cnt;
     a.blk = m.d_blk; a.hdr = m.d_hdr; a.mark = m.d_mark; a.list = m.d_list; a.fixed_top = fixed_top; a.fixed_bot = fixed_bot;
     a.append = 0; a.round_next = 0; a.amark = m.d_amark; a.list_next = nullptr; a.count_next = nullptr;
+    a.ho_dem = nullptr; a.ho_bslot = nullptr; a.ho_tabV = nullptr; a.ho_F = nullptr; a.ho_depths = nullptr;
     const unsigned grid = (unsigned)std::min<int64_t>((m.nt + 3) / 4, 512);
     for (int k = 0; k < nb; ++k, ++m.round) {
         a.maxcyc = m.maxcyc;
         a.count = m.d_any + m.round;     // tiles of this round (round 0: every tile)
+        if (!m.round && handover && handover->pending) {
+            // the flood's last pass and its proof ride on the classification (the flood cut the raster into the same tiles: begin() checked)
+            a.ho_dem = handover->dem; a.ho_bslot = handover->bslot; a.ho_tabV = handover->tabV;
+            a.ho_F = handover->filled; a.ho_depths = handover->depths;
+            hipLaunchKernelGGL(ng_handover_kernel, dim3(grid), dim3(256), m.lds, s, a);
+            handover->queued = true;
+            (void)hipEventRecord(m.span.back().first, s);
+            continue;
+        }
         if (!m.round) {
             hipLaunchKernelGGL(ng_first_kernel, dim3(grid), dim3(256), m.lds, s, a);
             (void)hipEventRecord(m.span.back().first, s);      // (the span counts the rounds after the classification)
@@ -1507,16 +1634,35 @@ int GeoRun::begin(hipStream_t s, bool *applicable, bool *active)
         if (dev < 0 || dev >= 64 || !attr_done[dev]) {
             MH_HIP(hipFuncSetAttribute((const void *)ng_round_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds));
             MH_HIP(hipFuncSetAttribute((const void *)ng_first_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds));
+            MH_HIP(hipFuncSetAttribute((const void *)ng_handover_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds));
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
     m.round = 0;
     m.last_count = 0xffffffffu;
     m.used = 0;
+    // a hand-over from a flood that cut the raster differently (or for another raster) is not taken: the flood's own last pass, late
+    if (handover && handover->pending &&
+        !(handover->ntr == m.ntr && handover->ntc == m.ntc && handover->H == H && handover->W == W && handover->filled == filled && handover->dem == dem &&
+          !fixed_top && !fixed_bot))
+        MH_TRY(fill_handover_complete(handover, s));
+    const bool took = handover && handover->pending;
     MH_TRY(launch_rounds(s, 1));
-    unsigned long long h_c[4] = {0, 0, 0, 0};
+    unsigned long long h_c[5] = {0, 0, 0, 0, 0};
     MH_HIP(hipMemcpyAsync(h_c, m.d_cnt, sizeof(h_c), hipMemcpyDeviceToHost, s));
     MH_HIP(stream_sync(s));   // (the table upload is complete as well: `tab` may go)
+    if (took) {               // ... and so is the last reader of the flood's workspace; its proof came with the counters
+        // (MHIP_HO_RECHECK: test hook -- the visit's proof is taken as failed, tests/test_gpu_fill_handover.py)
+        if (h_c[C_PROOF] != 0 || dev_env("MHIP_HO_RECHECK") != nullptr) {
+            // The proof failed in this visit: `filled` may be an upper bound only, the classification made from it is void.  The
+            // flood's workspace is still here: the caller lets the flood's own last pass write and prove the raster
+            // (fill_handover_complete: it repairs a surface that fails there too) and classifies again from the raster.
+            handover->suspect = true;
+            m.ws.release();
+            return MHIP_OK;
+        }
+        handover->release();
+    }
     m.used = 1;
     m.irregular = h_c[C_IRREGULAR];
     if (h_c[C_FATAL] || (m.irregular && !allow_partial)) {
@@ -1665,9 +1811,10 @@ int noflat_verify_dev(const float *d_dem, const double *d_out, int64_t H, int64_
 // which hold an upper bound (F + seed_add): the caller relaxes those in float64 and verifies.  MHIP_ELIMIT: not applicable to
 // this raster (NaN cells, epsilons without weights, a cell the verification rejects): the caller runs the float64 relaxation.
 int fill_noflat_geodesic_dev(const float *d_dem, const float *d_filled, double *d_out, int64_t H, int64_t W, double sh, double dg, double seed_add,
-                             hipStream_t s, FillStats *st, bool *partial, StageHook *tail_hook, D8Sink *d8)
+                             hipStream_t s, FillStats *st, bool *partial, StageHook *tail_hook, D8Sink *d8, FillHandover *ho)
 {
     GeoRun g;
+    g.handover = ho;
     g.tail_hook = tail_hook;
     if (d8) { g.d8_out = d8->flowdir; g.d8_nodir = d8->nodir; d8->done = false; }
     g.dem = d_dem; g.filled = d_filled; g.out = d_out; g.H = H; g.W = W; g.sh = sh; g.dg = dg;
@@ -1675,6 +1822,18 @@ int fill_noflat_geodesic_dev(const float *d_dem, const float *d_filled, double *
     g.seed_add = seed_add;
     bool applicable = false, active = false, ok = false;
     MH_TRY(g.begin(s, &applicable, &active));
+    // not taken (the transform launched nothing), or the proof failed in the fused visit: the flood's own last pass and proof --
+    // and, where that fails as well, the repair -- then, in the second case, the classification again, from the raster
+    if (ho && ho->pending) {
+        const bool again = ho->suspect;
+        MH_TRY(fill_handover_complete(ho, s));
+        if (again) {
+            g.handover = nullptr;
+            MH_TRY(g.begin(s, &applicable, &active));
+        }
+    }
+    // (the filled surface and the depths are final behind this point of the stream: a label branch that starts "with the no-flats fill")
+    if (tail_hook) tail_hook->fire_at(StageHook::FIRST_VISIT, s);
     if (!applicable) {
         if (st) st->geo_reject = 1;
         return MHIP_ELIMIT;

@@ -97,12 +97,6 @@ struct PfArgs {
 #define PF_STAMP(i)
 #endif
 
-__device__ __forceinline__ uint32_t dem_key(float v)
-{
-    if (v != v) return f32_key(__builtin_inff());   // a NaN cell never wins a comparison (_fill.pyx:22): like +inf
-    return f32_key(v + 0.0f);                        // -0.0 -> +0.0: the two compare equal in the reference
-}
-
 __device__ __forceinline__ int ring_pos(int wr, int wc)
 {
     if (wr == 0) return wc;
@@ -1623,6 +1617,14 @@ __global__ void pf_fill_f32_kernel(float *p, int64_t n, float v)
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
 }
+// test hook of the deferred last pass (MHIP_PF_CORRUPT with a hand-over: there is no raster to poke yet): the final level of the
+// basin of interior cell (r, c) is raised to `key` -- one thread
+__global__ void pf_raise_level_kernel(PfArgs a, int64_t r, int64_t c, uint32_t key)
+{
+    const int tile = (int)((r - 1) / TI) * a.ntc + (int)((c - 1) / TI);
+    const size_t i = (size_t)tile * NBMAX + min((int)a.bslot[r * a.W + c], NBMAX - 1);
+    a.tabV[i] = max(a.tabV[i], key);
+}
 
 }  // namespace
 
@@ -1983,33 +1985,20 @@ int PfRun::batch(hipStream_t s)
 }
 
 // the final level of every basin, then the raster (a band's halo rows stay as the neighbour left them)
-int PfRun::finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated)
+int PfRun::finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated, FillHandover *ho)
 {
     Impl &m = *impl;
     hipLaunchKernelGGL(pf_final_kernel, dim3((unsigned)m.ntiles), dim3(256), 0, s, m.a);
-    // The run-time proof (check.hip): K3 is a worklist schedule (marks + list appends wake neighbouring blocks); a wake lost there, or
-    // a fault in any of K1..K4, leaves a surface that is not a fixed point.  Rasters whose width is a multiple of 256 take the fused
-    // kernel (the check rides on the rows K4 computes); every other raster K4 + one streaming pass over dem + filled (8 B per cell).
-    unsigned int h_viol = 0;
-    const bool poke = violated && dev_env("MHIP_PF_CORRUPT") != nullptr && H > 8 && W > 8;    // test hook: one interior cell raised after the flood
-    const bool fused = violated && !poke && W % 256 == 0;
-    if (violated) MH_HIP(hipMemsetAsync(m.a.flags + 1, 0, 4, s));
-    if (fused) {
-        const unsigned nbx = (unsigned)(W / 1024 + (W % 1024 ? 1 : 0)), nby = (unsigned)cdiv(H, PF_RPW);
-        hipLaunchKernelGGL(pf_apply_check_kernel, dim3(nbx * nby), dim3(256), 0, s, m.a, out, d_depths, nbx, m.a.flags + 1);
+    m.launches += 1;
+    // The deferred form: K4 and the proof are left to the first visit of the no-flats fill (noflat_geo.hip: ng_handover_kernel),
+    // which cuts the raster into the same 62 x 62 tiles and evaluates the same stencil on F anyway.  The workspace stays.
+    const bool defer = ho && violated && !fixed_top && !fixed_bot;
+    if (defer) {
+        if (dev_env("MHIP_PF_CORRUPT") != nullptr && H > 8 && W > 8)      // (test hook: see pf_raise_level_kernel)
+            hipLaunchKernelGGL(pf_raise_level_kernel, dim3(1), dim3(1), 0, s, m.a, H / 2, W / 2, f32_key(3.0e38f));
+        MH_HIP(hipGetLastError());
     } else {
-        const int64_t groups = ((W + 3) / 4) * H;
-        hipLaunchKernelGGL(pf_apply_kernel, dim3((unsigned)cdiv(groups, 256)), dim3(256), 0, s, m.a, out, d_depths);
-    }
-    MH_HIP(hipGetLastError());
-    m.launches += 2;
-    if (violated) {
-        if (poke) hipLaunchKernelGGL(pf_fill_f32_kernel, dim3(1), dim3(1), 0, s, out + (H / 2) * W + W / 2, (int64_t)1, 3.0e38f);
-        if (!fused) {
-            MH_TRY(fill_check_f32_dev(dem, out, H, W, fixed_top, fixed_bot, s, m.a.flags + 1));
-            m.launches += 1;
-        }
-        MH_HIP(hipMemcpyAsync(&h_viol, m.a.flags + 1, 4, hipMemcpyDeviceToHost, s));
+        MH_TRY(finish_late(s, d_depths, violated));
     }
 #ifdef PF_PROFILE
     {
@@ -2035,6 +2024,8 @@ int PfRun::finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated)
                 (double)h_prof[15] / (double)m.ntiles, (double)h_prof[16] / (double)m.ntiles, (double)h_prof[17] / (double)m.ntiles, (double)h_prof[18] / (double)m.ntiles);
     }
 #endif
+    unsigned int h_viol = 0;
+    if (violated && !defer) MH_HIP(hipMemcpyAsync(&h_viol, m.a.flags + 1, 4, hipMemcpyDeviceToHost, s));
     if (st) {
         unsigned long long h_vis = 0;
         if (m.rounds_ran) MH_HIP(hipMemcpyAsync(&h_vis, m.visits, 8, hipMemcpyDeviceToHost, s));      // (the queue solve's visits came with its header)
@@ -2057,7 +2048,49 @@ int PfRun::finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated)
         MH_HIP(stream_sync(s));   // the workspace goes back to the pool now
     }
     if (violated) *violated = h_viol != 0;
+    if (defer) {
+        ho->dem = dem; ho->filled = out; ho->depths = d_depths; ho->H = H; ho->W = W;
+        ho->bslot = m.a.bslot; ho->tabV = m.a.tabV; ho->ntr = m.a.ntr; ho->ntc = m.a.ntc;
+        ho->pending = true;
+        return MHIP_OK;
+    }
     m.ws.release();
+    return MHIP_OK;
+}
+
+int PfRun::proof_flag(hipStream_t s, unsigned int *h_flag)
+{
+    MH_HIP(hipMemcpyAsync(h_flag, impl->a.flags + 1, 4, hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
+// K4 and the proof; the flag stays on the device (finish reads it with the statistics, a late caller on its own)
+int PfRun::finish_late(hipStream_t s, float *d_depths, bool *violated)
+{
+    Impl &m = *impl;
+    // The run-time proof (check.hip): K3 is a worklist schedule (marks + list appends wake neighbouring blocks); a wake lost there, or
+    // a fault in any of K1..K4, leaves a surface that is not a fixed point.  Rasters whose width is a multiple of 256 take the fused
+    // kernel (the check rides on the rows K4 computes); every other raster K4 + one streaming pass over dem + filled (8 B per cell).
+    const bool poke = violated && dev_env("MHIP_PF_CORRUPT") != nullptr && H > 8 && W > 8;    // test hook: one interior cell raised after the flood
+    const bool fused = violated && !poke && W % 256 == 0;
+    if (violated) MH_HIP(hipMemsetAsync(m.a.flags + 1, 0, 4, s));
+    if (fused) {
+        const unsigned nbx = (unsigned)(W / 1024 + (W % 1024 ? 1 : 0)), nby = (unsigned)cdiv(H, PF_RPW);
+        hipLaunchKernelGGL(pf_apply_check_kernel, dim3(nbx * nby), dim3(256), 0, s, m.a, out, d_depths, nbx, m.a.flags + 1);
+    } else {
+        const int64_t groups = ((W + 3) / 4) * H;
+        hipLaunchKernelGGL(pf_apply_kernel, dim3((unsigned)cdiv(groups, 256)), dim3(256), 0, s, m.a, out, d_depths);
+    }
+    MH_HIP(hipGetLastError());
+    m.launches += 1;
+    if (violated) {
+        if (poke) hipLaunchKernelGGL(pf_fill_f32_kernel, dim3(1), dim3(1), 0, s, out + (H / 2) * W + W / 2, (int64_t)1, 3.0e38f);
+        if (!fused) {
+            MH_TRY(fill_check_f32_dev(dem, out, H, W, fixed_top, fixed_bot, s, m.a.flags + 1));
+            m.launches += 1;
+        }
+    }
     return MHIP_OK;
 }
 
@@ -2065,14 +2098,47 @@ int PfRun::finish(hipStream_t s, float *d_depths, FillStats *st, bool *violated)
 // Exact tiled priority-flood on one raster.  Returns MHIP_ELIMIT (without touching d_out) when a per-tile capacity was
 // exceeded: the caller then runs the iterative schedule.
 int fill_plain_pflood_dev(const float *d_dem, float *d_out, float *d_depths, int64_t H, int64_t W, hipStream_t s, FillStats *st, bool *violated,
-                          uint32_t *overflow)
+                          uint32_t *overflow, FillHandover *ho)
 {
+    if (ho && violated) {      // the run outlives this call: its workspace is read by the no-flats fill's first visit
+        ho->release();
+        ho->run = new PfRun;
+        PfRun &f = *ho->run;
+        f.dem = d_dem; f.out = d_out; f.H = H; f.W = W;
+        int rc = f.begin(s);
+        if (overflow) *overflow = f.overflow;
+        if (rc == MHIP_OK) rc = f.finish(s, d_depths, st, violated, ho);
+        if (rc != MHIP_OK || !ho->pending) ho->release();
+        return rc;
+    }
     PfRun f;
     f.dem = d_dem; f.out = d_out; f.H = H; f.W = W;
     const int rc = f.begin(s);
     if (overflow) *overflow = f.overflow;
     if (rc != MHIP_OK) return rc;
     return f.finish(s, d_depths, st, violated);
+}
+
+FillHandover::~FillHandover() { release(); }
+void FillHandover::release()
+{
+    delete run;
+    run = nullptr;
+    pending = false;
+}
+
+// the hand-over nobody took (the transform does not run on this raster): the flood's own last pass and proof, late
+int fill_handover_complete(FillHandover *ho, hipStream_t s)
+{
+    if (!ho || !ho->pending || !ho->run) return MHIP_OK;
+    bool violated = false;
+    MH_TRY(ho->run->finish_late(s, ho->depths, &violated));
+    unsigned int h_viol = 0;
+    MH_TRY(ho->run->proof_flag(s, &h_viol));      // (synchronises the stream)
+    ho->release();
+    ho->violated = h_viol != 0;
+    if (ho->violated) MH_TRY(fill_handover_repair(ho, s));
+    return MHIP_OK;
 }
 
 }  // namespace mh
