@@ -492,7 +492,10 @@ int mhip_ctx_kernel_ms(mhip_ctx *ctx, const char *kernel, float *ms_total, int32
  * "noflat_algorithm" (2 integer geodesic transform, 3 + float64 relaxation of irregular flats, 0 float64 relaxation; why a
  * transform was handed back: "noflat_reject*"), "pour_algorithm" (1 keys out of the accumulation's final pass, 0 a pass over
  * values + labels), "accum_algorithm" (row bands: 1 the second pass as a delta over the boundary pass's graph, 0 a full pass),
- * "flowdir_computed" (1 the resident flow directions are the library's own D8, 0 they were uploaded or there are none) */
+ * "flowdir_computed" (1 the resident flow directions are the library's own D8, 0 they were uploaded or there are none),
+ * "noflat_pending" (1 MHIP_R_NOFLAT is resident but not written yet: a request that held NOFLAT and FLOWDIR on an undivided context
+ * took its directions from the surface in registers and left the store to whoever reads the raster first -- a download, a stage,
+ * a band call: that call writes it from MHIP_R_FILLED and MHIP_R_NGDIST, which stays resident for it, 4 bytes a cell) */
 int mhip_ctx_get_i64(mhip_ctx *ctx, const char *key, int64_t *value);
 int mhip_ctx_get_f64(mhip_ctx *ctx, const char *key, double *value);  /* "short", "diag" */
 /* label filter between MHIP_STAGE_LABEL and MHIP_STAGE_WATERSHED (reference bluespots.py:165-172):

@@ -831,8 +831,47 @@ int accum_band_delta_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t 
     return MHIP_OK;
 }
 
+namespace {
+// the node buffer of one accumulation: where its arrays start (exit_map: the two arrays of a row band's boundary pass as well)
+struct NodeLayout {
+    size_t o_gstate, o_inflow, o_arrived, o_next, o_dst, o_exit, o_flags, o_halo, o_bexit, bytes;
+    NodeLayout(int64_t nnodes, int64_t W, bool exit_map)
+    {
+        auto align = [](size_t x) { return (x + 255) & ~size_t(255); };
+        o_gstate = 0; o_inflow = align(o_gstate + 8 * (size_t)nnodes); o_arrived = align(o_inflow + 8 * (size_t)nnodes);
+        o_next = align(o_arrived + 4 * (size_t)nnodes); o_dst = align(o_next + 4 * (size_t)nnodes);
+        o_exit = align(o_dst + 4 * (size_t)nnodes); o_flags = align(o_exit + 2 * (size_t)nnodes);
+        o_halo = align(o_flags + (size_t)nnodes);
+        o_bexit = align(o_halo + (exit_map ? 8 * (size_t)W : 0));
+        bytes = o_bexit + (exit_map ? 4 * (size_t)nnodes : 0);
+    }
+};
+inline int64_t accum_nodes(int64_t H, int64_t W) { return cdiv(H, AT) * cdiv(W, AT) * NODE_STRIDE; }
+}  // namespace
+
+AccumPrep::~AccumPrep()
+{
+    if (valid && ready) (void)hipEventSynchronize(ready);      // (nobody took the buffer: its clears end before it goes back to the pool)
+}
+
+// The set-up of accum_dev that does not depend on the flow directions -- the node buffer and the clear of inflow | arrived -- queued
+// on `s` ahead of the call, with `ready` recorded behind it.  A raster accum_dev would refuse prepares nothing.
+int accum_prepare_dev(AccumPrep *prep, int64_t H, int64_t W, hipStream_t s, hipEvent_t ready)
+{
+    prep->valid = false;
+    const int64_t nnodes = accum_nodes(H, W);
+    if (nnodes >= (int64_t)INT32_MAX || H * W >= (1ll << 37)) return MHIP_OK;
+    const NodeLayout L(nnodes, W, false);
+    MH_TRY(prep->nodes.alloc(L.bytes));
+    MH_HIP(hipMemsetAsync(prep->nodes.as<char>() + L.o_inflow, 0, L.o_next - L.o_inflow, s));
+    MH_HIP(hipEventRecord(ready, s));
+    prep->ready = ready; prep->H = H; prep->W = W;
+    prep->valid = true;
+    return MHIP_OK;
+}
+
 int accum_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t W, hipStream_t s, int fixed_top, int fixed_bot, int halo_zero,
-              int32_t *d_exit_map, PourLink *pour, AccumKeep *keep)
+              int32_t *d_exit_map, PourLink *pour, AccumKeep *keep, AccumPrep *prep)
 {
     const int ntr = (int)cdiv(H, AT), ntc = (int)cdiv(W, AT);
     const int64_t ntiles = (int64_t)ntr * ntc, nnodes = ntiles * NODE_STRIDE;
@@ -841,13 +880,18 @@ int accum_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t W, hipStrea
         return MHIP_ELIMIT;
     }
     DevBuf buf;
-    auto align = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t o_gstate = 0, o_inflow = align(o_gstate + 8 * (size_t)nnodes), o_arrived = align(o_inflow + 8 * (size_t)nnodes);
-    const size_t o_next = align(o_arrived + 4 * (size_t)nnodes), o_dst = align(o_next + 4 * (size_t)nnodes);
-    const size_t o_exit = align(o_dst + 4 * (size_t)nnodes), o_flags = align(o_exit + 2 * (size_t)nnodes);
-    const size_t o_halo = align(o_flags + (size_t)nnodes);
-    const size_t o_bexit = align(o_halo + (d_exit_map ? 8 * (size_t)W : 0));
-    MH_TRY(buf.alloc(o_bexit + (d_exit_map ? 4 * (size_t)nnodes : 0)));
+    const NodeLayout L(nnodes, W, d_exit_map != nullptr);
+    const size_t o_gstate = L.o_gstate, o_inflow = L.o_inflow, o_arrived = L.o_arrived, o_next = L.o_next, o_dst = L.o_dst, o_exit = L.o_exit,
+                 o_flags = L.o_flags, o_halo = L.o_halo, o_bexit = L.o_bexit;
+    // a buffer prepared for this raster (accum_prepare_dev): taken over, its clears are behind `ready`
+    const bool prepared = prep && prep->valid && prep->H == H && prep->W == W && !d_exit_map && !keep;
+    if (prepared) {
+        buf.p = prep->nodes.p; buf.bytes = prep->nodes.bytes;
+        prep->nodes.p = nullptr; prep->nodes.bytes = 0;
+        prep->valid = false;
+        MH_HIP(hipStreamWaitEvent(s, prep->ready, 0));
+    } else
+        MH_TRY(buf.alloc(L.bytes));
     char *b = buf.as<char>();
     Nodes nd;
     nd.gstate = reinterpret_cast<uint64_t *>(b + o_gstate);
@@ -860,7 +904,7 @@ int accum_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t W, hipStrea
     nd.halo_first = d_exit_map ? reinterpret_cast<int32_t *>(b + o_halo) : nullptr;
     nd.bexit = d_exit_map ? reinterpret_cast<int32_t *>(b + o_bexit) : nullptr;
     if (d_exit_map) MH_HIP(hipMemsetAsync(nd.halo_first, 0xff, 8 * (size_t)W, s));
-    MH_HIP(hipMemsetAsync(nd.inflow, 0, o_next - o_inflow, s));      // inflow | arrived: phase 1 pushes the external in-degrees into `arrived`
+    if (!prepared) MH_HIP(hipMemsetAsync(nd.inflow, 0, o_next - o_inflow, s));      // inflow | arrived: phase 1 pushes the external in-degrees into `arrived`
     const unsigned gn = (unsigned)cdiv(nnodes, 256);
     // the local sums of phase 1 fit 32 bits unless halo cells bring the neighbouring band's flux in (the final pass of a row band)
     // the final pass as walks from the entry cells (accum_final_walk_kernel) wherever the sums fit 32 bits and no halo row is a source

@@ -317,6 +317,8 @@ struct GeoRun {
     uint8_t *d8_out = nullptr;                        // optional: end() also writes the flow directions of the surface (one context, no halo rows)
     unsigned int *d8_nodir = nullptr;                 // ... and sets this word when an interior cell has none
     bool d8_done = false;                             // set by end(): d8_out holds the directions of the verified surface
+    bool defer_out = false;                           // with d8_out and an external `dist`: end() may leave `out` unwritten ...
+    bool out_deferred = false;                        // ... set by end(): it did -- `out` is noflat_assemble_dev(filled, dist) whenever somebody wants it
     FillHandover *handover = nullptr;                 // pending: begin() computes, writes and proves `filled` (and the depths) in its first visit
     struct Impl;
     Impl *impl;
@@ -337,7 +339,13 @@ struct D8Sink {
     uint8_t *flowdir = nullptr;
     unsigned int *nodir = nullptr;     // zeroed by the caller; set when an interior cell has no downslope neighbour
     bool done = false;
+    // The caller reads the surface from nowhere but these directions (a chain request): with `dist`, a raster of its own
+    // for the distances, and `defer`, a finishing pass that is the last word on the surface does not store it -- `deferred`: d_out is
+    // unwritten, and noflat_assemble_dev(d_filled, dist, d_out) writes it at any later time.  Every other outcome stores as ever.
+    uint32_t *dist = nullptr;
+    bool defer = false, deferred = false;
 };
+int noflat_assemble_dev(const float *d_filled, const uint32_t *d_dist, double *d_out, int64_t n, double seed_add, hipStream_t s);
 int fill_noflat_geodesic_dev(const float *d_dem, const float *d_filled, double *d_out, int64_t H, int64_t W, double sh, double dg, double seed_add,
                              hipStream_t s, FillStats *st, bool *partial, StageHook *tail_hook = nullptr, D8Sink *d8 = nullptr, FillHandover *ho = nullptr);
 int noflat_verify_dev(const float *d_dem, const double *d_out, int64_t H, int64_t W, double sh, double dg, hipStream_t s, bool *ok, int fixed_top = 0,
@@ -404,8 +412,21 @@ struct AccumKeep {               // the perimeter graph of a row band's boundary
     int fixed_top = 0, fixed_bot = 0;
     bool valid = false;
 };
+// accum_dev's node buffer, allocated and cleared ahead of the call on a stream of the caller's choice: neither depends on the flow
+// directions, and a request that computes them first has time for both (mhip_ctx_run).  A buffer nobody takes goes back to the pool
+// when the object goes, behind its clears.
+struct AccumPrep {
+    DevBuf nodes;
+    int64_t H = 0, W = 0;
+    hipEvent_t ready = nullptr;      // (the caller's) recorded behind the clears
+    bool valid = false;
+    ~AccumPrep();
+};
+int accum_prepare_dev(AccumPrep *prep, int64_t H, int64_t W, hipStream_t s, hipEvent_t ready);
+// prep (optional): a buffer of accum_prepare_dev for this raster is taken over; without one, for a row band's passes (exit map,
+// keep) or another raster the call allocates and clears its own, as ever
 int accum_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t W, hipStream_t s, int fixed_top = 0, int fixed_bot = 0, int halo_zero = 0,
-              int32_t *d_exit_map = nullptr, PourLink *pour = nullptr, AccumKeep *keep = nullptr);
+              int32_t *d_exit_map = nullptr, PourLink *pour = nullptr, AccumKeep *keep = nullptr, AccumPrep *prep = nullptr);
 int accum_band_delta_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t W, hipStream_t s, int fixed_top, int fixed_bot, AccumKeep *keep, bool *done);
 // ccl.hip   (d_tmp: H*W int32 scratch)
 // stats_out: the labelling's last pass also reduces label_stats(d_data, labels) into *stats_out (allocated here: nlabels + 1 records)

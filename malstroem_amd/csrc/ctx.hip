@@ -30,6 +30,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
 {
     switch (which) {
     case MHIP_R_DEM:    // a new DEM invalidates everything derived from the previous one
+        c->noflat_pending = false;      // (a surface nobody has asked for goes with have[NOFLAT])
         for (int k = 0; k < MHIP_R_COUNT_; ++k) {
             if (k == MHIP_R_DEM) continue;
             c->have[k] = false;
@@ -81,6 +82,20 @@ int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, 
     const bool up = kind == hipMemcpyHostToDevice;
     MH_HIP(hipMemcpyAsync(up ? (void *)dev : host, up ? host : (void *)dev, rowb * (size_t)nrows, kind, cs(c)));
     MH_HIP(stream_sync(cs(c)));      // (an upload's caller reuses its window buffer)
+    return MHIP_OK;
+}
+
+int ctx_noflat(mhip_ctx *c, double **g)
+{
+    if (c->noflat_pending) {
+        MH_HIP(hipSetDevice(c->device));
+        // (no cell of an accepted surface takes the seed: the finishing pass counted none)
+        MH_TRY(noflat_assemble_dev(c->r[MHIP_R_FILLED].as<float>(), c->r[MHIP_R_NGDIST].as<uint32_t>(), c->r[MHIP_R_NOFLAT].as<double>(), c->H * c->W, 0.0,
+                                   c->stream));
+        c->noflat_pending = false;
+        if (cs(c) != c->stream) MH_HIP(stream_sync(c->stream));
+    }
+    if (g) *g = c->r[MHIP_R_NOFLAT].as<double>();
     return MHIP_OK;
 }
 
@@ -211,7 +226,7 @@ int mhip_ctx_destroy(mhip_ctx *c)
             (void)hipStreamDestroy(st);
         }
     }
-    for (hipEvent_t e : {c->ev_fork, c->ev_flowdir, c->ev_join, c->ev_label, c->ev_tail, c->ev_cand})
+    for (hipEvent_t e : {c->ev_fork, c->ev_flowdir, c->ev_join, c->ev_label, c->ev_tail, c->ev_cand, c->ev_prep})
         if (e) (void)hipEventDestroy(e);
     delete c->geo;
     delete c->pf;
@@ -268,6 +283,7 @@ int mhip_ctx_upload_rows(mhip_ctx *c, int which, int64_t row0, int64_t nrows, co
            "ctx_upload_rows(ctx, which, row0, nrows, host)");
     MH_HIP(hipSetDevice(c->device));
     MH_TRY(ctx_raster(c, which));
+    MH_TRY(ctx_settle(c, which, /*write=*/true));     // (a foreign FILLED leaves the surface of the old one behind, as ever)
     ctx_wrote(c, which, /*uploaded=*/true);
     c->have[which] = false;
     MH_TRY(ctx_copy_rows(c, c->r[which].p, raster_elem(which), row0, nrows, const_cast<void *>(host), hipMemcpyHostToDevice));
@@ -283,6 +299,7 @@ int mhip_ctx_download_rows(mhip_ctx *c, int which, int64_t row0, int64_t nrows, 
     MH_ARG(c && host && which >= 0 && which < MHIP_R_COUNT_ && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned,
            "ctx_download_rows(ctx, which, row0, nrows, host)");
     MH_ARG(c->have[which], "raster has not been computed or uploaded");
+    MH_TRY(ctx_settle(c, which, /*write=*/false));
     return ctx_copy_rows(c, c->r[which].p, raster_elem(which), row0, nrows, host, hipMemcpyDeviceToHost);
 }
 
@@ -335,6 +352,8 @@ int mhip_ctx_kernel_ms(mhip_ctx *c, const char *kernel, float *ms_total, int32_t
         // (a pair of events around a single 0.43 ms launch adds ~30 us of bracket to it); the resident surface and directions
         MH_ARG(c->have[MHIP_R_NOFLAT] && !c->ht && !c->hb, "d8_steady needs the no-flats surface on an undivided context");
         MH_HIP(hipSetDevice(c->device));
+        double *g = nullptr;
+        MH_TRY(ctx_noflat(c, &g));      // (in front of the events: the launches below are the stencil and nothing else)
         MH_TRY(ctx_raster(c, MHIP_R_FLOWDIR));
         MH_TRY(c->nodir_cnt.alloc(4));
         constexpr int REPS = 16;
@@ -345,8 +364,7 @@ int mhip_ctx_kernel_ms(mhip_ctx *c, const char *kernel, float *ms_total, int32_t
         MH_HIP(hipMemsetAsync(c->nodir_cnt.p, 0, 4, s));
         for (int i = 0; i < REPS + 2; ++i) {
             if (i == 2) MH_HIP(hipEventRecord(t->a, s));      // (two untimed launches first)
-            MH_TRY(d8_dev(c->r[MHIP_R_NOFLAT].as<double>(), c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->H, c->W, 1, s, 0, c->H_global,
-                          c->nodir_cnt.as<unsigned int>()));
+            MH_TRY(d8_dev(g, c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->H, c->W, 1, s, 0, c->H_global, c->nodir_cnt.as<unsigned int>()));
         }
         MH_HIP(hipEventRecord(t->b, s));
         MH_HIP(hipEventSynchronize(t->b));
@@ -405,6 +423,7 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "flowdir_computed") *value = (c->have[MHIP_R_FLOWDIR] && c->flowdir_own) ? 1 : 0;   // 1 the library's D8 wrote FLOWDIR, 0 it was uploaded
     else if (k == "pour_algorithm") *value = c->pour_algorithm;   // 0 a pass over values + labels (label_ops.hip), 1 keys out of the accumulation's final pass (PourLink)
     else if (k == "noflat_algorithm") *value = c->noflat_st.algorithm;   // 0 float64 relaxation (fill.hip), 2 integer geodesic transform (noflat_geo.hip)
+    else if (k == "noflat_pending") *value = c->noflat_pending ? 1 : 0;   // 1 NOFLAT is resident but not written yet: the next reader's call writes it (ctx_noflat)
     else if (k == "noflat_visits") *value = c->noflat_st.visits;
     else if (k == "noflat_reject") *value = c->noflat_st.geo_reject;            // diagnostics: FillStats::geo_reject and its counts
     else if (k == "noflat_reject_irregular") *value = c->noflat_st.geo_irregular;

@@ -89,6 +89,10 @@ struct mhip_ctx {
     hipStream_t stream = nullptr;
     mh::DevBuf r[MHIP_R_COUNT_];
     bool have[MHIP_R_COUNT_] = {};
+    // NOFLAT is resident (have[] says so) but not written: it is noflat_assemble_dev(FILLED, NGDIST), the surface the finishing pass
+    // of the last chain request checked and did not store (ctx_run.hip: stage_noflat).  ctx_noflat() is the only
+    // way to the raster's memory
+    bool noflat_pending = false;
     mh::DevBuf tmp_i32;     // CCL parent scratch
     mh::CclKeep ccl_keep;   // a row band's labelling between its two halves (mhip_ctx_band_ccl_begin / _finish)
     bool ccl_pending = false;
@@ -98,6 +102,7 @@ struct mhip_ctx {
     int accum_algorithm = 0;   // 0: full accumulation, 1: the band's second pass as a delta over the kept graph
     mh::DevBuf pp_mask0, pp_list, pp_tiles, pp_misc, pp_key;    // pour-point candidates on their way from the watersheds to the accumulation (PourLink)
     hipEvent_t ev_cand = nullptr;
+    hipEvent_t ev_prep = nullptr;   // behind the clears of the accumulation's node buffer, queued ahead of the stage (mhip_ctx_run: AccumPrep)
     int pour_algorithm = 0;
     int64_t nlabels_raw = -1, nlabels = -1;
     bool labels_components = false;   // LABELS came from the library's own labelling (not uploaded): 8-connected components
@@ -209,6 +214,17 @@ static inline bool on_side(mhip_ctx *c) { return t_side_ctx == c; }
 // was derived from the old content.  Host-only flag work.  uploaded: the content comes from outside (an uploaded FILLED surface
 // has no flood of this context behind it).
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded = false);
+// ---- the no-flats surface, wherever it is read (ctx.hip) --------------------------------------------------------------------------
+// The one way to c->r[MHIP_R_NOFLAT]: a surface that is pending is written first, on the context's stream (a caller on another
+// stream finds it complete), and is pending no more.  Call it before a stage's event bracket opens.
+int ctx_noflat(mhip_ctx *c, double **g = nullptr);
+// ... and in front of whatever touches raster `which` from outside the stages: a read of NOFLAT, or a write (`write`) of NOFLAT or of
+// the two rasters a pending surface is made of -- FILLED and NGDIST -- other than the context's own fill of the same DEM
+inline int ctx_settle(mhip_ctx *c, int which, bool write)
+{
+    if (which == MHIP_R_NOFLAT || (write && (which == MHIP_R_FILLED || which == MHIP_R_NGDIST))) return ctx_noflat(c);
+    return MHIP_OK;
+}
 // ---- the two ways data crosses between the host and a context (ctx.hip) -----------------------------------------------------------
 // Rows [row0, row0 + nrows) of the OWNED rows of `dev_base`, a device array of the local raster's full-width rows (halo rows
 // included) of `elem_bytes` per cell, to or from `host` by `kind`: one copy on cs(c), then one synchronisation.  The caller has

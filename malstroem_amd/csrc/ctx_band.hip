@@ -38,6 +38,7 @@ static int copy_edge_rows(mhip_ctx *c, int which, int side0, void *dst0, int sid
 {
     MH_ARG(c && which >= 0 && which < MHIP_R_COUNT_, usage);
     MH_ARG(c->r[which].p, "raster has not been computed or uploaded");
+    MH_TRY(ctx_settle(c, which, /*write=*/false));
     const int side[2] = {side0, side1};
     void *const dst[2] = {dst0, dst1};
     for (int k = 0; k < 2; ++k) MH_ARG(!dst[k] || side[k] < 2 || (side[k] == 2 ? c->ht : c->hb), "this band has no halo row on that side");
@@ -122,6 +123,7 @@ int mhip_ctx_set_halo_row_dev(mhip_ctx *c, int which, int side, const void *dev_
     MH_ARG(side == 0 ? c->ht : c->hb, "this band has no halo row on that side");
     MH_HIP(hipSetDevice(c->device));
     MH_TRY(ctx_raster(c, which));
+    MH_TRY(ctx_settle(c, which, /*write=*/true));
     int ch = 0;
     MH_TRY(row_update_dev(row_ptr(c, which, 2 + side), dev_src, (int64_t)row_bytes(c, which), &ch, cs(c)));
     if (changed) *changed = ch;
@@ -145,6 +147,7 @@ int mhip_ctx_set_halo_rows(mhip_ctx *c, int which, const void *host_top, const v
     if (!host_top && !host_bottom) return MHIP_OK;
     MH_HIP(hipSetDevice(c->device));
     MH_TRY(ctx_raster(c, which));
+    MH_TRY(ctx_settle(c, which, /*write=*/true));
     hipStream_t s = cs(c);
     const size_t rowb = row_bytes(c, which);
     DevBuf &stage = on_side(c) ? c->comm_stage_b : c->comm_stage;
@@ -168,6 +171,7 @@ int mhip_ctx_exchange_halo(mhip_ctx *c, int which, int32_t *changed)
     if (!c->ht && !c->hb) return MHIP_OK;
     MH_ARG(c->r[which].p, "raster has not been computed or uploaded");
     MH_HIP(hipSetDevice(c->device));
+    MH_TRY(ctx_settle(c, which, /*write=*/true));
     hipStream_t s = cs(c);
     const size_t rowb = row_bytes(c, which);
     MH_TRY(c->comm_stage.alloc(2 * rowb));
@@ -190,6 +194,7 @@ int mhip_ctx_exchange_edge_rows(mhip_ctx *c, int which, void *host_from_up, void
     MH_ARG(c->r[which].p, "raster has not been computed or uploaded");
     MH_ARG((!c->ht || host_from_up) && (!c->hb || host_from_down), "ctx_exchange_edge_rows: a buffer per neighbour");
     MH_HIP(hipSetDevice(c->device));
+    MH_TRY(ctx_settle(c, which, /*write=*/false));
     hipStream_t s = cs(c);
     const size_t rowb = row_bytes(c, which);
     DevBuf &stage = on_side(c) ? c->comm_stage_b : c->comm_stage;
@@ -227,6 +232,7 @@ int mhip_ctx_zero_raster(mhip_ctx *c, int which)
     MH_ARG(c && which >= 0 && which < MHIP_R_COUNT_, "ctx_zero_raster(ctx, which)");
     MH_HIP(hipSetDevice(c->device));
     MH_TRY(ctx_raster(c, which));
+    MH_TRY(ctx_settle(c, which, /*write=*/true));
     ctx_wrote(c, which);
     MH_HIP(hipMemsetAsync(c->r[which].p, 0, raster_elem(which) * (size_t)(c->H * c->W), cs(c)));
     return MHIP_OK;
@@ -584,6 +590,7 @@ int mhip_ctx_band_records(mhip_ctx *c, int which)
         // bluespots.py:195-206: the first arg-max of the accumulated flow (2), or the first arg-min of the no-flats surface (3)
         const int src = which == 2 ? MHIP_R_ACCUM : MHIP_R_NOFLAT;
         MH_ARG(c->have[src], which == 2 ? "pour points need the accumulated flow" : "pour points need the no-flats surface");
+        MH_TRY(ctx_settle(c, src, /*write=*/false));
         MH_TRY(label_arg_dev(c->r[src].as<double>() + off, c->r[MHIP_R_LABELS].as<int32_t>() + off, c->H_owned, c->W, c->nlabels,
                              which == 2, buf.as<mhip_index_record>(), cs(c), c->labels_components));
         hipLaunchKernelGGL(global_rows_kernel, dim3((unsigned)cdiv(nrec, 256)), dim3(256), 0, cs(c), buf.as<mhip_index_record>(), nrec,
@@ -684,6 +691,7 @@ int mhip_ctx_fill_begin(mhip_ctx *c, int kind, double short_, double diag, int32
     MH_HIP(hipSetDevice(c->device));
     const int which = kind ? MHIP_R_NOFLAT : MHIP_R_FILLED;
     MH_TRY(ctx_raster(c, which));
+    MH_TRY(ctx_settle(c, which, /*write=*/true));      // (this fill's raster is in flux between the calls of its loop)
     ctx_wrote(c, which);
     if (kind == 0) {
         // the tiled priority-flood first: the band's whole local solve happens here, the loop that follows only trades edge rows
@@ -735,6 +743,7 @@ int mhip_ctx_fill_attach(mhip_ctx *c, int kind, double short_, double diag)
     const int which = kind ? MHIP_R_NOFLAT : MHIP_R_FILLED;
     MH_ARG(c->r[which].p, "ctx_fill_attach: the raster to start from does not exist");
     MH_HIP(hipSetDevice(c->device));
+    MH_TRY(ctx_settle(c, which, /*write=*/true));      // (kind 1 starts from the surface that is there)
     ctx_wrote(c, which);
     if (kind == 0) {
         delete c->pf;
@@ -753,7 +762,9 @@ int mhip_ctx_noflat_verify(mhip_ctx *c, int32_t *ok)
     MH_ARG(c && ok && c->have[MHIP_R_NOFLAT] && c->have[MHIP_R_DEM], "ctx_noflat_verify(ctx, ok) needs the no-flats surface");
     MH_HIP(hipSetDevice(c->device));
     bool good = false;
-    MH_TRY(noflat_verify_dev(c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_NOFLAT].as<double>(), c->H, c->W, c->sh, c->dg, c->stream, &good, c->ht, c->hb));
+    double *g = nullptr;
+    MH_TRY(ctx_noflat(c, &g));
+    MH_TRY(noflat_verify_dev(c->r[MHIP_R_DEM].as<float>(), g, c->H, c->W, c->sh, c->dg, c->stream, &good, c->ht, c->hb));
     *ok = good ? 1 : 0;
     return MHIP_OK;
 }
@@ -891,6 +902,7 @@ int mhip_ctx_geo_begin(mhip_ctx *c, double short_, double diag, int32_t *applica
     MH_HIP(hipSetDevice(c->device));
     MH_TRY(ctx_raster(c, MHIP_R_NOFLAT));
     MH_TRY(ctx_raster(c, MHIP_R_NGDIST));
+    MH_TRY(ctx_noflat(c));      // (the distances of a pending surface are about to be overwritten)
     ctx_wrote(c, MHIP_R_NOFLAT);
     delete c->geo;
     GeoRun *g = c->geo = new GeoRun();

@@ -10,6 +10,7 @@ using namespace mh;
 
 constexpr int LABEL_START_DEFAULT = 3;      // chosen by measurement: DESIGN 4.5
 constexpr int FILL_HANDOVER_DEFAULT = 1;    // chosen by measurement: DESIGN 7
+constexpr int NOFLAT_LAZY_DEFAULT = 1;      // chosen by measurement: DESIGN 7
 
 // MHIP_FILL_HANDOVER = 0 | 1 (development knob, read per request): may a request that holds FILL and NOFLAT leave the flood's
 // last pass and its proof to the first visit of the no-flats fill?
@@ -17,6 +18,14 @@ static bool fill_handover_env()
 {
     const char *e = dev_env("MHIP_FILL_HANDOVER");
     return e ? e[0] != '0' : FILL_HANDOVER_DEFAULT != 0;
+}
+
+// MHIP_NOFLAT_LAZY = 0 | 1 (development knob, read per request): may a request that holds NOFLAT and FLOWDIR leave the no-flats
+// surface unwritten where its finishing pass has derived the directions from it (ctx.hpp: noflat_pending)?
+static bool noflat_lazy_env()
+{
+    const char *e = dev_env("MHIP_NOFLAT_LAZY");
+    return e ? e[0] != '0' : NOFLAT_LAZY_DEFAULT != 0;
 }
 
 static int stage_depths(mhip_ctx *c, hipStream_t s)
@@ -81,7 +90,8 @@ static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, Stag
 {
     const int64_t H = c->H, W = c->W, n = H * W;
     MH_ARG(c->have[MHIP_R_DEM], "NOFLAT needs the DEM");
-    MH_TRY(ctx_raster(c, MHIP_R_NOFLAT));
+    MH_TRY(ctx_raster(c, MHIP_R_NOFLAT));      // (allocated whoever writes it: the relaxation needs it, and no later reader runs out of memory)
+    c->noflat_pending = false;                 // a new surface replaces one that nobody has asked for
     MH_TRY(stage_begin(c, MHIP_STAGE_NOFLAT, s));
     if (!shdg_done) {
         // (the flood of THIS DEM has folded its extremes on the way: a request without the bluespot branch -- BASELINE configs[1] -- used
@@ -105,6 +115,13 @@ static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, Stag
         MH_HIP(hipMemsetAsync(c->nodir_cnt.p, 0, 4, s));
         d8.flowdir = c->r[MHIP_R_FLOWDIR].as<uint8_t>();
         d8.nodir = c->nodir_cnt.as<unsigned int>();
+        // nobody reads the surface in this request but the pass that writes the directions: it may stay F and the distances, which
+        // then live in a raster of the context's (they outlive the stage's workspace), until somebody asks (ctx_noflat)
+        if (c->nranks == 1 && noflat_lazy_env()) {
+            MH_TRY(ctx_raster(c, MHIP_R_NGDIST));
+            d8.dist = c->r[MHIP_R_NGDIST].as<uint32_t>();
+            d8.defer = true;
+        }
     }
     const int rc_nf = fill_noflat_dev(c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_NOFLAT].as<double>(), H, W, c->sh, c->dg, s, &st,
                                       c->r[MHIP_R_FILLED].as<float>(), tail_hook, d8.flowdir ? &d8 : nullptr, ho);
@@ -116,19 +133,21 @@ static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, Stag
     c->noflat_st = st;
     ctx_wrote(c, MHIP_R_NOFLAT);
     c->have[MHIP_R_NOFLAT] = true;
+    c->noflat_pending = d8.deferred;
     return MHIP_OK;
 }
 
 static int stage_flowdir(mhip_ctx *c, hipStream_t s)
 {
     MH_ARG(c->have[MHIP_R_NOFLAT], "FLOWDIR needs the no-flats surface");
+    double *g = nullptr;
+    MH_TRY(ctx_noflat(c, &g));      // (in front of the stage's events)
     MH_TRY(ctx_raster(c, MHIP_R_FLOWDIR));
     MH_TRY(stage_begin(c, MHIP_STAGE_FLOWDIR, s));
     ctx_wrote(c, MHIP_R_FLOWDIR);
     MH_TRY(c->nodir_cnt.alloc(4));
     MH_HIP(hipMemsetAsync(c->nodir_cnt.p, 0, 4, s));
-    MH_TRY(d8_dev(c->r[MHIP_R_NOFLAT].as<double>(), c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->H, c->W, 1, s, c->row0 - c->ht,
-                  c->H_global, c->nodir_cnt.as<unsigned int>()));
+    MH_TRY(d8_dev(g, c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->H, c->W, 1, s, c->row0 - c->ht, c->H_global, c->nodir_cnt.as<unsigned int>()));
     MH_TRY(stage_end(c, MHIP_STAGE_FLOWDIR, s));
     c->have[MHIP_R_FLOWDIR] = true;
     c->flowdir_own = true;
@@ -148,7 +167,8 @@ static int stage_flowdir_fused(mhip_ctx *c, hipStream_t s)
     return MHIP_OK;
 }
 
-static int stage_accum(mhip_ctx *c, hipStream_t s, PourLink *pour = nullptr)
+// prep: the node buffer, cleared ahead of the stage (mhip_ctx_run)
+static int stage_accum(mhip_ctx *c, hipStream_t s, PourLink *pour = nullptr, AccumPrep *prep = nullptr)
 {
     MH_ARG(c->have[MHIP_R_FLOWDIR], "ACCUM needs flow directions");
     MH_TRY(ctx_raster(c, MHIP_R_ACCUM));
@@ -161,7 +181,8 @@ static int stage_accum(mhip_ctx *c, hipStream_t s, PourLink *pour = nullptr)
     c->accum_algorithm = delta_done ? 1 : 0;
     ctx_wrote(c, MHIP_R_ACCUM);
     if (!delta_done)
-        MH_TRY(accum_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_ACCUM].as<double>(), c->H, c->W, s, c->ht, c->hb, 0, nullptr, pour));
+        MH_TRY(accum_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_ACCUM].as<double>(), c->H, c->W, s, c->ht, c->hb, 0, nullptr, pour, nullptr,
+                         prep));
     MH_TRY(stage_end(c, MHIP_STAGE_ACCUM, s));
     c->have[MHIP_R_ACCUM] = true;
     return MHIP_OK;
@@ -241,6 +262,8 @@ static int stage_pourpoints(mhip_ctx *c, hipStream_t s, PourLink *pour = nullptr
     MH_TRY(ctx_ensure_labels_final(c, s));
     MH_TRY(ctx_label_max(c, s));
     MH_TRY(c->pour.alloc(sizeof(mhip_index_record) * (size_t)(c->nlabels + 1)));
+    double *g = nullptr;
+    if (!c->have[MHIP_R_ACCUM]) MH_TRY(ctx_noflat(c, &g));      // (the arg-min below reads the surface; in front of the stage's events)
     MH_TRY(stage_begin(c, MHIP_STAGE_POURPOINTS, s));
     // bluespots.py:195-206: max accumulated flow if available, else min of the no-flats surface
     bool from_keys = false;
@@ -261,8 +284,7 @@ static int stage_pourpoints(mhip_ctx *c, hipStream_t s, PourLink *pour = nullptr
         MH_TRY(label_arg_dev(c->r[MHIP_R_ACCUM].as<double>(), c->r[MHIP_R_LABELS].as<int32_t>(), H, W, c->nlabels, true,
                              c->pour.as<mhip_index_record>(), s, c->labels_components));
     else
-        MH_TRY(label_arg_dev(c->r[MHIP_R_NOFLAT].as<double>(), c->r[MHIP_R_LABELS].as<int32_t>(), H, W, c->nlabels, false,
-                             c->pour.as<mhip_index_record>(), s));
+        MH_TRY(label_arg_dev(g, c->r[MHIP_R_LABELS].as<int32_t>(), H, W, c->nlabels, false, c->pour.as<mhip_index_record>(), s));
     MH_TRY(stage_end(c, MHIP_STAGE_POURPOINTS, s));
     c->pour_valid = true;
     return MHIP_OK;
@@ -338,6 +360,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     if (!c->stream_c) MH_TRY(side_stream(&c->stream_c));
     MH_TRY(ctx_fork_join_events(c));
     if (!c->ev_cand) MH_HIP(hipEventCreateWithFlags(&c->ev_cand, hipEventDisableTiming));
+    if (!c->ev_prep) MH_HIP(hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
     hipStream_t sb = c->stream_b;
     const bool do_fill = (mask & MHIP_STAGE_FILL) != 0;
     MH_ARG(c->have[MHIP_R_DEM] || !(mask & (MHIP_STAGE_FILL | MHIP_STAGE_NOFLAT)), "FILL / NOFLAT need the DEM");
@@ -382,6 +405,12 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     pour_link.wait = [](void *a) { return static_cast<CandHand *>(a)->f.get(); };
     static const bool pour_pass = [] { const char *e = dev_env("MHIP_POUR"); return e && std::string(e) == "pass"; }();
     PourLink *const pour = ((mask & MHIP_STAGE_ACCUM) && (mask & MHIP_STAGE_WATERSHED) && (mask & MHIP_STAGE_POURPOINTS) && !pour_pass) ? &pour_link : nullptr;
+    // The accumulation's node buffer and its clears depend on the raster's shape alone.  Behind the finishing pass they sat between
+    // its read-back and accum_tile_kernel, on the critical branch of the tail (0.2 ms at 16384^2); queued when the main thread turns
+    // to the no-flats stage, on the stream the watersheds will use much later, the clear is through before the stage's first visit
+    // starts (29 us: DESIGN 7.0000).  A request that never reaches the accumulation hands the buffer back when `acc_prep` goes.
+    AccumPrep acc_prep;
+    const bool prep_accum = (mask & MHIP_STAGE_ACCUM) && (mask & (MHIP_STAGE_NOFLAT | MHIP_STAGE_FLOWDIR)) && !c->ht && !c->hb;
     const bool ws_needs_new_flowdir = (mask & MHIP_STAGE_WATERSHED) && (mask & MHIP_STAGE_FLOWDIR);
     int rc_b = MHIP_OK;
     char err_b[512] = "";
@@ -442,6 +471,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
             if (c->fill_st.have_minmax) short_diag_from_minmax(c->fill_st.dem_min, c->fill_st.dem_max, c->fill_st.dem_nan, &c->sh, &c->dg);
             else MH_TRY(short_diag_dev(c->r[MHIP_R_DEM].as<float>(), c->H * c->W, &c->sh, &c->dg, s));
         }
+        if (prep_accum) MH_TRY(accum_prepare_dev(&acc_prep, c->H, c->W, c->stream_c, c->ev_prep));
         const int label_start = label_start_env();
         // (0 with a hand-over pending: the depths the label branch reads are written by the stage's first visit -- the hook fires behind it)
         const bool owed = ho && ho->pending;
@@ -459,7 +489,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     }();
     tail_hook.fire(s);                    // (no NOFLAT in the mask, or it failed early: the other thread is never left waiting)
     flowdir_ready.set_value(rc_a);
-    if (rc_a == MHIP_OK && (mask & MHIP_STAGE_ACCUM)) rc_a = stage_accum(c, s, pour);
+    if (rc_a == MHIP_OK && (mask & MHIP_STAGE_ACCUM)) rc_a = stage_accum(c, s, pour, &acc_prep);
     // POURPOINTS needs the final labels and the accumulation, not the watersheds: it runs next to them
     const int rc_l = label_fut.get();
     if (rc_a == MHIP_OK && rc_l == MHIP_OK && (mask & MHIP_STAGE_POURPOINTS)) {

@@ -1200,21 +1200,33 @@ __global__ __launch_bounds__(256) void ng_compact_kernel(unsigned long long *mar
 }
 
 // ---- G = F + u * D -------------------------------------------------------------------------------------------------------
+// One cell of the surface from its filled value and its distance: the ONE place this arithmetic stands.  ng_assemble_kernel, both
+// bodies of ng_finish_kernel and the late assembly of a deferred surface (noflat_assemble_dev) call it, so a surface that is
+// rebuilt from F and D is the surface the finishing pass checked, bit for bit.  *beyond: the distance is past the uint32 headroom.
+// A source has distance 0: G = F whatever its class.
+__device__ __forceinline__ double ng_value(float f, uint32_t dd, double seed_add, bool *beyond)
+{
+    *beyond = false;
+    if (dd == D_IRR) return (double)f + seed_add;   // a flat cell of an irregular level: an upper bound for the relaxation
+    if (dd >= 0x80000000u) {                        // a distance beyond the uint32 headroom (a very long flat in a low binade;
+        *beyond = true;                             // every smaller distance is exact): the relaxation settles it as well
+        return (double)f + seed_add;
+    }
+    return dd ? (double)f + (double)dd * class_ulp(class_above(f)) : (double)f;
+}
+
+// counters == nullptr: the late assembly of a surface the finishing pass has accepted (no cell is beyond the headroom)
 __global__ __launch_bounds__(256) void ng_assemble_kernel(const float *__restrict__ F, const uint32_t *__restrict__ d, double *__restrict__ G, int64_t n,
                                                           double seed_add, unsigned long long *counters)
 {
     const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i0 >= n) return;
     unsigned bad = 0;
-    // a source has distance 0: G = F whatever its class
     auto value = [&](float f, uint32_t dd) {
-        if (dd == D_IRR) return (double)f + seed_add;   // a flat cell of an irregular level: an upper bound for the relaxation
-        if (dd >= 0x80000000u) {                        // a distance beyond the uint32 headroom (a very long flat in a low binade;
-            ++bad;                                      // every smaller distance is exact): the relaxation settles it as well
-            return (double)f + seed_add;
-        }
-        const uint32_t e = class_above(f);
-        return dd ? (double)f + (double)dd * class_ulp(e) : (double)f;
+        bool beyond;
+        const double v = ng_value(f, dd, seed_add, &beyond);
+        bad += beyond ? 1u : 0u;
+        return v;
     };
     if (i0 + 4 <= n) {
         const float4 f = *reinterpret_cast<const float4 *>(F + i0);
@@ -1225,7 +1237,7 @@ __global__ __launch_bounds__(256) void ng_assemble_kernel(const float *__restric
     } else {
         for (int64_t i = i0; i < n; ++i) G[i] = value(F[i], d[i]);
     }
-    if (bad) atomicAdd(&counters[C_UNREACHED], (unsigned long long)bad);
+    if (bad && counters) atomicAdd(&counters[C_UNREACHED], (unsigned long long)bad);
 }
 
 // ---- the strict equation (*) at every cell, in the reference's arithmetic (_fill.pyx:107-117) ------------------------------
@@ -1290,7 +1302,10 @@ __device__ __forceinline__ double dright(double v)
 }
 // D8: the cell's flow direction as well (flow.terrain_flowdirection with the edges flowing outward, d8.hip) -- the 3 x 3
 // neighbourhood of G is in registers here already; as a pass of its own D8 reads all of G back (8 of its 9 bytes per cell).
-template <bool D8>
+// STORE == false (a chain request on one undivided context): the one store of G is left out -- nobody reads the surface in
+// such a request, the directions come from the registers -- and nothing else changes; whoever asks for G later gets it from F and
+// the distances (noflat_assemble_dev).
+template <bool D8, bool STORE = true>
 __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict__ F, const uint32_t *__restrict__ d, const float *__restrict__ dem,
                                                         double *__restrict__ G, int64_t H, int64_t W, double sh, double dg, double seed_add, int fixed_top,
                                                         int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir, unsigned int *nodir)
@@ -1306,14 +1321,10 @@ __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict_
     unsigned unreached = 0, bad = 0, anynodir = 0;
     auto value = [&](int64_t r) -> double {
         if (!(r >= 0 && r < H && col_in)) return PINF;
-        const float f = F[r * W + cc];
-        const uint32_t dd = d[r * W + cc];
-        if (dd == D_IRR) return (double)f + seed_add;                   // (ng_assemble_kernel)
-        if (dd >= 0x80000000u) {
-            unreached += mine && r >= rb && r < rb + FRB ? 1u : 0u;
-            return (double)f + seed_add;
-        }
-        return dd ? (double)f + (double)dd * class_ulp(class_above(f)) : (double)f;
+        bool beyond;
+        const double v = ng_value(F[r * W + cc], d[r * W + cc], seed_add, &beyond);
+        unreached += beyond && mine && r >= rb && r < rb + FRB ? 1u : 0u;
+        return v;
     };
     double a = value(rb - 1), b = value(rb);
     for (int i = 0; i < FRB; ++i) {
@@ -1331,7 +1342,7 @@ __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict_
             }
             const bool halo = (r == 0 && fixed_top) || (r == H - 1 && fixed_bot);   // the neighbouring band checks its own rows
             bad += (b == want || halo) ? 0u : 1u;                                    // NaN anywhere fails too
-            G[r * W + c] = b;
+            if (STORE) G[r * W + c] = b;
             if (D8) {
                 unsigned code;
                 if (r == 0 || r == H - 1 || c == 0 || c == W - 1) code = edge_code(r, c, H - 1, W - 1);
@@ -1370,12 +1381,10 @@ __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict_
 #define NG_FINISH_RESIDENCY
 #endif
 #if NG_FINISH_AHEAD
-template <>
-__global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true>(const float *__restrict__ F, const uint32_t *__restrict__ d,
-                                                                                  const float *__restrict__ dem, double *__restrict__ G, int64_t H, int64_t W,
-                                                                                  double sh, double dg, double seed_add, int fixed_top, int fixed_bot,
-                                                                                  unsigned long long *counters, uint8_t *__restrict__ flowdir,
-                                                                                  unsigned int *nodir)
+template <bool STORE>
+__device__ __forceinline__ void ng_finish_ahead(const float *__restrict__ F, const uint32_t *__restrict__ d, const float *__restrict__ dem,
+                                                double *__restrict__ G, int64_t H, int64_t W, double sh, double dg, double seed_add, int fixed_top,
+                                                int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir, unsigned int *nodir)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t c = ((int64_t)blockIdx.x * 4 + wave) * TI + lane - 1;
@@ -1398,12 +1407,10 @@ __global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true
     };
     auto value = [&](int64_t r, const Row &x) -> double {
         if (!(r >= 0 && r < H && col_in)) return PINF;
-        if (x.dd == D_IRR) return (double)x.f + seed_add;               // (ng_assemble_kernel)
-        if (x.dd >= 0x80000000u) {
-            unreached += mine && r >= rb && r < rb + FRB ? 1u : 0u;
-            return (double)x.f + seed_add;
-        }
-        return x.dd ? (double)x.f + (double)x.dd * class_ulp(class_above(x.f)) : (double)x.f;
+        bool beyond;
+        const double v = ng_value(x.f, x.dd, seed_add, &beyond);
+        unreached += beyond && mine && r >= rb && r < rb + FRB ? 1u : 0u;
+        return v;
     };
     const Row xa = load(rb - 1), xb = load(rb);
     Row x0 = load(rb + 1), x1{0.0f, 0.0f, 0u};
@@ -1430,7 +1437,7 @@ __global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true
             }
             const bool halo = (r == 0 && fixed_top) || (r == H - 1 && fixed_bot);   // the neighbouring band checks its own rows
             bad += (b == want || halo) ? 0u : 1u;                                    // NaN anywhere fails too
-            G[r * W + c] = b;
+            if (STORE) G[r * W + c] = b;
             unsigned code;
             if (r == 0 || r == H - 1 || c == 0 || c == W - 1) code = edge_code(r, c, H - 1, W - 1);
             else {
@@ -1456,6 +1463,18 @@ __global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true
     if (bad) atomicAdd(&counters[C_MISMATCH], (unsigned long long)bad);
     if (__any(anynodir != 0u) && lane == 0) *nodir = 1u;      // ("none" / "some": a plain store of the same value)
 }
+#define NG_FINISH_AHEAD_KERNEL(STORE)                                                                                                                  \
+    template <>                                                                                                                                        \
+    __global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true, STORE>(                                                          \
+        const float *__restrict__ F, const uint32_t *__restrict__ d, const float *__restrict__ dem, double *__restrict__ G, int64_t H, int64_t W,      \
+        double sh, double dg, double seed_add, int fixed_top, int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir,              \
+        unsigned int *nodir)                                                                                                                           \
+    {                                                                                                                                                  \
+        ng_finish_ahead<STORE>(F, d, dem, G, H, W, sh, dg, seed_add, fixed_top, fixed_bot, counters, flowdir, nodir);                                  \
+    }
+NG_FINISH_AHEAD_KERNEL(true)
+NG_FINISH_AHEAD_KERNEL(false)
+#undef NG_FINISH_AHEAD_KERNEL
 #endif
 
 // rn(eps / 2**(E - 52)) for the binade class e (E = e - 127) with eps = M * 2**q exactly; 0: no integer weight in (0, 2**28)
@@ -1732,7 +1751,12 @@ int GeoRun::end(hipStream_t s, bool *ok, FillStats *st)
     // every round (and the test hook's memset) is behind this point of the stream: what follows is one launch, a pure stream over
     // HBM that leaves the LDS alone -- the label branch may run beside it (mhip_ctx_run, MHIP_LABEL_START=3)
     if (tail_hook) tail_hook->fire_at(StageHook::FINISH, s);
-    if (with_d8)
+    const bool no_store = with_d8 && defer_out;      // (dist is the caller's raster then: it outlives this run)
+    out_deferred = false;
+    if (no_store)
+        hipLaunchKernelGGL((ng_finish_kernel<true, false>), dim3((unsigned)((W + 4 * TI - 1) / (4 * TI)), (unsigned)((H + FRB - 1) / FRB)), dim3(256), 0, s, filled, dist,
+                           dem, out, H, W, sh, dg, seed_add, fixed_top, fixed_bot, m.d_cnt, d8_out, d8_nodir);
+    else if (with_d8)
         hipLaunchKernelGGL(ng_finish_kernel<true>, dim3((unsigned)((W + 4 * TI - 1) / (4 * TI)), (unsigned)((H + FRB - 1) / FRB)), dim3(256), 0, s, filled, dist, dem,
                            out, H, W, sh, dg, seed_add, fixed_top, fixed_bot, m.d_cnt, d8_out, d8_nodir);
     else if (!partial)
@@ -1786,7 +1810,23 @@ int GeoRun::end(hipStream_t s, bool *ok, FillStats *st)
     }
     *ok = partial ? true : !(h_all[C_UNREACHED] || h_all[C_MISMATCH]);
     d8_done = with_d8 && !partial && *ok;        // (a surface that still goes through the relaxation gets its directions from d8.hip)
+    // The surface stays unwritten only where this pass was the last word on it.  Anything else -- cells beyond the headroom that the
+    // relaxation settles in `out`, a rejected surface -- gets the store the pass left out, now: the same values from the same function
+    if (no_store) {
+        if (d8_done) out_deferred = true;
+        else MH_TRY(noflat_assemble_dev(filled, dist, out, n, seed_add, s));
+    }
     m.ws.release();
+    return MHIP_OK;
+}
+
+// G = F + u * D as a pass of its own, from the function the finishing pass checked the surface with (ng_value): the store that a
+// request with a deferred surface left out.  No counters: the caller knows what the finishing pass found
+int noflat_assemble_dev(const float *d_filled, const uint32_t *d_dist, double *d_out, int64_t n, double seed_add, hipStream_t s)
+{
+    hipLaunchKernelGGL(ng_assemble_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, d_filled, d_dist, d_out, n, seed_add,
+                       (unsigned long long *)nullptr);
+    MH_HIP(hipGetLastError());
     return MHIP_OK;
 }
 
@@ -1816,7 +1856,11 @@ int fill_noflat_geodesic_dev(const float *d_dem, const float *d_filled, double *
     GeoRun g;
     g.handover = ho;
     g.tail_hook = tail_hook;
-    if (d8) { g.d8_out = d8->flowdir; g.d8_nodir = d8->nodir; d8->done = false; }
+    if (d8) {
+        g.d8_out = d8->flowdir; g.d8_nodir = d8->nodir; d8->done = false; d8->deferred = false;
+        if (d8->dist) g.dist = d8->dist;
+        g.defer_out = d8->defer && d8->dist;
+    }
     g.dem = d_dem; g.filled = d_filled; g.out = d_out; g.H = H; g.W = W; g.sh = sh; g.dg = dg;
     g.allow_partial = partial != nullptr && seed_add == seed_add && seed_add < 1e300;
     g.seed_add = seed_add;
@@ -1841,7 +1885,7 @@ int fill_noflat_geodesic_dev(const float *d_dem, const float *d_filled, double *
     while (active) MH_TRY(g.batch(s, &active));
     MH_TRY(g.end(s, &ok, st));
     if (partial) *partial = g.partial;
-    if (d8) d8->done = g.d8_done;
+    if (d8) { d8->done = g.d8_done; d8->deferred = g.out_deferred; }
     if (!ok && st) st->geo_reject = 2;
     return ok ? MHIP_OK : MHIP_ELIMIT;
 }

@@ -1192,7 +1192,15 @@ __device__ __forceinline__ void pf_solve_queue_body(const SolveArgs &sa, PfQueue
             }
             // mark word of a block: bit 0 = queued, or (while bit 1 is up) woken again; bit 1 = a visit of it is running.  Returned
             // before the barrier below: a level that changes from now on finds bit 0 clear and sets it
-            if (blk >= 0) (void)atomicExch(&sa.mark_cur[blk], 2u);
+            if (blk >= 0) {
+                (void)atomicExch(&sa.mark_cur[blk], 2u);
+                // ... and PERFORMED before the barrier: the exchange returns nothing, so nothing waited for it, and the workgroup
+                // barrier does not drain vmcnt.  With the exchange still on its way to its L2 channel the level loads below (other
+                // channels) could be served first; a neighbour that lowered one of those levels in between found bit 0 still up (the
+                // block counts as queued: no new ticket), then the exchange arrived and wiped that bit: a wake-up lost, a level left
+                // too high, the flood's proof failed (fill_algorithm 4) -- once in several thousand steps
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
             s_blk = blk;
             s_wake = 0;
         }

@@ -24,7 +24,9 @@ import sys
 # compulsory HBM bytes per cell and step of the streaming kernels (each input read once, each output written once)
 COMPULSORY = {
     "d8s_kernel": (8, 1), "d8_kernel": (8, 1), "minmax_kernel": (4, 0), "pf_apply_check_kernel": (6, 8), "pf_apply_kernel": (6, 8),
-    "pf_tile_kernel": (4, 2), "ng_first_kernel": (4, 5.1), "ng_handover_kernel": (6.4, 13.1), "ng_finish_kernel": (12, 8), "ccl_tile_kernel": (4, 4),
+    "pf_tile_kernel": (4, 2), "ng_first_kernel": (4, 5.1), "ng_handover_kernel": (6.4, 13.1), "ng_finish_kernel": (12, 8),
+    "ng_finish_kernel<true, false>": (12, 1),      # (a chain request: the surface is not stored, the directions are)
+    "ccl_tile_kernel": (4, 4),
     "ccl_emit_ranked_kernel": (4, 4), "stats_kernel": (8, 0), "count_kernel": (4, 0), "ws_tile_kernel": (5, 4), "ws_assign_hop_kernel": (8, 4),
     "arg_packed_kernel": (12, 0), "accum_tile_kernel": (1, 2), "accum_final_walk_kernel": (3, 8), "fill_check_kernel": (8, 0), "depths_kernel": (8, 4),
 }
@@ -56,8 +58,8 @@ def main():
                "fetch_bytes_per_cell_raw": round(fk * 1024 / cells, 3), "fetch_bytes_per_cell": round(2 * fk * 1024 / cells, 3),
                "write_bytes_per_cell": round(wk * 1024 / cells, 3)}
         base = re.sub(r"<.*", "", k)
-        if base in COMPULSORY and n * n == cells:
-            cr, cw = COMPULSORY[base]
+        if (k in COMPULSORY or base in COMPULSORY) and n * n == cells:
+            cr, cw = COMPULSORY.get(k) or COMPULSORY[base]
             row["compulsory_read_bytes_per_cell"], row["compulsory_write_bytes_per_cell"] = cr, cw
             row["below_compulsory"] = bool(row["fetch_bytes_per_cell"] < 0.97 * cr)
         rows.append(row)
