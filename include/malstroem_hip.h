@@ -62,6 +62,9 @@ typedef struct { double vmax, vmin_pos; int64_t cells, pos; } mhip_zone_record;
  * mhip_ctx_flow_distance */
 #define MHIP_ZSRC_WETAT 100
 #define MHIP_ZSRC_FLOWDIST 101
+/* ... and the two rasters of the last mhip_ctx_hand: the height above the nearest drainage, the distance to it */
+#define MHIP_ZSRC_HAND 102
+#define MHIP_ZSRC_DRAINDIST 103
 
 /* ---- library / device ------------------------------------------------------------------------- */
 const char *mhip_last_error(void);
@@ -176,6 +179,17 @@ int mhip_watersheds_i32(const uint8_t *flowdir, int32_t *labels_inout, int64_t H
  * MHIP_EINVAL.  unresolved (optional): the number of cells that hold -1. */
 int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, double scale, int64_t nlab, float *out_dist,
                        mhip_index_record *records, int64_t *unresolved);
+
+/* Height above the nearest drainage and the distance to it along the flow path (no reference counterpart; the definition is
+ * tests/_hand.py).  A cell is a drainage cell when accum >= threshold (compared in float64; a NaN is none) or, with
+ * labels, its label is != 0; threshold finite and >= 1.  D(c) is the first drainage cell on the downstream walk from c, c included,
+ * after `no` orthogonal and `nd` diagonal steps -- the first one, whatever the accumulation does further down.  A cell whose walk
+ * ends before it meets one (a code > 7, a step out of the raster, a flow cycle) is undrained.
+ * out_hand = elev[c] - elev[D(c)] as one float32 subtraction (+0.0 on a drainage cell; a result that is a NaN is stored as the quiet
+ * NaN 0x7fc00000), `nodata` verbatim where undrained.  out_dist (optional) = float((double(no) + double(nd) * 1.4142135623730951) *
+ * scale), -1 where undrained; scale: the cell size, finite and > 0.  undrained (optional): the number of undrained cells. */
+int mhip_hand_f32(const uint8_t *flowdir, const double *accum, const float *elev, const int32_t *labels, int64_t H, int64_t W, double threshold,
+                  double scale, float nodata, float *out_hand, float *out_dist, int64_t *undrained);
 
 /* Burn lines into a DEM in place (no reference counterpart; the definition is tests/_burn.py).  Segment (r0, c0) ->
  * (r1, c1) has n = max(|dr|, |dc|) steps along its major axis (the column when |dc| >= |dr|); step k = 0 .. n sits at major = start
@@ -529,6 +543,13 @@ int mhip_ctx_wet_at_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst)
 int mhip_ctx_flow_distance(mhip_ctx *ctx, double scale, int64_t *unresolved);
 int mhip_ctx_flow_distance_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
 int mhip_ctx_flow_distance_records(mhip_ctx *ctx, mhip_index_record *records);
+/* mhip_hand_f32 on the resident FLOWDIR, ACCUM and the elevation raster elev_source (MHIP_R_FILLED or MHIP_R_DEM) of an undivided
+ * context, with stop_at_labels also on its (filtered or uploaded) LABELS; a row band is refused.  Both rasters stay in buffers of
+ * the context (no members of enum mhip_raster) until FLOWDIR, ACCUM, the elevation raster or -- when they were used -- LABELS are
+ * written again: hand_rows copies rows [row0, row0 + nrows) of the height (which = 0) or of the distance (which = 1).
+ * mhip_ctx_get_i64 "hand_undrained": the undrained cells of the result held, -1: none. */
+int mhip_ctx_hand(mhip_ctx *ctx, int32_t elev_source, double threshold, int32_t stop_at_labels, double scale, float nodata, int64_t *undrained);
+int mhip_ctx_hand_rows(mhip_ctx *ctx, int32_t which, int64_t row0, int64_t nrows, float *dst);
 /* mhip_burn_lines_f32 on the resident DEM of an undivided context, in place; a row band is refused.  One more writer of the DEM:
  * every raster, record set, table and result derived from it is dropped as after an upload (the stages run again on the adapted
  * DEM).  nseg == 0 leaves the context as it is. */
@@ -538,7 +559,7 @@ int mhip_ctx_burn_lines(mhip_ctx *ctx, int64_t nseg, const mhip_burn_segment *se
  * of the context (no member of enum mhip_raster).  The zones come from outside: no write of a raster drops them, a new rasterize
  * replaces them.  zones_rows copies rows [row0, row0 + nrows) of the raster.  zone_stats: mhip_zone_stats_f32 of a resident
  * float32 raster over the zones, records[nzone + 1]; source: MHIP_R_DEM, MHIP_R_FILLED, MHIP_R_DEPTHS, MHIP_R_FINALDEPTHS,
- * MHIP_ZSRC_WETAT or MHIP_ZSRC_FLOWDIST; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
+ * MHIP_ZSRC_WETAT, MHIP_ZSRC_FLOWDIST, MHIP_ZSRC_HAND or MHIP_ZSRC_DRAINDIST; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
  * without zones.  mhip_ctx_get_i64 "zones": nzone of the raster held, -1: none. */
 int mhip_ctx_rasterize_zones(mhip_ctx *ctx, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
                              const int32_t *ring_zone, int64_t nzone, int32_t grow);

@@ -135,6 +135,49 @@ def flow_distance(flowdir, labelled=None, cellsize=1.0, records=False):
     return (out, rec, unresolved.value) if records else out
 
 
+def check_hand_nodata(nodata):
+    """The nodata value of a HAND raster as a float32 (``adaptations.check_nodata``'s rule, and it must fit the raster's type;
+    ``ValueError`` otherwise; nothing touches the library)."""
+    from ..adaptations import check_nodata
+    v = check_nodata(nodata)
+    with np.errstate(over="ignore"):
+        f = np.float32(v)
+    if np.isfinite(v) and not np.isfinite(f):
+        raise ValueError("nodata must fit a float32, got %r" % (nodata,))
+    return f
+
+
+def _like(name, a, shape, dtype):
+    a = np.asarray(a)
+    if a.shape != shape:
+        raise ValueError("shape mismatch: %s is %s, the flow directions are %s" % (name, a.shape, shape))
+    if a.dtype != dtype:
+        raise ValueError("Buffer dtype mismatch, expected '%s' but got '%s'" % (np.dtype(dtype).name, a.dtype))
+    return np.ascontiguousarray(a)
+
+
+def hand(flowdir, accum, elev, threshold, labelled=None, cellsize=1.0, nodata=-9999.0, distance=False):
+    """Height above the nearest drainage: per cell ``elev`` (float32) minus the elevation of the first drainage cell on its flow
+    path -- a cell with ``accum >= threshold`` (float64; the stream cells of ``flow_paths``) or, with ``labelled`` (int32), a cell
+    inside a bluespot -- as float32; a drainage cell holds 0, a cell whose path ends without meeting one (at the raster's edge, in a
+    sink, on a flow cycle) holds ``nodata``.  No reference counterpart.
+
+    ``distance=True``: ``(hand, dist, undrained)`` -- ``dist`` is the distance along the flow path to that drainage cell in units of
+    ``cellsize`` as ``flow_distance`` measures it (-1 where ``hand`` holds ``nodata``), ``undrained`` counts those cells."""
+    from ..flowpaths import check_threshold
+    thr, scale, nd = check_threshold(threshold), check_cellsize(cellsize), check_hand_nodata(nodata)
+    fd = _flowdir(flowdir)
+    acc, z = _like("accum", accum, fd.shape, DTYPE_ACCUM), _like("elev", elev, fd.shape, np.float32)
+    lab = _like("labelled", labelled, fd.shape, np.int32) if labelled is not None else None
+    out = np.empty(fd.shape, dtype=np.float32)
+    dist = np.empty(fd.shape, dtype=np.float32) if distance else None
+    undrained = ctypes.c_int64(0)
+    _lib.call("mhip_hand_f32", _lib.ptr(fd), _lib.ptr(acc), _lib.ptr(z), _lib.ptr(lab) if lab is not None else None, _lib.i64(fd.shape[0]),
+              _lib.i64(fd.shape[1]), ctypes.c_double(thr), ctypes.c_double(scale), ctypes.c_float(nd), _lib.ptr(out),
+              _lib.ptr(dist) if distance else None, ctypes.byref(undrained))
+    return (out, dist, undrained.value) if distance else out
+
+
 # ---- per-cell host helpers (reference flow.py:170-301), used by stream tracing and tests --------------
 
 def direction_to_delta(direction):

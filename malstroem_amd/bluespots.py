@@ -103,13 +103,20 @@ class BluespotTool(object):
     (``flowpaths.features_from_reaches``), written after the pour points are taken, from the resident rasters; with
     ``flowpaths_stop_at_bluespots`` a reach ends where it runs into a (filtered) bluespot.  ``flowpaths_run_accum``: the pipeline
     holds no accumulated flow yet and the stage runs first -- after the pour points, which stay where they are without it.
+
+    ``output_hand_raster`` / ``output_drain_distance_raster`` (no reference counterpart): raster writers for the height
+    of every cell of the filled surface above the first cell on its flow path that has at least ``hand_threshold`` cells upstream or
+    lies in a (filtered) bluespot (nodata: the writer's, -9999 without one), and for the distance in metres along the flow path to
+    that cell (-1 where there is none).  They are computed after the pour points are taken, from the resident rasters, and streamed
+    in row windows.  ``hand_run_accum``: as ``flowpaths_run_accum``.  A tool that reads its inputs itself needs ``input_dem`` for them.
     """
 
     def __init__(self, input_depths, input_flowdir, input_bluespot_filter_function,
                  output_labeled_raster, output_pourpoints, output_watersheds_raster,
                  input_accum=None, input_dem=None, output_labeled_vector=None, output_watersheds_vector=None,
                  pipeline=None, device=0, output_flowlength_raster=None, output_flowpaths=None, flowpaths_threshold=None,
-                 flowpaths_stop_at_bluespots=True, flowpaths_run_accum=False):
+                 flowpaths_stop_at_bluespots=True, flowpaths_run_accum=False, output_hand_raster=None, output_drain_distance_raster=None,
+                 hand_threshold=None, hand_run_accum=False):
         self.input_depths = input_depths
         self.input_flowdir = input_flowdir
         self.input_bluespot_filter_function = input_bluespot_filter_function
@@ -128,6 +135,13 @@ class BluespotTool(object):
         self.flowpaths_run_accum = flowpaths_run_accum
         if output_flowpaths is not None:
             self.flowpaths_threshold = check_threshold(flowpaths_threshold)
+        self.output_hand_raster = output_hand_raster
+        self.output_drain_distance_raster = output_drain_distance_raster
+        self.hand_run_accum = hand_run_accum
+        self.want_hand = output_hand_raster is not None or output_drain_distance_raster is not None
+        if self.want_hand:
+            self.hand_threshold = check_threshold(hand_threshold)
+            assert self.input_dem or pipeline, "The height above drainage needs input_dem"
         assert self.input_accum or self.input_dem or pipeline, "Either input_dem or input_accum must be specified"
         self.logger = logging.getLogger(__name__)
 
@@ -148,6 +162,9 @@ class BluespotTool(object):
                 # DEM invalidates every raster derived from the previous one
                 pipe.upload("dem", self.input_dem.read())
                 pipe.run("noflat")
+            elif self.want_hand:
+                pipe.upload("dem", self.input_dem.read())      # (the filled surface the heights are measured on)
+                pipe.run("fill")
             pipe.upload("depths", depths)
             pipe.upload("flowdir", self.input_flowdir.read())
             if self.input_accum:
@@ -186,15 +203,27 @@ class BluespotTool(object):
                 for feature, lfp in zip(pour_points, pipe.flow_distance_records()):
                     feature['properties'].update(wshed_lfp=float(lfp['value']), lfp_row=int(lfp['row']), lfp_col=int(lfp['col']))
             self.output_pourpoints.write_geojson_features(dict(type="FeatureCollection", features=pour_points))
+            # the accumulated flow for the flow paths and the heights above drainage, once, where the pipeline holds none yet
+            if ((self.output_flowpaths is not None and (self.flowpaths_run_accum or (own and not self.input_accum))) or
+                    (self.want_hand and (self.hand_run_accum or (own and not self.input_accum)))):
+                self.logger.info("Calculating flow accumulation")
+                pipe.run("accum")
             if self.output_flowpaths is not None:
-                if self.flowpaths_run_accum or (own and not self.input_accum):
-                    self.logger.info("Calculating flow accumulation")
-                    pipe.run("accum")
                 self.logger.info("Extracting flow paths")
                 xy, offsets, reaches, unresolved = pipe.flow_paths(self.flowpaths_threshold, self.flowpaths_stop_at_bluespots)
                 if unresolved:
                     self.logger.warning("{} stream cells lie on a cycle that nothing flows into: no flow path".format(unresolved))
                 self.output_flowpaths.write_geojson_features(features_from_reaches(xy, offsets, reaches, transform, cell_width))
+            if self.want_hand:
+                self.logger.info("Calculating heights above the nearest drainage")
+                nodata = getattr(self.output_hand_raster, "nodata", None)
+                undrained = pipe.hand(self.hand_threshold, "filled", True, cell_width, -9999.0 if nodata is None else nodata)
+                if undrained:
+                    self.logger.info("{} cells reach no drainage before their flow path ends: no height".format(undrained))
+                if self.output_hand_raster is not None:
+                    pipe.download_hand_to(self.output_hand_raster)
+                if self.output_drain_distance_raster is not None:
+                    pipe.download_drain_distance_to(self.output_drain_distance_raster)
             self.logger.info("Done")
         finally:
             if own:

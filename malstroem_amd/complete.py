@@ -89,7 +89,7 @@ def parse_filter(filter):
 
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
                 finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
-                flowpaths=None, flowpaths_stop_at_bluespots=True, adaptations=None):
+                flowpaths=None, flowpaths_stop_at_bluespots=True, hand=None, adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -135,10 +135,18 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     (``flowpaths.features_from_reaches``), computed on the device from the resident rasters after the watersheds; with
     ``flowpaths_stop_at_bluespots`` (the default) a reach ends where it runs into a (filtered) bluespot.  The accumulated flow is
     computed for it even with ``accum=False`` (``accum.tif`` is written with ``accum`` only; the pour points stay where they are
-    without ``accum``).  The dict gains ``flowpaths``.  Not on row bands yet."""
-    if flowpaths is not None:
+    without ``accum``).  The dict gains ``flowpaths``.  Not on row bands yet.
+
+    ``hand`` (keyword only): the smallest number of upstream cells of a stream cell, as for ``flowpaths``.  Also writes ``hand.tif`` --
+    the height of every cell of the filled surface above the first stream cell or (filtered) bluespot on its flow path, nodata -9999
+    where the path meets neither -- and ``hand_dist.tif``, the distance in metres along the flow path to that cell (nodata -1);
+    the dict gains ``hand`` and ``hand_dist``.  With ``objects`` every object also gets ``hand_min`` (the lowest height above
+    drainage > 0 among its cells; null: none) and ``hand_dist_min`` (the shortest distance > 0).  The accumulated flow is computed
+    for it as for ``flowpaths``.  Not on row bands yet."""
+    if flowpaths is not None or hand is not None:
         from .flowpaths import check_threshold
-        flowpaths = check_threshold(flowpaths)
+        flowpaths = check_threshold(flowpaths) if flowpaths is not None else None
+        hand = check_threshold(hand) if hand is not None else None
     if (onset or not final_rasters) and not finalstate:
         raise ValueError("onset and final_rasters belong to the final state: pass finalstate=True")
     if comm is not None and comm.size > 1:
@@ -157,6 +165,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         if flowpaths is not None:
             raise NotImplementedError("flowpaths on row bands: a reach crosses the seams between the bands, and joining the chains of "
                                       "the bands there is not built yet; run it on one context")
+        if hand is not None:
+            raise NotImplementedError("hand on row bands: a flow path crosses the seams between the bands, and the walk over them is "
+                                      "not built yet; run it on one context")
         if objects is not None:
             raise NotImplementedError("objects on row bands: an object crosses the seams between the bands, and the zone raster of a "
                                       "band is not built yet; run it on one context")
@@ -197,13 +208,17 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         labeled_vector_writer = io.VectorWriter('GeoJSON', outvector, 'bluespots', None, None, crs) if vector else None
         watershed_vector_writer = io.VectorWriter('GeoJSON', outvector, 'watersheds', None, None, crs) if vector else None
         flowpaths_writer = io.VectorWriter('GeoJSON', outvector, 'flowpaths', None, None, crs) if flowpaths is not None else None
+        hand_path, hand_dist_path = os.path.join(outdir, 'hand.tif'), os.path.join(outdir, 'hand_dist.tif')
         BluespotTool(input_depths=dem_reader, input_flowdir=dem_reader, input_bluespot_filter_function=filter_function,
                      input_accum=None, input_dem=dem_reader, output_labeled_raster=labeled_writer, output_pourpoints=pourpoint_writer,
                      output_watersheds_raster=watershed_writer, pipeline=pipe, device=device,
                      output_labeled_vector=labeled_vector_writer, output_watersheds_vector=watershed_vector_writer,
                      output_flowlength_raster=io.RasterWriter(flowlength_path, tr, crs, -1) if flowlength else None,
                      output_flowpaths=flowpaths_writer, flowpaths_threshold=flowpaths, flowpaths_stop_at_bluespots=flowpaths_stop_at_bluespots,
-                     flowpaths_run_accum=not accum).process()
+                     flowpaths_run_accum=not accum,
+                     output_hand_raster=io.RasterWriter(hand_path, tr, crs, -9999.0) if hand is not None else None,
+                     output_drain_distance_raster=io.RasterWriter(hand_dist_path, tr, crs, -1) if hand is not None else None,
+                     hand_threshold=hand, hand_run_accum=not accum).process()
         nlabels = pipe.get_int("nlabels")
         # Process pourpoints: the walk runs on the resident flow directions and labels
         pourpoints_reader = io.VectorReader(outvector, pourpoint_writer.layername)
@@ -223,6 +238,12 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                 # (an object that covers no cell centre has no largest depth: null)
                 f["properties"].update(cells=int(zrec["cells"][k + 1]), bs_dmax=float(zrec["vmax"][k + 1]) if zrec["cells"][k + 1] else None,
                                        bs_wet_cells=int(zrec["pos"][k + 1]))
+            if hand is not None:
+                # (the two rasters are still resident: the stream walk writes no raster)
+                zh, zd = pipe.zone_stats("hand"), pipe.zone_stats("drain_distance")
+                for k, f in enumerate(object_features):
+                    f["properties"].update(hand_min=float(zh["vmin_pos"][k + 1]) if zh["pos"][k + 1] else None,
+                                           hand_dist_min=float(zd["vmin_pos"][k + 1]) if zd["pos"][k + 1] else None)
         if not finalstate:
             pipe.close()
         # Process rain events
@@ -237,6 +258,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
             res["flowlength"] = flowlength_path
         if flowpaths is not None:
             res["flowpaths"] = flowpaths_writer.filepath
+        if hand is not None:
+            res.update(hand=hand_path, hand_dist=hand_dist_path)
         if adaptations is not None:
             res.update(dem_adapted=adapted_path, adaptations=report_writer.filepath)
         if finalstate:

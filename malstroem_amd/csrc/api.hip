@@ -407,6 +407,28 @@ int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H,
     return download(out_dist, d_out, n * 4, s);
 }
 
+int mhip_hand_f32(const uint8_t *flowdir, const double *accum, const float *elev, const int32_t *labels, int64_t H, int64_t W, double threshold,
+                  double scale, float nodata, float *out_hand, float *out_dist, int64_t *undrained)
+{
+    MH_ARG(flowdir && accum && elev && out_hand && H >= 1 && W >= 1,
+           "hand_f32(flowdir, accum, elev, labels, H>=1, W>=1, threshold, scale, nodata, out_hand, out_dist, undrained)");
+    MH_TRY(hand_check(threshold, scale));
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    const size_t n = (size_t)(H * W);
+    DevBuf d_fd, d_a, d_z, d_l, d_h, d_d;
+    MH_TRY(upload(d_fd, flowdir, n, s));
+    MH_TRY(upload(d_a, accum, n * 8, s));
+    MH_TRY(upload(d_z, elev, n * 4, s));
+    if (labels) MH_TRY(upload(d_l, labels, n * 4, s));
+    MH_TRY(d_h.alloc(n * 4));
+    if (out_dist) MH_TRY(d_d.alloc(n * 4));
+    MH_TRY(hand_dev(d_fd.as<uint8_t>(), d_a.as<double>(), d_z.as<float>(), labels ? d_l.as<int32_t>() : nullptr, H, W, threshold, scale, nodata,
+                    d_h.as<float>(), out_dist ? d_d.as<float>() : nullptr, undrained, s));
+    if (out_dist) MH_HIP(hipMemcpyAsync(out_dist, d_d.p, n * 4, hipMemcpyDeviceToHost, s));
+    return download(out_hand, d_h, n * 4, s);
+}
+
 int mhip_burn_lines_f32(float *dem, int64_t H, int64_t W, int64_t nseg, const mhip_burn_segment *segments, int64_t nline,
                         const mhip_burn_line *lines, double nodata, mhip_burn_result *results)
 {

@@ -501,6 +501,16 @@ int wet_at_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t 
 bool flow_distance_scale_ok(double scale);      // finite and > 0
 int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int64_t W, double scale, int64_t nlab, float *d_out, mhip_index_record *d_rec,
                       int64_t *unresolved, hipStream_t s);
+// the perimeter jumps of the flow distance's engine on two node arrays of ntiles * 256 slots (`cur` written by a tile pass, `nxt`
+// scratch); d_open: two zeroable words.  Afterwards `cur` is the array the final pass reads.  Synchronises.  (hand.hip runs them too.)
+int fdist_jumps_dev(uint4 *&cur, uint4 *&nxt, int64_t W, int64_t ntc, int64_t ntiles, unsigned int *d_open, hipStream_t s);
+// hand.hip: height above the nearest drainage and the distance to it along the flow path.  A drainage cell:
+// d_acc >= threshold (float64; a NaN is none) or, with d_lab, a label != 0.  d_hand = elev[c] - elev[D(c)] (a NaN result is the
+// canonical quiet NaN), `nodata` for a cell whose walk ends without drainage; d_dist (optional) as flow_distance_dev's raster, -1
+// there.  Synchronises.  hand_check: the argument rules (MHIP_EINVAL; no device work): threshold finite and >= 1, scale finite and > 0.
+int hand_check(double threshold, double scale);
+int hand_dev(const uint8_t *d_fd, const double *d_acc, const float *d_elev, const int32_t *d_lab, int64_t H, int64_t W, double threshold, double scale,
+             float nodata, float *d_hand, float *d_dist, int64_t *undrained, hipStream_t s);
 // burn.hip: DEM adaptations.  burn_check: the argument rules of mhip_burn_lines_f32 on the host arrays (MHIP_EINVAL; no
 // device work).  burn_lines_dev: the checked lines into the float32 raster d_dem in place, the per-line records to `results` (host).
 // Synchronises.  nseg == 0 writes the records on the host and touches no device.
@@ -601,6 +611,42 @@ __device__ __forceinline__ int64_t ws_node_of(int32_t cell, uint32_t W, int ntc)
     const uint32_t r = (uint32_t)cell / W, c = (uint32_t)cell - r * W;
     const int slot = ws_perim_slot((int)(r & 63u), (int)(c & 63u));
     return slot < 0 ? -1 : (int64_t)((r >> 6) * (uint32_t)ntc + (c >> 6)) * 256 + slot;
+}
+
+// ---- the scratch word, the node and the step pair of the flow distance's engine (flowdist.hip; hand.hip) ----------------------
+constexpr int32_t FD_NONE = 0x7fffffff;              // unresolved
+constexpr int32_t FD_DONE = (int32_t)0x80000000;     // | the global index of the terminal; without it: an entry cell (>= 0)
+constexpr double FD_SQRT2 = 1.4142135623730951;
+// a step as a packed tile-local pair: orthogonal steps in the low, diagonal steps in the high 16 bits (a tile-local path has at
+// most 4095 steps and one more out of the tile: neither field ever carries into the other)
+__device__ __forceinline__ uint32_t fd_step(unsigned code) { return (code & 1u) ? 0x10000u : 1u; }
+// the exact pair and the terminal of a cell from its scratch word and, for a path that leaves its tile, the node of its entry cell;
+// false: unresolved (a cycle inside the tile, or a node still open after the jumps: a cycle across tiles)
+__device__ __forceinline__ bool fd_resolve(uint2 s, const uint4 *__restrict__ Nn, uint32_t W, int ntc, uint32_t &no, uint32_t &nd, int32_t &T)
+{
+    int32_t t = (int32_t)s.x;
+    no = s.y & 0xffffu;
+    nd = s.y >> 16;
+    if (t >= 0 && t != FD_NONE) {      // an entry cell: what its node has been resolved to
+        const int64_t node = ws_node_of(t, W, ntc);
+        uint4 m = make_uint4((uint32_t)FD_NONE, 0u, 0u, 0u);
+        if (node >= 0) m = Nn[node];
+        t = (int32_t)m.x;
+        no += m.y;
+        nd += m.z;
+    }
+    T = t & ~FD_DONE;      // (meaningless where the result is false)
+    return t < 0;          // FD_NONE and an entry cell are >= 0
+}
+__device__ __forceinline__ double fd_u(uint32_t no, uint32_t nd) { return __dadd_rn((double)no, __dmul_rn((double)nd, FD_SQRT2)); }
+template <int V> __device__ __forceinline__ void fd_load(const uint2 *__restrict__ S, int64_t i0, uint2 (&s)[V])
+{
+    if constexpr (V == 4) {
+        const uint4 a = *reinterpret_cast<const uint4 *>(S + i0), b = *reinterpret_cast<const uint4 *>(S + i0 + 2);
+        s[0] = make_uint2(a.x, a.y); s[1] = make_uint2(a.z, a.w); s[2] = make_uint2(b.x, b.y); s[3] = make_uint2(b.z, b.w);
+    } else {
+        s[0] = S[i0];
+    }
 }
 
 // open-addressing slot of `key` in an LDS table of TS (power of two) slots, -1 when the probe limit is hit (the caller

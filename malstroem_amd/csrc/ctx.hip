@@ -26,8 +26,20 @@ static void drop_flow_distance(mhip_ctx *c)
     c->fdist_rec.release();
 }
 
+// `which` was written: the result of mhip_ctx_hand goes if it was made from that raster (which < 0: whatever it was made from)
+static void drop_hand(mhip_ctx *c, int which)
+{
+    std::lock_guard<std::mutex> lk(c->hand_mu);
+    if (c->hand_undrained < 0) return;
+    if (!(which < 0 || which == MHIP_R_FLOWDIR || which == MHIP_R_ACCUM || which == c->hand_src || (which == MHIP_R_LABELS && c->hand_labels))) return;
+    c->hand_undrained = -1;      // (the call that fills the buffers has synchronised: nothing on the device still uses them)
+    c->hand_out.release();
+    c->hand_dist.release();
+}
+
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
 {
+    drop_hand(c, which);
     switch (which) {
     case MHIP_R_DEM:    // a new DEM invalidates everything derived from the previous one
         c->noflat_pending = false;      // (a surface nobody has asked for goes with have[NOFLAT])
@@ -434,7 +446,8 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
     else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels
     else if (k == "flow_distance_unresolved") *value = c->fdist_unresolved;   // -1: no result of mhip_ctx_flow_distance on the resident flow directions and labels
-    else if (k == "zones") *value = c->nzone;                        // -1: no zone raster of mhip_ctx_rasterize_zones
+    else if (k == "hand_undrained") *value = c->hand_undrained;      // -1: no result of mhip_ctx_hand on the resident rasters
+    else if (k == "zones") *value = c->nzone;                       // -1: no zone raster of mhip_ctx_rasterize_zones
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
     else {
@@ -642,6 +655,41 @@ int mhip_ctx_flow_distance_records(mhip_ctx *c, mhip_index_record *records)
     return ctx_fetch(c, c->fdist_rec, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
 }
 
+/* ---- height above the nearest drainage and the distance to it (hand.hip) ---------------------------------------------------------- */
+int mhip_ctx_hand(mhip_ctx *c, int32_t elev_source, double threshold, int32_t stop_at_labels, double scale, float nodata, int64_t *undrained)
+{
+    MH_ARG(c && undrained, "ctx_hand(ctx, elev_source, threshold, stop_at_labels, scale, nodata, undrained)");
+    MH_ARG(elev_source == MHIP_R_FILLED || elev_source == MHIP_R_DEM, "ctx_hand: the elevation source is MHIP_R_FILLED or MHIP_R_DEM");
+    MH_TRY(hand_check(threshold, scale));
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "hand on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_ACCUM] && c->have[elev_source], "ctx_hand needs the FLOWDIR and ACCUM rasters and the elevation source");
+    if (stop_at_labels) {
+        MH_ARG(c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_hand with stop_at_labels needs the LABELS raster");
+        MH_ARG(c->labels_filtered, "ctx_hand needs mhip_ctx_apply_keep after the LABEL run");
+    }
+    MH_HIP(hipSetDevice(c->device));
+    const int64_t n = c->H * c->W;
+    drop_hand(c, -1);
+    MH_TRY(c->hand_out.alloc(4 * (size_t)n));
+    MH_TRY(c->hand_dist.alloc(4 * (size_t)n));
+    int64_t u = 0;
+    MH_TRY(hand_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_ACCUM].as<double>(), c->r[elev_source].as<float>(),
+                    stop_at_labels ? c->r[MHIP_R_LABELS].as<int32_t>() : nullptr, c->H, c->W, threshold, scale, nodata, c->hand_out.as<float>(),
+                    c->hand_dist.as<float>(), &u, c->stream));      // (synchronises)
+    c->hand_src = elev_source;
+    c->hand_labels = stop_at_labels != 0;
+    c->hand_undrained = u;
+    *undrained = u;
+    return MHIP_OK;
+}
+
+int mhip_ctx_hand_rows(mhip_ctx *c, int32_t which, int64_t row0, int64_t nrows, float *dst)
+{
+    MH_ARG(c && dst && (which == 0 || which == 1) && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_hand_rows(ctx, which, row0, nrows, dst)");
+    MH_ARG(c->hand_undrained >= 0 && c->hand_out.p && c->hand_dist.p, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters");
+    return ctx_copy_rows(c, which ? c->hand_dist.p : c->hand_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+}
+
 /* ---- DEM adaptations: culvert and dike lines into the resident DEM (burn.hip) ---------------------------------------------------- */
 int mhip_ctx_burn_lines(mhip_ctx *c, int64_t nseg, const mhip_burn_segment *segments, int64_t nline, const mhip_burn_line *lines, double nodata,
                         mhip_burn_result *results)
@@ -700,6 +748,10 @@ int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
     case MHIP_ZSRC_FLOWDIST:
         MH_ARG(c->fdist_unresolved >= 0 && c->fdist_out.p, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels");
         src = c->fdist_out.as<float>();
+        break;
+    case MHIP_ZSRC_HAND: case MHIP_ZSRC_DRAINDIST:
+        MH_ARG(c->hand_undrained >= 0 && c->hand_out.p && c->hand_dist.p, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters");
+        src = source == MHIP_ZSRC_HAND ? c->hand_out.as<float>() : c->hand_dist.as<float>();
         break;
     default:
         MH_ARG(false, "ctx_zone_stats: the source is no float32 raster of the context");

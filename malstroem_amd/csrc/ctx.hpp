@@ -125,6 +125,14 @@ struct mhip_ctx {
     mh::DevBuf fdist_out, fdist_rec;
     std::atomic<int64_t> fdist_unresolved{-1};
     std::mutex fdist_mu;
+    // the two rasters (float32, H x W; no members of mhip_raster) of the last mhip_ctx_hand and its number of undrained cells; -1:
+    // none.  They live and die with FLOWDIR, ACCUM, the elevation raster `hand_src` and, where `hand_labels` says they were used,
+    // LABELS; handed back under the lock, as above
+    mh::DevBuf hand_out, hand_dist;
+    std::atomic<int64_t> hand_undrained{-1};
+    int hand_src = -1;
+    bool hand_labels = false;
+    std::mutex hand_mu;
     // the zone raster (int32, H x W; not a member of mhip_raster) of the last mhip_ctx_rasterize_zones and its number of zones; -1:
     // none.  It comes from outside: no write of a raster drops it
     mh::DevBuf zones;

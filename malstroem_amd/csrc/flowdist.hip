@@ -18,14 +18,7 @@ namespace mh {
 namespace {
 
 constexpr int WT = WS_TILE;
-constexpr int32_t FD_NONE = 0x7fffffff;              // unresolved
-constexpr int32_t FD_DONE = (int32_t)0x80000000;     // | the global index of the terminal; without it: an entry cell (>= 0)
-constexpr double FD_SQRT2 = 1.4142135623730951;
-constexpr int FD_HOPS = 5;
-
-// a step as a packed tile-local pair: orthogonal steps in the low, diagonal steps in the high 16 bits (a tile-local path has at
-// most 4095 steps and one more out of the tile: neither field ever carries into the other)
-__device__ __forceinline__ uint32_t fd_step(unsigned code) { return (code & 1u) ? 0x10000u : 1u; }
+constexpr int FD_HOPS = 5;      // (FD_NONE, FD_DONE, the step pair and the decoding of a scratch word: common.hpp, shared with hand.hip)
 
 // ---- tile pass ---------------------------------------------------------------------------------------------------------------
 // One workgroup per 64 x 64 tile; pull-only pointer doubling on 16-bit tile-local indices as in ws_tile_kernel, and every cell
@@ -185,37 +178,9 @@ __global__ __launch_bounds__(256) void fdist_jump_kernel(const uint4 *__restrict
 }
 
 // ---- final pass ------------------------------------------------------------------------------------------------------------------
-// the exact pair and the terminal of a cell from its scratch word and, for a path that leaves its tile, the node of its entry cell;
-// false: unresolved (a cycle inside the tile, or a node still open after the jumps: a cycle across tiles)
-__device__ __forceinline__ bool fd_resolve(uint2 s, const uint4 *__restrict__ Nn, uint32_t W, int ntc, uint32_t &no, uint32_t &nd, int32_t &T)
-{
-    int32_t t = (int32_t)s.x;
-    no = s.y & 0xffffu;
-    nd = s.y >> 16;
-    if (t >= 0 && t != FD_NONE) {      // an entry cell: what its node has been resolved to
-        const int64_t node = ws_node_of(t, W, ntc);
-        uint4 m = make_uint4((uint32_t)FD_NONE, 0u, 0u, 0u);
-        if (node >= 0) m = Nn[node];
-        t = (int32_t)m.x;
-        no += m.y;
-        nd += m.z;
-    }
-    T = t & ~FD_DONE;      // (meaningless where the result is false)
-    return t < 0;          // FD_NONE and an entry cell are >= 0
-}
-__device__ __forceinline__ double fd_u(uint32_t no, uint32_t nd) { return __dadd_rn((double)no, __dmul_rn((double)nd, FD_SQRT2)); }
+// (fd_resolve: the exact pair and the terminal of a cell from its scratch word and the node of its entry cell -- common.hpp)
 // u >= 0: doubles order as their bit patterns; + 1 keeps 0 for "no cell"
 __device__ __forceinline__ unsigned long long fd_key(double u) { return (unsigned long long)__double_as_longlong(u) + 1ull; }
-
-template <int V> __device__ __forceinline__ void fd_load(const uint2 *__restrict__ S, int64_t i0, uint2 (&s)[V])
-{
-    if constexpr (V == 4) {
-        const uint4 a = *reinterpret_cast<const uint4 *>(S + i0), b = *reinterpret_cast<const uint4 *>(S + i0 + 2);
-        s[0] = make_uint2(a.x, a.y); s[1] = make_uint2(a.z, a.w); s[2] = make_uint2(b.x, b.y); s[3] = make_uint2(b.z, b.w);
-    } else {
-        s[0] = S[i0];
-    }
-}
 
 // the raster alone: V cells a thread (V = 4: n is a multiple of four, 16-byte stores), 12 bytes a cell
 template <int V>
@@ -375,6 +340,25 @@ __global__ __launch_bounds__(256) void fdist_records_kernel(const unsigned long 
 
 bool flow_distance_scale_ok(double scale) { return std::isfinite(scale) && scale > 0.0; }
 
+int fdist_jumps_dev(uint4 *&cur, uint4 *&nxt, int64_t W, int64_t ntc, int64_t ntiles, unsigned int *d_open, hipStream_t s)
+{
+    constexpr int MAX_ROUNDS = 40;      // the watersheds' cap; nodes on a cycle across tiles are still open then
+    for (int round = 0; round < MAX_ROUNDS;) {
+        const int k = round == 0 ? 2 : 1;
+        MH_HIP(hipMemsetAsync(d_open, 0, 8, s));
+        for (int j = 0; j < k; ++j) {
+            hipLaunchKernelGGL(fdist_jump_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, cur, nxt, W, (int)ntc, ntiles * 256, d_open + j);
+            std::swap(cur, nxt);
+        }
+        unsigned int h[2] = {0, 0};
+        MH_HIP(hipMemcpyAsync(h, d_open, 8, hipMemcpyDeviceToHost, s));
+        MH_HIP(stream_sync(s));
+        round += k;
+        if (!h[k - 1]) break;
+    }
+    return MHIP_OK;
+}
+
 int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int64_t W, double scale, int64_t nlab, float *d_out, mhip_index_record *d_rec,
                       int64_t *unresolved, hipStream_t s)
 {
@@ -401,20 +385,7 @@ int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int6
     }
     hipLaunchKernelGGL(fdist_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, d_fd, d_lab, S.as<uint2>(), H, W, (int)ntc, NA.as<uint4>());
     uint4 *cur = NA.as<uint4>(), *nxt = NB.as<uint4>();
-    constexpr int MAX_ROUNDS = 40;      // the watersheds' cap; nodes on a cycle across tiles are still open then
-    for (int round = 0; round < MAX_ROUNDS;) {
-        const int k = round == 0 ? 2 : 1;
-        MH_HIP(hipMemsetAsync(d_open, 0, 8, s));
-        for (int j = 0; j < k; ++j) {
-            hipLaunchKernelGGL(fdist_jump_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, cur, nxt, W, (int)ntc, nnodes, d_open + j);
-            std::swap(cur, nxt);
-        }
-        unsigned int h[2] = {0, 0};
-        MH_HIP(hipMemcpyAsync(h, d_open, 8, hipMemcpyDeviceToHost, s));
-        MH_HIP(stream_sync(s));
-        round += k;
-        if (!h[k - 1]) break;
-    }
+    MH_TRY(fdist_jumps_dev(cur, nxt, W, ntc, ntiles, d_open, s));
     const bool vec = W % 4 == 0 && ((uintptr_t)d_out | (uintptr_t)S.p) % 16 == 0;
     const int V = vec ? 4 : 1;
     const dim3 grid((unsigned)cdiv(cdiv(n, V), 256)), block(256);

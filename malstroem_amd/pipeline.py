@@ -216,6 +216,55 @@ class HydroPipeline(CtxHandle):
         """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
         write_windows(writer, self.shape, np.float32, self.download_flow_distance_rows, max_rows)
 
+    # ---- height above the nearest drainage and the distance to it (DESIGN.md 16) ------------------------------
+    HAND_SOURCES = {"filled": _lib.R_FILLED, "dem": _lib.R_DEM}
+
+    def hand(self, threshold, source="filled", stop_at_bluespots=True, cellsize=1.0, nodata=-9999.0):
+        """Height above the nearest drainage on the resident flow directions, accumulated flow and elevations (``source``:
+        ``"filled"`` or ``"dem"``): per cell its elevation minus the elevation of the first cell on its flow path that has at least
+        ``threshold`` cells upstream or, with ``stop_at_bluespots``, lies in a (filtered or uploaded) bluespot.  Returns the number of
+        undrained cells -- their path ends at the edge, in a sink or on a cycle before it meets drainage; they hold ``nodata``, and -1
+        in the distance.  Both rasters stay on the device for ``download_hand`` / ``download_drain_distance`` (and their ``_rows`` /
+        ``_to`` forms) until one of the rasters they were made from is written again."""
+        from .algorithms.flow import check_cellsize, check_hand_nodata
+        from .flowpaths import check_threshold
+        if source not in self.HAND_SOURCES:
+            raise ValueError("source must be one of %s, got %r" % (sorted(self.HAND_SOURCES), source))
+        thr, scale, nd = check_threshold(threshold), check_cellsize(cellsize), check_hand_nodata(nodata)
+        undrained = ctypes.c_int64(0)
+        _lib.call("mhip_ctx_hand", self._ctx, ctypes.c_int32(self.HAND_SOURCES[source]), ctypes.c_double(thr),
+                  ctypes.c_int32(1 if stop_at_bluespots else 0), ctypes.c_double(scale), ctypes.c_float(nd), ctypes.byref(undrained))
+        return undrained.value
+
+    def _hand_rows(self, which, row0, nrows):
+        if self.get_int("hand_undrained") < 0:
+            raise ValueError("hand() has not been run on the resident rasters")
+        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
+        _lib.call("mhip_ctx_hand_rows", self._ctx, ctypes.c_int32(which), _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
+        return out
+
+    def download_hand_rows(self, row0, nrows):
+        return self._hand_rows(0, row0, nrows)
+
+    def download_hand(self):
+        """The height raster of the last ``hand`` (float32); ``ValueError`` once a raster it was made from is gone."""
+        return self._hand_rows(0, 0, self.shape[0])
+
+    def download_hand_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.float32, self.download_hand_rows, max_rows)
+
+    def download_drain_distance_rows(self, row0, nrows):
+        return self._hand_rows(1, row0, nrows)
+
+    def download_drain_distance(self):
+        """The distance raster of the last ``hand`` (float32); ``ValueError`` once a raster it was made from is gone."""
+        return self._hand_rows(1, 0, self.shape[0])
+
+    def download_drain_distance_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.float32, self.download_drain_distance_rows, max_rows)
+
     # ---- DEM adaptations: culvert and dike lines into the resident DEM (adaptations.py; DESIGN.md 12) -----
     def burn_lines(self, lines, segments, nodata=np.nan):
         """Burn ``lines`` / ``segments`` (``adaptations.lines_from_features``) into the resident DEM in place: all lower lines, then all
@@ -230,7 +279,8 @@ class HydroPipeline(CtxHandle):
 
     # ---- object exposure: polygons to a zone raster, a resident raster reduced per zone (objects.py) -----
     ZONE_SOURCES = {"dem": _lib.R_DEM, "filled": _lib.R_FILLED, "depths": _lib.R_DEPTHS, "finaldepths": _lib.R_FINALDEPTHS,
-                    "wet_at": _lib.ZSRC_WETAT, "flow_distance": _lib.ZSRC_FLOWDIST}
+                    "wet_at": _lib.ZSRC_WETAT, "flow_distance": _lib.ZSRC_FLOWDIST, "hand": _lib.ZSRC_HAND,
+                    "drain_distance": _lib.ZSRC_DRAINDIST}
 
     def rasterize_zones(self, xy, ring_offsets, ring_zone, nzone, grow=0):
         """Rasterize polygons (``objects.rings_from_features``) at the pipeline's shape; the zone raster stays on the device for
@@ -243,8 +293,10 @@ class HydroPipeline(CtxHandle):
 
     def zone_stats(self, source):
         """``nzone + 1`` records (``_lib.ZONE_DTYPE``) of a resident float32 raster over the zones: ``source`` is ``"dem"``,
-        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"`` or ``"flow_distance"``.  ``ValueError`` without zones or when the
-        source has not been computed."""
+        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"``, ``"flow_distance"``, ``"hand"`` or ``"drain_distance"``.  ``ValueError`` without zones or when the
+        source has not been computed.  (``"hand"``: ``vmin_pos`` is the lowest positive height above drainage of an object's cells.
+        The negative nodata of its undrained cells is never the largest value of a zone that has one drained cell, and is never
+        positive: it shows in ``vmax`` only where no cell of the zone is drained.)"""
         if source not in self.ZONE_SOURCES:
             raise ValueError("source must be one of %s, got %r" % (sorted(self.ZONE_SOURCES), source))
         nzone = self.get_int("zones")
