@@ -65,6 +65,10 @@ typedef struct { double vmax, vmin_pos; int64_t cells, pos; } mhip_zone_record;
 /* ... and the two rasters of the last mhip_ctx_hand: the height above the nearest drainage, the distance to it */
 #define MHIP_ZSRC_HAND 102
 #define MHIP_ZSRC_DRAINDIST 103
+/* ... and the depth raster of the last mhip_ctx_inundate */
+#define MHIP_ZSRC_INUNDATION 104      /* mhip_ctx_zone_stats */
+/* a source of mhip_ctx_polygonize that is no member of enum mhip_raster: the catchment raster of the last mhip_ctx_reach_catchments */
+#define MHIP_PSRC_REACHCATCH 110      /* mhip_ctx_polygonize */
 
 /* ---- library / device ------------------------------------------------------------------------- */
 const char *mhip_last_error(void);
@@ -559,7 +563,7 @@ int mhip_ctx_burn_lines(mhip_ctx *ctx, int64_t nseg, const mhip_burn_segment *se
  * of the context (no member of enum mhip_raster).  The zones come from outside: no write of a raster drops them, a new rasterize
  * replaces them.  zones_rows copies rows [row0, row0 + nrows) of the raster.  zone_stats: mhip_zone_stats_f32 of a resident
  * float32 raster over the zones, records[nzone + 1]; source: MHIP_R_DEM, MHIP_R_FILLED, MHIP_R_DEPTHS, MHIP_R_FINALDEPTHS,
- * MHIP_ZSRC_WETAT, MHIP_ZSRC_FLOWDIST, MHIP_ZSRC_HAND or MHIP_ZSRC_DRAINDIST; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
+ * MHIP_ZSRC_WETAT, MHIP_ZSRC_FLOWDIST, MHIP_ZSRC_HAND, MHIP_ZSRC_DRAINDIST or MHIP_ZSRC_INUNDATION; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
  * without zones.  mhip_ctx_get_i64 "zones": nzone of the raster held, -1: none. */
 int mhip_ctx_rasterize_zones(mhip_ctx *ctx, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
                              const int32_t *ring_zone, int64_t nzone, int32_t grow);
@@ -582,7 +586,7 @@ int mhip_ctx_zone_stats(mhip_ctx *ctx, int32_t source, mhip_zone_record *records
  * run, and holds 8 B a vertex + 12 B a ring of device memory until it is freed.  MHIP_EINVAL: a negative label; MHIP_ELIMIT: more than 2**32 - 1 edges.
  * An all-zero raster gives 0 rings and asks for no device.
  * On a context: source MHIP_R_LABELS (the filtered labels, as mhip_ctx_stats wants them) or MHIP_R_WATERSHEDS of an undivided context (a
- * row band is refused); a source that is not valid is MHIP_EINVAL as from its own getter.  No raster leaves the device. */
+ * row band is refused), or MHIP_PSRC_REACHCATCH (the catchment raster of the last mhip_ctx_reach_catchments, below); a source that is not valid is MHIP_EINVAL as from its own getter.  No raster leaves the device. */
 typedef struct mhip_polygons mhip_polygons;
 int mhip_polygonize_i32(const int32_t *labels, int64_t H, int64_t W, mhip_polygons **out);
 int mhip_ctx_polygonize(mhip_ctx *ctx, int32_t source, mhip_polygons **out);
@@ -625,6 +629,37 @@ int mhip_ctx_flowpaths(mhip_ctx *ctx, double threshold, int32_t stop_at_labels, 
 int mhip_flowpaths_sizes(const mhip_flowpaths *p, int64_t *nreach, int64_t *nvert, int64_t *unresolved);
 int mhip_flowpaths_fetch(const mhip_flowpaths *p, int32_t *xy, int64_t *reach_offsets, mhip_reach_record *records);
 void mhip_flowpaths_free(mhip_flowpaths *p);
+
+/* Reach catchments and flood depths from a stage per reach (ours; the definition is tests/_reachcatch.py).  The inputs
+ * are those of mhip_flowpaths_f64.  rc(c), the reach of a stream cell: k + 1 when c is one of the cells c0 .. ck of reach k (the
+ * appended e is no cell of the reach), 0 for every other cell -- no stream cell, or a stream cell on a cycle of the mask that nothing
+ * flows into.  out_catch[H][W] int32 = rc(D(c)), D(c) mhip_hand_f32's with the same threshold and labels; 0 where c is undrained.  One
+ * threshold and one label raster make the two masks agree: a drainage cell that is no stream cell is labelled, so a cell that drains
+ * into a bluespot holds 0.  *out_reaches: an ordinary mhip_flowpaths whose arrays are bit for bit those of mhip_flowpaths_f64 with the
+ * same arguments (sizes, fetch, free as above).  assigned (optional): the cells with out_catch > 0.  An empty mask gives 0 reaches and
+ * an all-zero raster.  MHIP_EINVAL as mhip_flowpaths_f64; MHIP_ELIMIT: that call's, and H * W >= 2**31 - 2 cells.
+ * mhip_inundate_f32: hand[n], catch_[n] (values in [0, nreach], anything else is MHIP_EINVAL), stage[nreach + 1] float32 (stage[0] is
+ * ignored), out_depth[n].  With k = catch_[c]: out_depth[c] = stage[k] - hand[c] as one float32 subtraction when k > 0, hand[c] does
+ * not hold the bit pattern of nodata, and stage[k] > hand[c] (a NaN on either side compares false); +0.0 otherwise.  No stage value is
+ * an error.  records (optional, nreach + 1): mhip_zone_stats_f32 of out_depth over catch_ -- cells the size of the local catchment,
+ * pos its wet cells, vmax the deepest, vmin_pos the shallowest positive depth; W as there (0: a flat array).
+ * On an undivided context (a row band is refused): reach_catchments on the resident MHIP_R_FLOWDIR and MHIP_R_ACCUM, with
+ * stop_at_labels on the filtered or uploaded MHIP_R_LABELS by the rules of mhip_ctx_hand.  The catchment raster stays in a buffer of
+ * the context (no member of enum mhip_raster) until FLOWDIR, ACCUM or -- when they were used -- LABELS are written again;
+ * reach_catchments_rows copies rows [row0, row0 + nrows); mhip_ctx_polygonize takes it as MHIP_PSRC_REACHCATCH.  mhip_ctx_inundate is
+ * MHIP_EINVAL unless a result of mhip_ctx_hand and one of mhip_ctx_reach_catchments are held, both were made with the same threshold
+ * and the same stop_at_labels, and nreach is the catchments' count; it uses the nodata of the hand call.  The depth raster stays in a
+ * buffer of the context until the catchments or the hand result go, or either call is made again; inundation_rows copies rows of it,
+ * mhip_ctx_zone_stats takes it as MHIP_ZSRC_INUNDATION.  mhip_ctx_get_i64 "reach_catchments": nreach of the result held, -1: none;
+ * "inundation": 1, -1: none. */
+int mhip_reach_catchments_i32(const uint8_t *flowdir, const double *accum, const int32_t *labels_or_NULL, int64_t H, int64_t W,
+                              double threshold, int32_t *out_catch, mhip_flowpaths **out_reaches, int64_t *assigned_or_NULL);
+int mhip_inundate_f32(const float *hand, const int32_t *catch_, int64_t n, int64_t W, int64_t nreach, const float *stage,
+                      float nodata, float *out_depth, mhip_zone_record *records_or_NULL);
+int mhip_ctx_reach_catchments(mhip_ctx *ctx, double threshold, int32_t stop_at_labels, mhip_flowpaths **out_reaches, int64_t *assigned);
+int mhip_ctx_reach_catchments_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, int32_t *dst);
+int mhip_ctx_inundate(mhip_ctx *ctx, int64_t nreach, const float *stage, mhip_zone_record *records_or_NULL);
+int mhip_ctx_inundation_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
 
 #ifdef __cplusplus
 }

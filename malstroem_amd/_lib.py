@@ -26,7 +26,8 @@ BURN_RESULT_DTYPE = np.dtype([("z0", "<f8"), ("z1", "<f8"), ("cells", "<i8"), ("
 
 # object exposure (objects.py): mhip_zone_record; sources of mhip_ctx_zone_stats that are no member of mhip_raster
 ZONE_DTYPE = np.dtype([("vmax", "<f8"), ("vmin_pos", "<f8"), ("cells", "<i8"), ("pos", "<i8")])
-ZSRC_WETAT, ZSRC_FLOWDIST, ZSRC_HAND, ZSRC_DRAINDIST = 100, 101, 102, 103
+ZSRC_WETAT, ZSRC_FLOWDIST, ZSRC_HAND, ZSRC_DRAINDIST, ZSRC_INUNDATION = 100, 101, 102, 103, 104
+PSRC_REACHCATCH = 110      # a source of mhip_ctx_polygonize that is no member of mhip_raster
 
 # flow paths (flowpaths.py): mhip_reach_record; the end kinds of a reach
 REACH_DTYPE = np.dtype([("first_cell", "<i8"), ("last_cell", "<i8"), ("end_cell", "<i8"), ("up_cells", "<f8"), ("down_cells", "<f8"),
@@ -71,6 +72,8 @@ SYMBOLS = [
     "mhip_ctx_final_depths", "mhip_label_wet_at_f32", "mhip_ctx_wet_at", "mhip_ctx_wet_at_rows",
     "mhip_flow_distance", "mhip_ctx_flow_distance", "mhip_ctx_flow_distance_rows", "mhip_ctx_flow_distance_records",
     "mhip_hand_f32", "mhip_ctx_hand", "mhip_ctx_hand_rows",
+    "mhip_reach_catchments_i32", "mhip_inundate_f32", "mhip_ctx_reach_catchments", "mhip_ctx_reach_catchments_rows", "mhip_ctx_inundate",
+    "mhip_ctx_inundation_rows",
     "mhip_burn_lines_f32", "mhip_ctx_burn_lines",
     "mhip_rasterize_zones_i32", "mhip_zone_stats_f32", "mhip_ctx_rasterize_zones", "mhip_ctx_zones_rows", "mhip_ctx_zone_stats",
     "mhip_polygonize_i32", "mhip_ctx_polygonize", "mhip_polygons_sizes", "mhip_polygons_fetch", "mhip_polygons_free",

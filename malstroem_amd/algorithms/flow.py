@@ -261,3 +261,17 @@ def flow_paths(flowdir, accum, threshold, labelled=None):
     (ours: the reference has no counterpart)."""
     from ..flowpaths import extract
     return extract(flowdir, accum, threshold, labelled)
+
+
+def reach_catchments(flowdir, accum, threshold, labelled=None):
+    """The reaches of ``flow_paths`` and, per cell, the reach its flow path drains to:
+    ``(catch, xy, reach_offsets, records, unresolved, assigned)`` -- ``flowpaths.reach_catchments`` (ours)."""
+    from ..flowpaths import reach_catchments as impl
+    return impl(flowdir, accum, threshold, labelled)
+
+
+def inundate(hand, catchments, stage, nodata=-9999.0, records=False):
+    """Flood depths from a stage per reach over a ``hand`` raster and its reach catchments -- ``flowpaths.inundate`` (ours;
+    DESIGN.md 17)."""
+    from ..flowpaths import inundate as impl
+    return impl(hand, catchments, stage, nodata, records)

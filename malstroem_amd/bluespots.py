@@ -10,7 +10,7 @@ import logging
 import numpy as np
 
 from .algorithms import speedups
-from .pipeline import HydroPipeline
+from .pipeline import HydroPipeline, write_windows
 from .flowpaths import check_threshold, features_from_reaches
 from .vector import features_from_rings, transform_cell_to_world  # noqa: F401  (transform_cell_to_world lives in vector.py, as in the reference)
 
@@ -109,6 +109,13 @@ class BluespotTool(object):
     lies in a (filtered) bluespot (nodata: the writer's, -9999 without one), and for the distance in metres along the flow path to
     that cell (-1 where there is none).  They are computed after the pour points are taken, from the resident rasters, and streamed
     in row windows.  ``hand_run_accum``: as ``flowpaths_run_accum``.  A tool that reads its inputs itself needs ``input_dem`` for them.
+
+    ``output_reach_catchments_raster`` / ``output_reach_catchments_vector`` (no reference counterpart): a raster writer
+    for the local catchment of every reach -- per cell ``reach_id + 1`` of the reach of the ``flowpaths`` layer that its flow path
+    drains to, 0 where it drains to none -- and a vector writer for the outlines of those catchments, one ``Polygon`` per ring with
+    the ``reach_id`` that ``features_from_reaches`` gives its reach.  They use ``flowpaths_threshold`` and
+    ``flowpaths_stop_at_bluespots``; when either is set, the ``flowpaths`` layer comes from the same call and its features gain
+    ``local_cells`` / ``local_area``.  The catchments stay on the pipeline for ``HydroPipeline.inundate``.
     """
 
     def __init__(self, input_depths, input_flowdir, input_bluespot_filter_function,
@@ -116,7 +123,7 @@ class BluespotTool(object):
                  input_accum=None, input_dem=None, output_labeled_vector=None, output_watersheds_vector=None,
                  pipeline=None, device=0, output_flowlength_raster=None, output_flowpaths=None, flowpaths_threshold=None,
                  flowpaths_stop_at_bluespots=True, flowpaths_run_accum=False, output_hand_raster=None, output_drain_distance_raster=None,
-                 hand_threshold=None, hand_run_accum=False):
+                 hand_threshold=None, hand_run_accum=False, output_reach_catchments_raster=None, output_reach_catchments_vector=None):
         self.input_depths = input_depths
         self.input_flowdir = input_flowdir
         self.input_bluespot_filter_function = input_bluespot_filter_function
@@ -133,7 +140,10 @@ class BluespotTool(object):
         self.output_flowpaths = output_flowpaths
         self.flowpaths_stop_at_bluespots = flowpaths_stop_at_bluespots
         self.flowpaths_run_accum = flowpaths_run_accum
-        if output_flowpaths is not None:
+        self.output_reach_catchments_raster = output_reach_catchments_raster
+        self.output_reach_catchments_vector = output_reach_catchments_vector
+        self.want_catchments = output_reach_catchments_raster is not None or output_reach_catchments_vector is not None
+        if output_flowpaths is not None or self.want_catchments:
             self.flowpaths_threshold = check_threshold(flowpaths_threshold)
         self.output_hand_raster = output_hand_raster
         self.output_drain_distance_raster = output_drain_distance_raster
@@ -204,11 +214,38 @@ class BluespotTool(object):
                     feature['properties'].update(wshed_lfp=float(lfp['value']), lfp_row=int(lfp['row']), lfp_col=int(lfp['col']))
             self.output_pourpoints.write_geojson_features(dict(type="FeatureCollection", features=pour_points))
             # the accumulated flow for the flow paths and the heights above drainage, once, where the pipeline holds none yet
-            if ((self.output_flowpaths is not None and (self.flowpaths_run_accum or (own and not self.input_accum))) or
+            if (((self.output_flowpaths is not None or self.want_catchments) and (self.flowpaths_run_accum or (own and not self.input_accum))) or
                     (self.want_hand and (self.hand_run_accum or (own and not self.input_accum)))):
                 self.logger.info("Calculating flow accumulation")
                 pipe.run("accum")
-            if self.output_flowpaths is not None:
+            if self.want_catchments:
+                self.logger.info("Extracting flow paths and their local catchments")
+                xy, offsets, reaches, unresolved, assigned = pipe.reach_catchments(self.flowpaths_threshold, self.flowpaths_stop_at_bluespots)
+                if unresolved:
+                    self.logger.warning("{} stream cells lie on a cycle that nothing flows into: no flow path".format(unresolved))
+                self.logger.info("{} cells drain to one of {} reaches".format(assigned, reaches.size))
+                local = np.zeros(reaches.size + 1, dtype=np.int64)      # the cells per catchment, counted window by window
+
+                def counted_rows(row0, nrows):
+                    rows = pipe.download_reach_catchments_rows(row0, nrows)
+                    local[:] += np.bincount(rows.ravel(), minlength=local.size)
+                    return rows
+                if self.output_reach_catchments_raster is not None:
+                    write_windows(self.output_reach_catchments_raster, pipe.shape, np.int32, counted_rows, 4096)
+                else:
+                    for row0 in range(0, pipe.shape[0], 4096):
+                        counted_rows(row0, min(4096, pipe.shape[0] - row0))
+                if self.output_flowpaths is not None:
+                    self.output_flowpaths.write_geojson_features(features_from_reaches(xy, offsets, reaches, transform, cell_width,
+                                                                                       local_cells=local[1:]))
+                if self.output_reach_catchments_vector is not None:
+                    self.logger.info("Vectorizing the local catchments")
+                    features = features_from_rings(*pipe.polygonize("reach_catchments"), transform, 'reach_id')
+                    for f in features:      # (the raster holds reach_id + 1: 0 is its background)
+                        f['properties']['reach_id'] -= 1
+                        f['id'] = f['properties']['reach_id']
+                    self.output_reach_catchments_vector.write_geojson_features(features)
+            elif self.output_flowpaths is not None:
                 self.logger.info("Extracting flow paths")
                 xy, offsets, reaches, unresolved = pipe.flow_paths(self.flowpaths_threshold, self.flowpaths_stop_at_bluespots)
                 if unresolved:

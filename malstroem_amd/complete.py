@@ -89,7 +89,8 @@ def parse_filter(filter):
 
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
                 finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
-                flowpaths=None, flowpaths_stop_at_bluespots=True, hand=None, adaptations=None):
+                flowpaths=None, flowpaths_stop_at_bluespots=True, hand=None, reach_catchments=False, inundation=None,
+                adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -142,7 +143,36 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     where the path meets neither -- and ``hand_dist.tif``, the distance in metres along the flow path to that cell (nodata -1);
     the dict gains ``hand`` and ``hand_dist``.  With ``objects`` every object also gets ``hand_min`` (the lowest height above
     drainage > 0 among its cells; null: none) and ``hand_dist_min`` (the shortest distance > 0).  The accumulated flow is computed
-    for it as for ``flowpaths``.  Not on row bands yet."""
+    for it as for ``flowpaths``.  Not on row bands yet.
+
+    ``reach_catchments`` (keyword only; needs ``flowpaths``): also writes ``reach_catchments.tif`` (int32, nodata 0) -- per cell
+    ``reach_id + 1`` of the reach of the ``flowpaths`` layer that its flow path drains to, the local catchment of that line; 0 where
+    the path meets no stream cell or runs into a bluespot first -- and, with ``vector``, the layer ``reach_catchments``: the outlines
+    of those catchments with ``reach_id``.  The features of ``flowpaths`` gain ``local_cells`` / ``local_area``.  The dict gains
+    ``reach_catchments`` (and ``reach_catchments_vector``).  Not on row bands yet.
+
+    ``inundation`` (keyword only): a water level above the stream bed in metres, or a list of them, applied to every reach; needs
+    ``reach_catchments=True``, ``hand == flowpaths`` and ``flowpaths_stop_at_bluespots=True``, so that the heights and the catchments
+    speak of the same drainage cells.  Writes ``inundation_<cm>.tif`` per level (the level in whole centimetres): the depth
+    ``level - hand`` in the cells that lie lower above their reach than the level, 0 elsewhere.  The dict gains ``inundation``, a dict
+    of the paths by centimetres.  Not on row bands yet."""
+    if reach_catchments and flowpaths is None:
+        raise ValueError("reach_catchments needs flowpaths: the threshold of the reaches whose catchments are wanted")
+    stages = []
+    if inundation is not None:
+        levels = list(inundation) if isinstance(inundation, (list, tuple, np.ndarray)) else [inundation]
+        for v in levels:
+            if isinstance(v, (str, bytes, bool)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v <= 0:
+                raise ValueError("inundation must be a level in metres, finite and > 0, or a list of them, got %r" % (inundation,))
+            stages.append((int(round(float(v) * 100.0)), float(v)))
+        if not stages or len({cm for cm, _ in stages}) != len(stages) or min(cm for cm, _ in stages) < 1:
+            raise ValueError("inundation: the levels must differ by whole centimetres and be at least one, got %r" % (inundation,))
+        if not reach_catchments:
+            raise ValueError("inundation needs reach_catchments=True")
+        if hand is None or float(hand) != float(flowpaths):
+            raise ValueError("inundation needs hand == flowpaths: one threshold for the heights and for the catchments")
+        if not flowpaths_stop_at_bluespots:
+            raise ValueError("inundation needs flowpaths_stop_at_bluespots=True: hand stops at the bluespots")
     if flowpaths is not None or hand is not None:
         from .flowpaths import check_threshold
         flowpaths = check_threshold(flowpaths) if flowpaths is not None else None
@@ -162,6 +192,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         if adaptations is not None:
             raise NotImplementedError("adaptations on row bands: a line crosses the seams between the bands, and its levels hang on "
                                       "both of its ends, which is not built yet; run it on one context")
+        if reach_catchments or inundation is not None:
+            raise NotImplementedError("reach_catchments and inundation on row bands: a flow path crosses the seams between the bands, "
+                                      "and the walk over them is not built yet; run it on one context")
         if flowpaths is not None:
             raise NotImplementedError("flowpaths on row bands: a reach crosses the seams between the bands, and joining the chains of "
                                       "the bands there is not built yet; run it on one context")
@@ -209,6 +242,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         watershed_vector_writer = io.VectorWriter('GeoJSON', outvector, 'watersheds', None, None, crs) if vector else None
         flowpaths_writer = io.VectorWriter('GeoJSON', outvector, 'flowpaths', None, None, crs) if flowpaths is not None else None
         hand_path, hand_dist_path = os.path.join(outdir, 'hand.tif'), os.path.join(outdir, 'hand_dist.tif')
+        catch_path = os.path.join(outdir, 'reach_catchments.tif')
+        catch_vector_writer = io.VectorWriter('GeoJSON', outvector, 'reach_catchments', None, None, crs) if reach_catchments and vector else None
         BluespotTool(input_depths=dem_reader, input_flowdir=dem_reader, input_bluespot_filter_function=filter_function,
                      input_accum=None, input_dem=dem_reader, output_labeled_raster=labeled_writer, output_pourpoints=pourpoint_writer,
                      output_watersheds_raster=watershed_writer, pipeline=pipe, device=device,
@@ -218,7 +253,18 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                      flowpaths_run_accum=not accum,
                      output_hand_raster=io.RasterWriter(hand_path, tr, crs, -9999.0) if hand is not None else None,
                      output_drain_distance_raster=io.RasterWriter(hand_dist_path, tr, crs, -1) if hand is not None else None,
-                     hand_threshold=hand, hand_run_accum=not accum).process()
+                     hand_threshold=hand, hand_run_accum=not accum,
+                     output_reach_catchments_raster=io.RasterWriter(catch_path, tr, crs, 0) if reach_catchments else None,
+                     output_reach_catchments_vector=catch_vector_writer).process()
+        inundation_paths = {}
+        if stages:
+            # (the heights and the catchments are resident, made with one threshold at the bluespots: nothing has been written since)
+            nreach = pipe.get_int("reach_catchments")
+            for cm, level in stages:
+                logger.info("Calculating the flood depths of a stream rise of {} cm".format(cm))
+                pipe.inundate(np.full(nreach + 1, level, dtype=np.float32))
+                inundation_paths[cm] = os.path.join(outdir, 'inundation_{}.tif'.format(cm))
+                pipe.download_inundation_to(io.RasterWriter(inundation_paths[cm], tr, crs))
         nlabels = pipe.get_int("nlabels")
         # Process pourpoints: the walk runs on the resident flow directions and labels
         pourpoints_reader = io.VectorReader(outvector, pourpoint_writer.layername)
@@ -260,6 +306,12 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
             res["flowpaths"] = flowpaths_writer.filepath
         if hand is not None:
             res.update(hand=hand_path, hand_dist=hand_dist_path)
+        if reach_catchments:
+            res["reach_catchments"] = catch_path
+            if vector:
+                res["reach_catchments_vector"] = catch_vector_writer.filepath
+        if stages:
+            res["inundation"] = inundation_paths
         if adaptations is not None:
             res.update(dem_adapted=adapted_path, adaptations=report_writer.filepath)
         if finalstate:

@@ -1,6 +1,6 @@
 // api.hip -- the host-raster entry points of libmalstroem_hip.so (declared in include/malstroem_hip.h): upload -> stage -> download,
 // one per malstroem.algorithms stage function, over the device-pointer stage implementations (fill.hip, d8.hip, accum.hip, ccl.hip,
-// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, zones.hip, polygonize.hip, flowpaths.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
+// label_ops.hip, hyps.hip, watershed.hip, flowdist.hip, burn.hip, zones.hip, polygonize.hip, flowpaths.hip, reachcatch.hip, trace.hip).  They keep no state; the device-resident pipeline is ctx.hip.
 #include <new>
 #include <vector>
 
@@ -568,6 +568,56 @@ void mhip_flowpaths_free(mhip_flowpaths *p)
 {
     if (p && p->device >= 0) (void)hipSetDevice(p->device);
     delete p;
+}
+
+int mhip_reach_catchments_i32(const uint8_t *flowdir, const double *accum, const int32_t *labels, int64_t H, int64_t W, double threshold,
+                              int32_t *out_catch, mhip_flowpaths **out_reaches, int64_t *assigned)
+{
+    MH_ARG(flowdir && accum && out_catch && out_reaches, "reach_catchments_i32(flowdir, accum, labels, H, W, threshold, out_catch, out_reaches, assigned)");
+    MH_TRY(flowpaths_check(H, W, threshold));
+    MH_TRY(require_device());
+    mhip_flowpaths *p = new (std::nothrow) mhip_flowpaths();
+    if (!p) {
+        set_error("reach_catchments: out of host memory");
+        return MHIP_EHIP;
+    }
+    const size_t n = (size_t)(H * W);
+    hipStream_t s = 0;
+    DevBuf d_fd, d_acc, d_lab, d_catch;
+    int rc = hipGetDevice(&p->device) == hipSuccess ? MHIP_OK : MHIP_EHIP;
+    if (rc == MHIP_OK) rc = upload(d_fd, flowdir, n, s);
+    if (rc == MHIP_OK) rc = upload(d_acc, accum, 8 * n, s);
+    if (rc == MHIP_OK && labels) rc = upload(d_lab, labels, 4 * n, s);
+    if (rc == MHIP_OK) rc = d_catch.alloc(4 * n);
+    if (rc == MHIP_OK)
+        rc = reach_catchments_dev(d_fd.as<uint8_t>(), d_acc.as<double>(), labels ? d_lab.as<int32_t>() : nullptr, H, W, threshold, d_catch.as<int32_t>(), p,
+                                  assigned, s);
+    if (rc == MHIP_OK) rc = download(out_catch, d_catch, 4 * n, s);
+    if (rc != MHIP_OK) {
+        delete p;
+        return rc;
+    }
+    *out_reaches = p;
+    return MHIP_OK;
+}
+
+int mhip_inundate_f32(const float *hand, const int32_t *catch_, int64_t n, int64_t W, int64_t nreach, const float *stage, float nodata, float *out_depth,
+                      mhip_zone_record *records)
+{
+    MH_ARG(hand && catch_ && stage && out_depth && n >= 1 && W >= 0 && nreach >= 0 && nreach < 0x7fffffff,
+           "inundate_f32(hand, catch, n>=1, W>=0, 0<=nreach<2**31-1, stage, nodata, out_depth, records)");
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    DevBuf d_h, d_c, d_s, d_d, d_r;
+    MH_TRY(upload(d_h, hand, (size_t)n * 4, s));
+    MH_TRY(upload(d_c, catch_, (size_t)n * 4, s));
+    MH_TRY(upload(d_s, stage, ((size_t)nreach + 1) * 4, s));
+    MH_TRY(d_d.alloc((size_t)n * 4));
+    if (records) MH_TRY(d_r.alloc(sizeof(mhip_zone_record) * (size_t)(nreach + 1)));
+    MH_TRY(inundate_dev(d_h.as<float>(), d_c.as<int32_t>(), n, W, nreach, d_s.as<float>(), nodata, d_d.as<float>(),
+                        records ? d_r.as<mhip_zone_record>() : nullptr, s));
+    if (records) MH_HIP(hipMemcpyAsync(records, d_r.p, sizeof(mhip_zone_record) * (size_t)(nreach + 1), hipMemcpyDeviceToHost, s));
+    return download(out_depth, d_d, (size_t)n * 4, s);
 }
 
 int mhip_trace_downstream_i32(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, const int64_t *cells_rc, int64_t n,

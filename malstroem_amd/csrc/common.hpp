@@ -511,6 +511,17 @@ int fdist_jumps_dev(uint4 *&cur, uint4 *&nxt, int64_t W, int64_t ntc, int64_t nt
 int hand_check(double threshold, double scale);
 int hand_dev(const uint8_t *d_fd, const double *d_acc, const float *d_elev, const int32_t *d_lab, int64_t H, int64_t W, double threshold, double scale,
              float nodata, float *d_hand, float *d_dist, int64_t *undrained, hipStream_t s);
+// reach_catchments_dev (hand.hip): the reaches of flowpaths_dev into `p` and, per cell, the reach (k + 1) of the drainage
+// cell D(c) its walk ends at into the int32 raster d_catch -- 0 where the cell is undrained, where D(c) is labelled, and where D(c)
+// lies on a cycle of the stream mask that nothing flows into; *assigned: the cells that hold a reach.  Every cell is written.
+// Synchronises.  MHIP_ELIMIT as hand_dev and flowpaths_dev, MHIP_EINVAL: a negative label.
+int reach_catchments_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, int32_t *d_catch,
+                         mhip_flowpaths *p, int64_t *assigned, hipStream_t s);
+// reachcatch.hip: d_depth = stage[catch] - hand where catch > 0, hand is not `nodata` and stage[catch] > hand, +0.0
+// elsewhere; d_stage: nreach + 1 float32 on the device; d_rec (optional): nreach + 1 records of d_depth over d_catch by
+// zone_stats_dev.  Synchronises.  MHIP_EINVAL: a catchment id outside [0, nreach].
+int inundate_dev(const float *d_hand, const int32_t *d_catch, int64_t n, int64_t W, int64_t nreach, const float *d_stage, float nodata, float *d_depth,
+                 mhip_zone_record *d_rec, hipStream_t s);
 // burn.hip: DEM adaptations.  burn_check: the argument rules of mhip_burn_lines_f32 on the host arrays (MHIP_EINVAL; no
 // device work).  burn_lines_dev: the checked lines into the float32 raster d_dem in place, the per-line records to `results` (host).
 // Synchronises.  nseg == 0 writes the records on the host and touches no device.
@@ -539,7 +550,10 @@ int polygonize_dev(const int32_t *d_lab, int64_t H, int64_t W, DevBuf &d_xy, Dev
 // Synchronises.  MHIP_EINVAL: a negative label; MHIP_ELIMIT: more than 2**31 - 1 stream cells.  flowpaths_fetch_dev copies the three
 // buffers to the caller's arrays and computes the Strahler orders there.
 int flowpaths_check(int64_t H, int64_t W, double threshold);
-int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, mhip_flowpaths *p, hipStream_t s);
+// d_rc (optional): an int32 raster that receives the reach of every cell -- k + 1 for the cells of reach k, 0 for every
+// other cell; every cell is written.  Without it the call launches what it launches without the parameter.
+int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, mhip_flowpaths *p, hipStream_t s,
+                  int32_t *d_rc = nullptr);
 int flowpaths_fetch_dev(const mhip_flowpaths *p, int32_t *xy, int64_t *reach_offsets, mhip_reach_record *records);
 // watershed.hip
 int watersheds_dev(const uint8_t *d_fd, int32_t *d_labels, int64_t H, int64_t W, int32_t unassigned, hipStream_t s,

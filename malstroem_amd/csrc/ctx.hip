@@ -1,5 +1,5 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
-// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, the flow paths, and the one
+// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, the flow paths, the reach catchments and their flood depths, and the one
 // rule for what a write of a resident raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
 #include <mutex>
 #include <new>
@@ -26,6 +26,28 @@ static void drop_flow_distance(mhip_ctx *c)
     c->fdist_rec.release();
 }
 
+// the depths of mhip_ctx_inundate go with either of the two results they were made from
+static void drop_inundation(mhip_ctx *c)
+{
+    std::lock_guard<std::mutex> lk(c->rcatch_mu);
+    c->inund_held = -1;      // (the call that fills the buffer has synchronised: nothing on the device still uses it)
+    c->inund_out.release();
+}
+
+// `which` was written: the result of mhip_ctx_reach_catchments goes if it was made from that raster (which < 0: whatever it was made from)
+static void drop_reach_catchments(mhip_ctx *c, int which)
+{
+    if (c->rcatch_nreach < 0 && c->inund_held < 0) return;      // (nothing held: the stages' writes take no lock for this)
+    {
+        std::lock_guard<std::mutex> lk(c->rcatch_mu);
+        if (c->rcatch_nreach < 0) return;
+        if (!(which < 0 || which == MHIP_R_FLOWDIR || which == MHIP_R_ACCUM || (which == MHIP_R_LABELS && c->rcatch_labels))) return;
+        c->rcatch_nreach = -1;
+        c->rcatch_out.release();
+    }
+    drop_inundation(c);
+}
+
 // `which` was written: the result of mhip_ctx_hand goes if it was made from that raster (which < 0: whatever it was made from)
 static void drop_hand(mhip_ctx *c, int which)
 {
@@ -35,11 +57,13 @@ static void drop_hand(mhip_ctx *c, int which)
     c->hand_undrained = -1;      // (the call that fills the buffers has synchronised: nothing on the device still uses them)
     c->hand_out.release();
     c->hand_dist.release();
+    drop_inundation(c);
 }
 
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
 {
     drop_hand(c, which);
+    drop_reach_catchments(c, which);
     switch (which) {
     case MHIP_R_DEM:    // a new DEM invalidates everything derived from the previous one
         c->noflat_pending = false;      // (a surface nobody has asked for goes with have[NOFLAT])
@@ -447,6 +471,8 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels
     else if (k == "flow_distance_unresolved") *value = c->fdist_unresolved;   // -1: no result of mhip_ctx_flow_distance on the resident flow directions and labels
     else if (k == "hand_undrained") *value = c->hand_undrained;      // -1: no result of mhip_ctx_hand on the resident rasters
+    else if (k == "reach_catchments") *value = c->rcatch_nreach;     // -1: no result of mhip_ctx_reach_catchments on the resident rasters
+    else if (k == "inundation") *value = c->inund_held;              // 1: a depth raster of mhip_ctx_inundate is held, -1: none
     else if (k == "zones") *value = c->nzone;                       // -1: no zone raster of mhip_ctx_rasterize_zones
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
@@ -678,6 +704,8 @@ int mhip_ctx_hand(mhip_ctx *c, int32_t elev_source, double threshold, int32_t st
                     c->hand_dist.as<float>(), &u, c->stream));      // (synchronises)
     c->hand_src = elev_source;
     c->hand_labels = stop_at_labels != 0;
+    c->hand_thr = threshold;
+    c->hand_nodata = nodata;
     c->hand_undrained = u;
     *undrained = u;
     return MHIP_OK;
@@ -753,6 +781,10 @@ int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
         MH_ARG(c->hand_undrained >= 0 && c->hand_out.p && c->hand_dist.p, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters");
         src = source == MHIP_ZSRC_HAND ? c->hand_out.as<float>() : c->hand_dist.as<float>();
         break;
+    case MHIP_ZSRC_INUNDATION:
+        MH_ARG(c->inund_held > 0 && c->inund_out.p, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments");
+        src = c->inund_out.as<float>();
+        break;
     default:
         MH_ARG(false, "ctx_zone_stats: the source is no float32 raster of the context");
     }
@@ -768,9 +800,11 @@ int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
 int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
 {
     MH_ARG(c && out, "ctx_polygonize(ctx, source, out)");
-    MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS, "ctx_polygonize: the source is MHIP_R_LABELS or MHIP_R_WATERSHEDS");
+    MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS || source == MHIP_PSRC_REACHCATCH,
+           "ctx_polygonize: the source is MHIP_R_LABELS or MHIP_R_WATERSHEDS, or MHIP_PSRC_REACHCATCH for the reach catchments");
     MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "outlines on a row band are not built (a ring crosses the seams: a later step); use an undivided context");
-    MH_ARG(c->have[source], "raster has not been computed or uploaded");
+    if (source == MHIP_PSRC_REACHCATCH) MH_ARG(c->rcatch_nreach >= 0 && c->rcatch_out.p, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters");
+    else MH_ARG(c->have[source], "raster has not been computed or uploaded");
     if (source == MHIP_R_LABELS) MH_ARG(c->labels_filtered && !c->ccl_pending, "ctx_polygonize needs mhip_ctx_apply_keep after the LABEL run");
     MH_TRY(polygonize_check(c->H, c->W));
     MH_HIP(hipSetDevice(c->device));
@@ -780,7 +814,8 @@ int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
         return MHIP_EHIP;
     }
     p->device = c->device;
-    const int rc = polygonize_dev(c->r[source].as<int32_t>(), c->H, c->W, p->xy, p->ring_offsets, p->ring_label, &p->nring, &p->nvert, c->stream);      // (synchronises)
+    const int32_t *d_src = source == MHIP_PSRC_REACHCATCH ? c->rcatch_out.as<int32_t>() : c->r[source].as<int32_t>();
+    const int rc = polygonize_dev(d_src, c->H, c->W, p->xy, p->ring_offsets, p->ring_label, &p->nring, &p->nvert, c->stream);      // (synchronises)
     if (rc != MHIP_OK) {
         delete p;
         return rc;
@@ -815,6 +850,86 @@ int mhip_ctx_flowpaths(mhip_ctx *c, double threshold, int32_t stop_at_labels, mh
     }
     *out = p;
     return MHIP_OK;
+}
+
+/* ---- reach catchments and flood depths from a stage per reach (hand.hip, flowpaths.hip, reachcatch.hip) ---------------------------- */
+int mhip_ctx_reach_catchments(mhip_ctx *c, double threshold, int32_t stop_at_labels, mhip_flowpaths **out, int64_t *assigned)
+{
+    MH_ARG(c && out && assigned, "ctx_reach_catchments(ctx, threshold, stop_at_labels, out_reaches, assigned)");
+    MH_TRY(flowpaths_check(c->H, c->W, threshold));
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "reach catchments on a row band are not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_ACCUM], "ctx_reach_catchments needs the FLOWDIR and ACCUM rasters");
+    if (stop_at_labels) {
+        MH_ARG(c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_reach_catchments with stop_at_labels needs the LABELS raster");
+        MH_ARG(c->labels_filtered, "ctx_reach_catchments needs mhip_ctx_apply_keep after the LABEL run");
+    }
+    MH_HIP(hipSetDevice(c->device));
+    mhip_flowpaths *p = new (std::nothrow) mhip_flowpaths();
+    if (!p) {
+        set_error("ctx_reach_catchments: out of host memory");
+        return MHIP_EHIP;
+    }
+    p->device = c->device;
+    drop_reach_catchments(c, -1);
+    drop_inundation(c);      // (a new call drops the depths, whether catchments were held or not)
+    int64_t a = 0;
+    int rc = c->rcatch_out.alloc(4 * (size_t)(c->H * c->W));
+    if (rc == MHIP_OK)
+        rc = reach_catchments_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_ACCUM].as<double>(),
+                                  stop_at_labels ? c->r[MHIP_R_LABELS].as<int32_t>() : nullptr, c->H, c->W, threshold, c->rcatch_out.as<int32_t>(), p, &a,
+                                  c->stream);      // (synchronises)
+    if (rc != MHIP_OK) {
+        delete p;
+        c->rcatch_out.release();
+        return rc;
+    }
+    c->rcatch_thr = threshold;
+    c->rcatch_labels = stop_at_labels != 0;
+    c->rcatch_nreach = p->nreach;
+    *assigned = a;
+    *out = p;
+    return MHIP_OK;
+}
+
+int mhip_ctx_reach_catchments_rows(mhip_ctx *c, int64_t row0, int64_t nrows, int32_t *dst)
+{
+    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_reach_catchments_rows(ctx, row0, nrows, dst)");
+    MH_ARG(c->rcatch_nreach >= 0 && c->rcatch_out.p, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters");
+    return ctx_copy_rows(c, c->rcatch_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+}
+
+int mhip_ctx_inundate(mhip_ctx *c, int64_t nreach, const float *stage, mhip_zone_record *records)
+{
+    MH_ARG(c && stage, "ctx_inundate(ctx, nreach, stage, records)");
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "inundation on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->hand_undrained >= 0 && c->hand_out.p, "ctx_inundate needs mhip_ctx_hand on the resident rasters");
+    MH_ARG(c->rcatch_nreach >= 0 && c->rcatch_out.p, "ctx_inundate needs mhip_ctx_reach_catchments on the resident rasters");
+    MH_ARG(c->hand_thr == c->rcatch_thr, "ctx_inundate: the hand and the reach catchments were made with different thresholds");
+    MH_ARG(c->hand_labels == c->rcatch_labels, "ctx_inundate: the hand and the reach catchments were made with different stop_at_labels");
+    MH_ARG(nreach == c->rcatch_nreach, "ctx_inundate: nreach is not the number of reaches of the catchments held");
+    MH_HIP(hipSetDevice(c->device));
+    drop_inundation(c);
+    const int64_t n = c->H * c->W;
+    DevBuf d_stage, d_rec;
+    MH_TRY(upload(d_stage, stage, 4 * ((size_t)nreach + 1), c->stream));
+    if (records) MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(nreach + 1)));
+    MH_TRY(c->inund_out.alloc(4 * (size_t)n));
+    const int rc = inundate_dev(c->hand_out.as<float>(), c->rcatch_out.as<int32_t>(), n, c->W, nreach, d_stage.as<float>(), c->hand_nodata,
+                                c->inund_out.as<float>(), records ? d_rec.as<mhip_zone_record>() : nullptr, c->stream);      // (synchronises)
+    if (rc != MHIP_OK) {
+        c->inund_out.release();
+        return rc;
+    }
+    c->inund_held = 1;
+    if (records) return ctx_fetch(c, d_rec, sizeof(mhip_zone_record) * (size_t)(nreach + 1), records);
+    return MHIP_OK;
+}
+
+int mhip_ctx_inundation_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
+{
+    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_inundation_rows(ctx, row0, nrows, dst)");
+    MH_ARG(c->inund_held > 0 && c->inund_out.p, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments");
+    return ctx_copy_rows(c, c->inund_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
 }
 
 }  // extern "C"

@@ -132,7 +132,19 @@ struct mhip_ctx {
     std::atomic<int64_t> hand_undrained{-1};
     int hand_src = -1;
     bool hand_labels = false;
+    double hand_thr = 0;          // the threshold and the nodata of that call: what mhip_ctx_inundate compares and uses
+    float hand_nodata = 0;
     std::mutex hand_mu;
+    // the catchment raster (int32, H x W; no member of mhip_raster) of the last mhip_ctx_reach_catchments and its number of reaches;
+    // -1: none.  It lives and dies with FLOWDIR, ACCUM and, where `rcatch_labels` says they were used, LABELS.  The depth raster
+    // (float32, H x W) of the last mhip_ctx_inundate goes with the catchments, with the hand result, and with a new call of either;
+    // both are handed back under the lock, as above
+    mh::DevBuf rcatch_out, inund_out;
+    std::atomic<int64_t> rcatch_nreach{-1};
+    std::atomic<int> inund_held{-1};
+    double rcatch_thr = 0;
+    bool rcatch_labels = false;
+    std::mutex rcatch_mu;
     // the zone raster (int32, H x W; not a member of mhip_raster) of the last mhip_ctx_rasterize_zones and its number of zones; -1:
     // none.  It comes from outside: no write of a raster drops it
     mh::DevBuf zones;

@@ -27,6 +27,8 @@
 //                          on); a last cell appends e = down(c)
 //   fp_record_kernel       one thread per stream cell: a first cell writes the record of its reach; to_reach is the number held where
 //                          the reach of end_cell ends
+//   fp_reachcell_kernel    (only with a reach raster) one thread per cell: a stream cell writes the number of its reach
+//                          + 1 -- rinfo where its pointer rests -- or 0 when that is no last cell; every other cell writes 0
 // No thread walks a reach.  The Strahler orders are one pass of Kahn's algorithm over to_reach on the host (flowpaths_fetch_dev).
 #include <new>
 #include <vector>
@@ -351,6 +353,37 @@ __global__ __launch_bounds__(256) void fp_record_kernel(const uint4 *__restrict_
     rec[ri.x] = out;
 }
 
+// rc: the reach of every cell, k + 1 for the cells c0 .. ck of reach k, 0 for a cell that is no stream cell and for a
+// stream cell on a cycle that nothing flows into.  Every cell is written.
+// V cells a thread (V = 4: N is a multiple of four: one 4-byte load of the class bytes, one 16-byte store).
+template <int V>
+__global__ __launch_bounds__(256) void fp_reachcell_kernel(const uint8_t *__restrict__ cls, const unsigned long long *__restrict__ bits,
+                                                          const uint32_t *__restrict__ wbase, const uint4 *__restrict__ st, const uint8_t *__restrict__ flags,
+                                                          const uint4 *__restrict__ rinfo, int64_t N, uint32_t n, int64_t nreach, int32_t *__restrict__ rc)
+{
+    const int64_t c0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (c0 >= N) return;
+    uint32_t cl4;
+    if constexpr (V == 4) cl4 = *reinterpret_cast<const uint32_t *>(cls + c0);
+    else cl4 = cls[c0];
+    int32_t v[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        v[e] = 0;
+        if ((cl4 >> (8 * e)) & CL_STREAM) {
+            uint32_t i = fp_rank(bits, wbase, c0 + e);
+            i = i < n ? i : n - 1u;                 // (it is: the cell is a stream cell)
+            const uint32_t t = st[i].x;             // (< n: a pointer is a compact index)
+            if (t < n && (flags[t] & FL_LAST)) {
+                const uint32_t k = rinfo[t].x;
+                v[e] = (int64_t)k < nreach ? (int32_t)(k + 1u) : 0;
+            }
+        }
+    }
+    if constexpr (V == 4) *reinterpret_cast<int4 *>(rc + c0) = make_int4(v[0], v[1], v[2], v[3]);
+    else rc[c0] = v[0];
+}
+
 }  // namespace
 
 int flowpaths_check(int64_t H, int64_t W, double threshold)
@@ -360,7 +393,8 @@ int flowpaths_check(int64_t H, int64_t W, double threshold)
     return MHIP_OK;
 }
 
-int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, mhip_flowpaths *p, hipStream_t s)
+int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, mhip_flowpaths *p, hipStream_t s,
+                  int32_t *d_rc)
 {
     FpGeom g;
     g.H = H; g.W = W; g.N = H * W;
@@ -398,7 +432,13 @@ int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab
     }
     p->nreach = p->nvert = p->unresolved = 0;
     const uint32_t n = (uint32_t)h.cells;
-    if (n == 0) return MHIP_OK;      // an empty mask: no reach, and the fetch writes the one offset itself
+    if (n == 0) {                    // an empty mask: no reach, and the fetch writes the one offset itself
+        if (d_rc) {
+            MH_HIP(hipMemsetAsync(d_rc, 0, 4 * (size_t)g.N, s));
+            MH_HIP(stream_sync(s));
+        }
+        return MHIP_OK;
+    }
     const int64_t neb = cdiv((int64_t)n, FB);
     const unsigned ge = (unsigned)cdiv((int64_t)n, 256), gc = (unsigned)cdiv(g.N, 256);
     if (cdiv(g.N, 256) > 0x7fffffff) {
@@ -437,7 +477,13 @@ int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab
     MH_HIP(stream_sync(s));
     const int64_t nr = (int64_t)(h.reaches >> 32), nv = (int64_t)(h.reaches & 0xffffffffull);
     p->unresolved = (int64_t)h.unresolved;
-    if (nr == 0) return MHIP_OK;     // every stream cell lies on a cycle that nothing flows into
+    if (nr == 0) {                   // every stream cell lies on a cycle that nothing flows into
+        if (d_rc) {
+            MH_HIP(hipMemsetAsync(d_rc, 0, 4 * (size_t)g.N, s));
+            MH_HIP(stream_sync(s));
+        }
+        return MHIP_OK;
+    }
     MH_TRY(d_rinfo.alloc(16 * (size_t)n));
     MH_TRY(p->xy.alloc(8 * (size_t)nv));
     MH_TRY(p->reach_offsets.alloc(8 * (size_t)(nr + 1)));
@@ -448,6 +494,14 @@ int flowpaths_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab
                        g, n, nv, p->xy.as<int2>());
     hipLaunchKernelGGL(fp_record_kernel, dim3(ge), dim3(256), 0, s, st, d_flags.as<uint8_t>(), d_cell.as<int64_t>(), d_cls.as<uint8_t>(), d_rinfo.as<uint4>(),
                        bits, d_wbase.as<uint32_t>(), d_fd, d_acc, d_lab, g, threshold, n, nr, p->records.as<mhip_reach_record>());
+    if (d_rc) {
+        if (g.N % 4 == 0 && ((uintptr_t)d_rc % 16 == 0) && ((uintptr_t)d_cls.p % 4 == 0))
+            hipLaunchKernelGGL(fp_reachcell_kernel<4>, dim3((unsigned)cdiv(g.N / 4, 256)), dim3(256), 0, s, d_cls.as<uint8_t>(), bits, d_wbase.as<uint32_t>(), st,
+                               d_flags.as<uint8_t>(), d_rinfo.as<uint4>(), g.N, n, nr, d_rc);
+        else
+            hipLaunchKernelGGL(fp_reachcell_kernel<1>, dim3(gc), dim3(256), 0, s, d_cls.as<uint8_t>(), bits, d_wbase.as<uint32_t>(), st, d_flags.as<uint8_t>(),
+                               d_rinfo.as<uint4>(), g.N, n, nr, d_rc);
+    }
     MH_HIP(hipGetLastError());
     MH_HIP(stream_sync(s));      // (the work buffers may go)
     p->nreach = nr;

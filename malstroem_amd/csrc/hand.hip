@@ -9,6 +9,10 @@
 // decoding (fd_resolve, common.hpp).  The tile pass and the final pass are siblings of that file's: the tile pass ends a walk at a
 // drainage cell, and a walk that ends at anything else leaves the tile's cells as FD_NONE, which is what a flow cycle leaves -- the
 // jumps and the decoding need no third kind of end.  The final pass fetches the elevation of the cell the walk ended at.
+//
+// The reach catchments (tests/_reachcatch.py) run the same tile pass and jumps (hand_walk) and end in a sibling of the final
+// pass, catch_final_kernel, which fetches the reach of that cell from the raster flowpaths.hip's fp_reachcell_kernel wrote.
+#include <algorithm>
 #include <cmath>
 
 #include "common.hpp"
@@ -17,6 +21,7 @@ namespace mh {
 namespace {
 
 constexpr int WT = WS_TILE;
+constexpr int64_t CATCH_MAX_BLOCKS = 4096;      // of catch_final_kernel: 16 workgroups of 256 a CU
 
 // ---- tile pass ---------------------------------------------------------------------------------------------------------------
 // fdist_tile_kernel with the drainage test: one workgroup per 64 x 64 tile, a thread owns 16 consecutive cells of a tile row at the
@@ -184,6 +189,39 @@ __global__ __launch_bounds__(256) void hand_final_kernel(const uint2 *__restrict
     if (cnt && (threadIdx.x & 63) == 0) atomicAdd(undrained, (unsigned long long)cnt);
 }
 
+// ---- final pass of the reach catchments ---------------------------------------------------------------------------
+// hand_final_kernel's sibling: 8 B scratch in, one gather of the reach rc[D(c)] at the end of the walk, 4 B out; no elevation and no
+// distance.  Every value is computed and then selected; the gather of an undrained cell goes to the cell itself.  `assigned`: the
+// cells that hold a reach, one atomic per wavefront -- and so that this is a few thousand atomics on the one word and not one per 256
+// cells where most cells are assigned (without labels nearly all are), the grid is bounded and a thread strides over the raster.
+template <int V>
+__global__ __launch_bounds__(256) void catch_final_kernel(const uint2 *__restrict__ S, const uint4 *__restrict__ Nn, const int32_t *__restrict__ rc,
+                                                         int64_t n, int64_t W, int ntc, int32_t *__restrict__ out, unsigned long long *assigned)
+{
+    const int64_t step = (int64_t)gridDim.x * blockDim.x * V;
+    unsigned int cnt = 0;      // (a thread sees fewer than 2**32 cells)
+    for (int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V; i0 < n; i0 += step) {
+        uint2 s[V];
+        fd_load<V>(S, i0, s);
+        int32_t o[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            uint32_t no, nd;
+            int32_t T;
+            const bool ok = fd_resolve(s[e], Nn, (uint32_t)W, ntc, no, nd, T);
+            const int64_t at = ok ? (int64_t)T : i0 + e;
+            const int32_t k = rc[at];
+            o[e] = ok ? k : 0;
+            cnt += (ok && k > 0) ? 1u : 0u;
+        }
+        if constexpr (V == 4) *reinterpret_cast<int4 *>(out + i0) = make_int4(o[0], o[1], o[2], o[3]);
+        else out[i0] = o[0];
+    }
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) cnt += __shfl_xor(cnt, w);
+    if (cnt && (threadIdx.x & 63) == 0) atomicAdd(assigned, (unsigned long long)cnt);
+}
+
 }  // namespace
 
 int hand_check(double threshold, double scale)
@@ -193,38 +231,92 @@ int hand_check(double threshold, double scale)
     return MHIP_OK;
 }
 
+namespace {
+
+// the tile pass and the perimeter jumps of one call: the scratch words and, in `cur`, the node array a final pass reads
+struct HandWalk {
+    DevBuf S, NA, NB, misc;      // misc: [0], [1] the `open` words of two launches, [2..3] the count of the final pass (64 bits)
+    uint4 *cur = nullptr;
+    int64_t ntc = 0;
+    unsigned long long *count() { return misc.as<unsigned long long>() + 1; }
+};
+
+int hand_walk(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, const char *who, HandWalk &w,
+              hipStream_t s)
+{
+    const int64_t n = H * W;
+    if (n >= (int64_t)FD_NONE - 1) {
+        set_error("%s: %lld cells exceed the int32 index domain", who, (long long)n);
+        return MHIP_ELIMIT;
+    }
+    const int64_t ntr = cdiv(H, WT), ntc = cdiv(W, WT), ntiles = ntr * ntc, nnodes = ntiles * 256;
+    MH_TRY(w.S.alloc(8 * (size_t)n));
+    MH_TRY(w.NA.alloc(16 * (size_t)nnodes));
+    MH_TRY(w.NB.alloc(16 * (size_t)nnodes));
+    MH_TRY(w.misc.alloc(16));
+    MH_HIP(hipMemsetAsync(w.misc.p, 0, 16, s));
+    hipLaunchKernelGGL(hand_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, d_fd, d_acc, d_lab, threshold, w.S.as<uint2>(), H, W, (int)ntc, w.NA.as<uint4>());
+    uint4 *nxt = w.NB.as<uint4>();
+    w.cur = w.NA.as<uint4>();
+    w.ntc = ntc;
+    return fdist_jumps_dev(w.cur, nxt, W, ntc, ntiles, w.misc.as<unsigned int>(), s);
+}
+
+// the count of the final pass, once the stream is idle (the scratch and the nodes go back to the pool with `w`)
+int hand_count(HandWalk &w, int64_t *count, hipStream_t s)
+{
+    MH_HIP(hipGetLastError());
+    unsigned long long hm[2] = {0, 0};
+    MH_HIP(hipMemcpyAsync(hm, w.misc.p, 16, hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
+    if (count) *count = (int64_t)hm[1];
+    return MHIP_OK;
+}
+
+}  // namespace
+
 int hand_dev(const uint8_t *d_fd, const double *d_acc, const float *d_elev, const int32_t *d_lab, int64_t H, int64_t W, double threshold, double scale,
              float nodata, float *d_hand, float *d_dist, int64_t *undrained, hipStream_t s)
 {
     const int64_t n = H * W;
-    if (n >= (int64_t)FD_NONE - 1) {
-        set_error("hand: %lld cells exceed the int32 index domain", (long long)n);
-        return MHIP_ELIMIT;
-    }
-    const int64_t ntr = cdiv(H, WT), ntc = cdiv(W, WT), ntiles = ntr * ntc, nnodes = ntiles * 256;
-    DevBuf S, NA, NB, misc;
-    MH_TRY(S.alloc(8 * (size_t)n));
-    MH_TRY(NA.alloc(16 * (size_t)nnodes));
-    MH_TRY(NB.alloc(16 * (size_t)nnodes));
-    // misc: [0], [1] the `open` words of two launches, [2..3] the undrained cells (64 bits)
-    MH_TRY(misc.alloc(16));
-    MH_HIP(hipMemsetAsync(misc.p, 0, 16, s));
-    unsigned int *d_open = misc.as<unsigned int>();
-    unsigned long long *d_und = misc.as<unsigned long long>() + 1;
-    hipLaunchKernelGGL(hand_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, d_fd, d_acc, d_lab, threshold, S.as<uint2>(), H, W, (int)ntc, NA.as<uint4>());
-    uint4 *cur = NA.as<uint4>(), *nxt = NB.as<uint4>();
-    MH_TRY(fdist_jumps_dev(cur, nxt, W, ntc, ntiles, d_open, s));
-    const bool vec = W % 4 == 0 && ((uintptr_t)d_hand | (uintptr_t)d_dist | (uintptr_t)d_elev | (uintptr_t)S.p) % 16 == 0;
+    HandWalk w;
+    MH_TRY(hand_walk(d_fd, d_acc, d_lab, H, W, threshold, "hand", w, s));
+    const bool vec = W % 4 == 0 && ((uintptr_t)d_hand | (uintptr_t)d_dist | (uintptr_t)d_elev | (uintptr_t)w.S.p) % 16 == 0;
     const int V = vec ? 4 : 1;
     const dim3 grid((unsigned)cdiv(cdiv(n, V), 256)), block(256);
-    if (vec) hipLaunchKernelGGL(hand_final_kernel<4>, grid, block, 0, s, S.as<uint2>(), cur, d_elev, n, W, (int)ntc, scale, nodata, d_hand, d_dist, d_und);
-    else hipLaunchKernelGGL(hand_final_kernel<1>, grid, block, 0, s, S.as<uint2>(), cur, d_elev, n, W, (int)ntc, scale, nodata, d_hand, d_dist, d_und);
-    MH_HIP(hipGetLastError());
-    unsigned long long hm[2] = {0, 0};
-    MH_HIP(hipMemcpyAsync(hm, misc.p, 16, hipMemcpyDeviceToHost, s));
-    MH_HIP(stream_sync(s));      // (the scratch and the nodes go back to the pool)
-    if (undrained) *undrained = (int64_t)hm[1];
-    return MHIP_OK;
+    if (vec) hipLaunchKernelGGL(hand_final_kernel<4>, grid, block, 0, s, w.S.as<uint2>(), w.cur, d_elev, n, W, (int)w.ntc, scale, nodata, d_hand, d_dist, w.count());
+    else hipLaunchKernelGGL(hand_final_kernel<1>, grid, block, 0, s, w.S.as<uint2>(), w.cur, d_elev, n, W, (int)w.ntc, scale, nodata, d_hand, d_dist, w.count());
+    return hand_count(w, undrained, s);
+}
+
+// The reach catchments: the reaches and the reach of every stream cell by flowpaths_dev, the walk to D(c) by the tile
+// pass and the jumps above, one gather.  The drainage cells of the walk and the stream cells of the reaches come from one threshold
+// and one label raster, so the two masks agree by construction: a drainage cell that is no stream cell is a labelled one, and holds 0.
+int reach_catchments_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, int32_t *d_catch,
+                         mhip_flowpaths *p, int64_t *assigned, hipStream_t s)
+{
+    const int64_t n = H * W;
+    if (n >= (int64_t)FD_NONE - 1) {      // (before any device work: the limit of both engines)
+        set_error("reach_catchments: %lld cells exceed the int32 index domain", (long long)n);
+        return MHIP_ELIMIT;
+    }
+    DevBuf d_rc;
+    MH_TRY(d_rc.alloc(4 * (size_t)n));
+    MH_TRY(flowpaths_dev(d_fd, d_acc, d_lab, H, W, threshold, p, s, d_rc.as<int32_t>()));
+    if (p->nreach == 0) {      // an empty mask, or cycles of the mask only: no walk ends in a reach
+        MH_HIP(hipMemsetAsync(d_catch, 0, 4 * (size_t)n, s));
+        MH_HIP(stream_sync(s));
+        if (assigned) *assigned = 0;
+        return MHIP_OK;
+    }
+    HandWalk w;
+    MH_TRY(hand_walk(d_fd, d_acc, d_lab, H, W, threshold, "reach_catchments", w, s));
+    const bool vec = W % 4 == 0 && ((uintptr_t)d_catch | (uintptr_t)d_rc.p | (uintptr_t)w.S.p) % 16 == 0;
+    const int V = vec ? 4 : 1;
+    const dim3 grid((unsigned)std::min<int64_t>(cdiv(cdiv(n, V), 256), CATCH_MAX_BLOCKS)), block(256);
+    if (vec) hipLaunchKernelGGL(catch_final_kernel<4>, grid, block, 0, s, w.S.as<uint2>(), w.cur, d_rc.as<int32_t>(), n, W, (int)w.ntc, d_catch, w.count());
+    else hipLaunchKernelGGL(catch_final_kernel<1>, grid, block, 0, s, w.S.as<uint2>(), w.cur, d_rc.as<int32_t>(), n, W, (int)w.ntc, d_catch, w.count());
+    return hand_count(w, assigned, s);
 }
 
 }  // namespace mh

@@ -68,6 +68,15 @@ def extract(flowdir, accum, threshold, labelled=None):
     ``flowdir`` (uint8, AGNPS codes) on the device; ``accum`` float64; ``labelled`` (int32, optional): a cell with a label is no
     stream cell, and a reach that runs into one ends there (``end_kind`` 3, ``to_label``).  ``unresolved``: the stream cells on a
     cycle of the mask that nothing flows into (none when ``accum`` is the accumulation of ``flowdir``)."""
+    thr, fd, acc, lab = _check_inputs(flowdir, accum, threshold, labelled)
+    handle = ctypes.c_void_p()
+    _lib.call("mhip_flowpaths_f64", _lib.ptr(fd), _lib.ptr(acc), _lib.ptr(lab) if lab is not None else None, _lib.i64(fd.shape[0]),
+              _lib.i64(fd.shape[1]), ctypes.c_double(thr), ctypes.byref(handle))
+    return take_flowpaths(handle)
+
+
+def _check_inputs(flowdir, accum, threshold, labelled):
+    """``(threshold, flowdir, accum, labelled or None)``, checked and contiguous (``ValueError``; nothing touches the library)"""
     thr = check_threshold(threshold)
     fd, acc = np.asarray(flowdir), np.asarray(accum)
     if fd.dtype != np.uint8:
@@ -85,23 +94,80 @@ def extract(flowdir, accum, threshold, labelled=None):
         if lab.dtype != np.int32:
             raise ValueError("Buffer dtype mismatch, expected 'int32' but got '%s'" % lab.dtype)
         lab = np.ascontiguousarray(lab)
-    handle = ctypes.c_void_p()
-    _lib.call("mhip_flowpaths_f64", _lib.ptr(fd), _lib.ptr(acc), _lib.ptr(lab) if lab is not None else None, _lib.i64(fd.shape[0]),
-              _lib.i64(fd.shape[1]), ctypes.c_double(thr), ctypes.byref(handle))
-    return take_flowpaths(handle)
+    return thr, fd, acc, lab
+
+
+def reach_catchments(flowdir, accum, threshold, labelled=None):
+    """``(catch, xy, reach_offsets, records, unresolved, assigned)``: the reaches of ``extract`` with the same arguments and, per
+    cell, the reach its flow path drains to (the definition is ``tests/_reachcatch.py``).  ``catch`` (int32) holds
+    ``reach_id + 1`` of the reach that the first drainage cell on the cell's flow path belongs to -- the drainage cells of
+    ``algorithms.flow.hand`` with the same threshold and labels -- and 0 where the path meets no drainage, ends in a bluespot (the
+    watersheds raster says which) or on a stream cell that lies on a cycle of the mask.  ``assigned`` counts the cells > 0."""
+    thr, fd, acc, lab = _check_inputs(flowdir, accum, threshold, labelled)
+    catch = np.empty(fd.shape, dtype=np.int32)
+    handle, assigned = ctypes.c_void_p(), ctypes.c_int64(0)
+    _lib.call("mhip_reach_catchments_i32", _lib.ptr(fd), _lib.ptr(acc), _lib.ptr(lab) if lab is not None else None, _lib.i64(fd.shape[0]),
+              _lib.i64(fd.shape[1]), ctypes.c_double(thr), _lib.ptr(catch), ctypes.byref(handle), ctypes.byref(assigned))
+    return (catch,) + take_flowpaths(handle) + (assigned.value,)
+
+
+def check_stage(stage, nreach=None):
+    """A stage per reach as a contiguous float32 array of ``nreach + 1`` entries, entry 0 ignored; any values (``ValueError`` for
+    another shape or a dtype that is no number; nothing touches the library)."""
+    st = np.asarray(stage)
+    if st.ndim != 1 or st.size < 1 or not (np.issubdtype(st.dtype, np.floating) or np.issubdtype(st.dtype, np.integer)):
+        raise ValueError("stage must be a 1-D array of numbers with nreach + 1 entries (entry 0 is ignored)")
+    if nreach is not None and st.size != nreach + 1:
+        raise ValueError("stage must have nreach + 1 = %d entries, got %d" % (nreach + 1, st.size))
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(st, dtype=np.float32)
+
+
+def inundate(hand, catchments, stage, nodata=-9999.0, records=False):
+    """Flood depths for a water level per reach: ``stage[k] - hand`` (float32) in the catchment of reach ``k - 1`` where that is
+    positive and ``hand`` is not ``nodata``, 0 elsewhere.  ``hand`` float32 (``algorithms.flow.hand``), ``catchments`` int32
+    (``reach_catchments``, made with the same threshold and labels) with values in ``[0, nreach]``, ``stage``: ``nreach + 1`` values,
+    entry 0 ignored; a NaN, zero or negative stage wets nothing above its drainage.  ``records=True``: ``(depth, records)`` with one
+    ``_lib.ZONE_DTYPE`` record per entry of ``stage`` -- ``cells`` the size of the local catchment, ``pos`` its wet cells, ``vmax`` the
+    deepest, ``vmin_pos`` the shallowest positive depth."""
+    from .algorithms.flow import check_hand_nodata
+    nd = check_hand_nodata(nodata)
+    h, k = np.asarray(hand), np.asarray(catchments)
+    if h.dtype != np.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32' but got '%s'" % h.dtype)
+    if k.dtype != np.int32:
+        raise ValueError("Buffer dtype mismatch, expected 'int32' but got '%s'" % k.dtype)
+    if h.ndim != 2 or h.size < 1 or k.shape != h.shape:
+        raise ValueError("hand and catchments must be rasters of one shape, got %r and %r" % (h.shape, k.shape))
+    st = check_stage(stage)
+    if st.size - 1 >= 2 ** 31 - 1:
+        raise ValueError("more than 2**31 - 2 reaches")
+    h, k = np.ascontiguousarray(h), np.ascontiguousarray(k)
+    if k.min() < 0 or k.max() >= st.size:
+        raise ValueError("catchments holds an id outside [0, nreach = %d]" % (st.size - 1))
+    depth = np.empty(h.shape, dtype=np.float32)
+    rec = np.empty(st.size, dtype=_lib.ZONE_DTYPE) if records else None
+    _lib.call("mhip_inundate_f32", _lib.ptr(h), _lib.ptr(k), _lib.i64(h.size), _lib.i64(h.shape[1]), _lib.i64(st.size - 1), _lib.ptr(st),
+              ctypes.c_float(nd), _lib.ptr(depth), _lib.ptr(rec) if records else None)
+    return (depth, rec) if records else depth
 
 
 # ---- features ---------------------------------------------------------------------------------------------------------------------------
-def features_from_reaches(xy, reach_offsets, records, transform, cellsize=None):
+def features_from_reaches(xy, reach_offsets, records, transform, cellsize=None, local_cells=None):
     """One GeoJSON feature per reach, in reach order: a ``LineString`` through the cell centres ``(col + 0.5, row + 0.5)`` of its
     vertices in world coordinates (the six-term ``transform`` in float64, all vertices at once), a ``Point`` for a reach of one
     vertex.  Properties: ``reach_id``; ``up_cells`` / ``down_cells`` (the accumulated flow at its first and last cell) and
     ``up_area`` / ``down_area`` (times the cell area of the transform); ``length`` = ``(n_orth + n_diag * 2**0.5) * cellsize``
     (``cellsize``: ``abs(transform[1])`` by default); ``order`` (Strahler; 0: a reach on a cycle); ``to_reach`` (null: none),
     ``to_bspot`` / ``from_bspot`` (null: none); ``end``: ``"confluence"``, ``"edge"``, ``"sink"``, ``"bluespot"`` or
-    ``"below_threshold"``."""
+    ``"below_threshold"``.  With ``local_cells`` (one count per reach: the cells of its catchment, ``reach_catchments``) also
+    ``local_cells`` and ``local_area``."""
     xy, off, rec = check_reaches(xy, reach_offsets, records)
     t = check_transform(transform)
+    if local_cells is not None:
+        local_cells = np.asarray(local_cells)
+        if local_cells.shape != (rec.size,) or not np.issubdtype(local_cells.dtype, np.integer):
+            raise ValueError("local_cells must be a 1-D integer array with one entry per reach")
     if cellsize is None:
         cellsize = abs(t[1])
     else:
@@ -120,5 +186,7 @@ def features_from_reaches(xy, reach_offsets, records, transform, cellsize=None):
                      down_area=float(r["down_cells"] * cell_area), length=float(length[k]), order=int(r["order"]),
                      to_reach=int(r["to_reach"]) if r["to_reach"] >= 0 else None, to_bspot=int(r["to_label"]) or None,
                      from_bspot=int(r["from_label"]) or None, end=_lib.REACH_END[int(r["end_kind"])])
+        if local_cells is not None:
+            props.update(local_cells=int(local_cells[k]), local_area=float(local_cells[k] * cell_area))
         features.append(dict(type="Feature", id=k, properties=props, geometry=geometry))
     return features

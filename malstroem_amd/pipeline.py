@@ -280,7 +280,7 @@ class HydroPipeline(CtxHandle):
     # ---- object exposure: polygons to a zone raster, a resident raster reduced per zone (objects.py) -----
     ZONE_SOURCES = {"dem": _lib.R_DEM, "filled": _lib.R_FILLED, "depths": _lib.R_DEPTHS, "finaldepths": _lib.R_FINALDEPTHS,
                     "wet_at": _lib.ZSRC_WETAT, "flow_distance": _lib.ZSRC_FLOWDIST, "hand": _lib.ZSRC_HAND,
-                    "drain_distance": _lib.ZSRC_DRAINDIST}
+                    "drain_distance": _lib.ZSRC_DRAINDIST, "inundation": _lib.ZSRC_INUNDATION}
 
     def rasterize_zones(self, xy, ring_offsets, ring_zone, nzone, grow=0):
         """Rasterize polygons (``objects.rings_from_features``) at the pipeline's shape; the zone raster stays on the device for
@@ -293,7 +293,7 @@ class HydroPipeline(CtxHandle):
 
     def zone_stats(self, source):
         """``nzone + 1`` records (``_lib.ZONE_DTYPE``) of a resident float32 raster over the zones: ``source`` is ``"dem"``,
-        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"``, ``"flow_distance"``, ``"hand"`` or ``"drain_distance"``.  ``ValueError`` without zones or when the
+        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"``, ``"flow_distance"``, ``"hand"``, ``"drain_distance"`` or ``"inundation"``.  ``ValueError`` without zones or when the
         source has not been computed.  (``"hand"``: ``vmin_pos`` is the lowest positive height above drainage of an object's cells.
         The negative nodata of its undrained cells is never the largest value of a zone that has one drained cell, and is never
         positive: it shows in ``vmax`` only where no cell of the zone is drained.)"""
@@ -320,11 +320,11 @@ class HydroPipeline(CtxHandle):
         write_windows(writer, self.shape, np.int32, self.download_zones_rows, max_rows)
 
     # ---- outlines of the resident labels / watersheds (vector.py) ----------------------------------------
-    POLYGON_SOURCES = {"labels": _lib.R_LABELS, "watersheds": _lib.R_WATERSHEDS}
+    POLYGON_SOURCES = {"labels": _lib.R_LABELS, "watersheds": _lib.R_WATERSHEDS, "reach_catchments": _lib.PSRC_REACHCATCH}
 
     def polygonize(self, source="labels"):
-        """``(xy, ring_offsets, ring_label)`` of the resident (filtered) labels or of the watersheds, as ``vector.polygonize`` gives
-        them for the downloaded raster; no raster leaves the device.  The arrays are a snapshot: a later run does not change them."""
+        """``(xy, ring_offsets, ring_label)`` of the resident (filtered) labels, of the watersheds or of the catchments of the last
+        ``reach_catchments`` (``ring_label``: ``reach_id + 1``), as ``vector.polygonize`` gives them for the downloaded raster; no raster leaves the device.  The arrays are a snapshot: a later run does not change them."""
         from .vector import take_polygons
         if source not in self.POLYGON_SOURCES:
             raise ValueError("source must be one of %s, got %r" % (sorted(self.POLYGON_SOURCES), source))
@@ -342,3 +342,60 @@ class HydroPipeline(CtxHandle):
         handle = ctypes.c_void_p()
         _lib.call("mhip_ctx_flowpaths", self._ctx, ctypes.c_double(thr), ctypes.c_int32(1 if stop_at_bluespots else 0), ctypes.byref(handle))
         return take_flowpaths(handle)
+
+    # ---- reach catchments and flood depths from a stage per reach (flowpaths.py) ---------------------------
+    def reach_catchments(self, threshold, stop_at_bluespots=True):
+        """``(xy, reach_offsets, records, unresolved, assigned)``: the reaches of ``flow_paths`` with the same arguments and, in a
+        raster that stays on the device, per cell ``reach_id + 1`` of the reach its flow path drains to (0: none; the definition is
+        ``tests/_reachcatch.py``) -- the catchments of ``hand`` with the same ``threshold`` and ``stop_at_bluespots``.  ``assigned``
+        counts the cells > 0.  The raster is there for ``download_reach_catchments`` (and its ``_rows`` / ``_to`` forms),
+        ``polygonize("reach_catchments")`` and ``inundate`` until the flow directions, the accumulated flow or the labels it was made
+        from are written again."""
+        from .flowpaths import check_threshold, take_flowpaths
+        thr = check_threshold(threshold)
+        handle, assigned = ctypes.c_void_p(), ctypes.c_int64(0)
+        _lib.call("mhip_ctx_reach_catchments", self._ctx, ctypes.c_double(thr), ctypes.c_int32(1 if stop_at_bluespots else 0), ctypes.byref(handle),
+                  ctypes.byref(assigned))
+        return take_flowpaths(handle) + (assigned.value,)
+
+    def download_reach_catchments_rows(self, row0, nrows):
+        if self.get_int("reach_catchments") < 0:
+            raise ValueError("reach_catchments() has not been run on the resident rasters")
+        out = np.empty((int(nrows), self.shape[1]), dtype=np.int32)
+        _lib.call("mhip_ctx_reach_catchments_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
+        return out
+
+    def download_reach_catchments(self):
+        """The catchment raster of the last ``reach_catchments`` (int32); ``ValueError`` once a raster it was made from is gone."""
+        return self.download_reach_catchments_rows(0, self.shape[0])
+
+    def download_reach_catchments_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.int32, self.download_reach_catchments_rows, max_rows)
+
+    def inundate(self, stage):
+        """Flood depths for a water level per reach on the held ``hand`` and ``reach_catchments`` results, which must have been made
+        with the same threshold and ``stop_at_bluespots``: ``stage`` has one value per reach behind an ignored entry 0
+        (``flowpaths.inundate``).  Returns the ``nreach + 1`` records (``_lib.ZONE_DTYPE``) of the depths over the catchments; the
+        depth raster stays on the device for ``download_inundation`` (and its ``_rows`` / ``_to`` forms) and
+        ``zone_stats("inundation")`` until either result goes or is made again."""
+        from .flowpaths import check_stage
+        st = check_stage(stage)
+        rec = np.empty(st.size, dtype=_lib.ZONE_DTYPE)
+        _lib.call("mhip_ctx_inundate", self._ctx, _lib.i64(st.size - 1), _lib.ptr(st), _lib.ptr(rec))
+        return rec
+
+    def download_inundation_rows(self, row0, nrows):
+        if self.get_int("inundation") < 0:
+            raise ValueError("inundate() has not been run on the held hand and reach catchments")
+        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
+        _lib.call("mhip_ctx_inundation_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
+        return out
+
+    def download_inundation(self):
+        """The depth raster of the last ``inundate`` (float32); ``ValueError`` once a result it was made from is gone."""
+        return self.download_inundation_rows(0, self.shape[0])
+
+    def download_inundation_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.float32, self.download_inundation_rows, max_rows)
