@@ -22,6 +22,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "handover_addr.hpp"
 
 namespace mh {
 namespace {
@@ -141,9 +142,14 @@ __device__ __forceinline__ void unite_l(uint32_t *par, uint32_t a, uint32_t b)
 #ifndef CCL_U3
 #define CCL_U3 4
 #endif
-template <typename T>
+// WET (the bluespot depths of a request whose flood handed over to the no-flats fill): the foreground is not read from
+// the depths -- 64 rows of floats a lane for a yes / no -- but from the wet bits that request's first visit left behind, "filled >
+// dem", which is "filled - dem != 0" for finite floats with gradual underflow: the two or three words of the lane's column that
+// cover the tile's 64 rows (handover_addr.hpp: wet_rows64), each from its one owner.  A raster border cell is dry without a look.
+template <typename T, bool WET = false>
 __global__ __launch_bounds__(256) void ccl_tile_kernel(const T *__restrict__ data, int32_t *__restrict__ parent, int64_t H, int64_t W, int ntc,
-                                                       int32_t *__restrict__ rootlist, int32_t *__restrict__ rootcount, int32_t *__restrict__ colpar)
+                                                       int32_t *__restrict__ rootlist, int32_t *__restrict__ rootcount, int32_t *__restrict__ colpar,
+                                                       const unsigned long long *__restrict__ wet = nullptr, int wet_ntr = 0)
 {
     __shared__ uint32_t par[CT * CT];
     __shared__ int s_nroots;
@@ -152,12 +158,21 @@ __global__ __launch_bounds__(256) void ccl_tile_kernel(const T *__restrict__ dat
     const int ti = blockIdx.x / ntc, tj = blockIdx.x - ti * ntc;
     const int64_t r0 = (int64_t)ti * CT, c0 = (int64_t)tj * CT;
     const int64_t cc = c0 + lane;
+    uint64_t wrows = 0ull;      // WET: bit r = the foreground of tile row r in this lane's column
+    if constexpr (WET) {
+        const int t0 = ho::wet_tile_row(r0, wet_ntr), t1 = t0 + 1 < wet_ntr ? t0 + 1 : wet_ntr - 1, t2 = t0 + 2 < wet_ntr ? t0 + 2 : wet_ntr - 1;
+        const int64_t cw = cc < W ? cc : W - 1;
+        const uint64_t w0 = wet[(int64_t)t0 * W + cw], w1 = wet[(int64_t)t1 * W + cw], w2 = wet[(int64_t)t2 * W + cw];
+        wrows = (cc > 0 && cc < W - 1) ? ho::wet_rows64(w0, w1, w2, r0, H, wet_ntr) : 0ull;
+    }
     // (the foreground masks of the rows are not kept for the union phase -- sixteen 64-bit values per wavefront that held the kernel
     // at 94 VGPRs: a row's mask is a ballot over its parents, which are LBG exactly on the background)
 #pragma unroll
     for (int k = 0; k < CT / 4; ++k) {
         const int r = wave + 4 * k;
-        const bool fg = (r0 + r) < H && cc < W && is_fg(data[(r0 + r) * W + cc]);
+        bool fg;
+        if constexpr (WET) fg = (wrows >> r) & 1ull;
+        else fg = (r0 + r) < H && cc < W && is_fg(data[(r0 + r) * W + cc]);
         const uint64_t m = __ballot(fg);
         // first lane of my run: the highest run start at or below my lane
         const uint64_t starts = m & ~(m << 1);
@@ -439,9 +454,10 @@ __global__ __launch_bounds__(256) void ccl_emit_kernel(const int32_t *__restrict
     labels[i] = p == -1 ? 0 : -p - 1;
 }
 
+// wet (float depths only, the tiled schedule): their foreground as the wet bits of handover_addr.hpp, for the tile pass
 template <typename T>
 int ccl8_dev(const T *d_data, int32_t *d_labels, int32_t *d_tmp, int64_t H, int64_t W, int64_t *nlabels, hipStream_t s, DevBuf *stats_out = nullptr,
-             CclKeep *keep = nullptr)
+             CclKeep *keep = nullptr, const unsigned long long *wet = nullptr, bool *wet_used = nullptr)
 {
     if (keep) keep->valid = false;
     const int64_t n = H * W;
@@ -477,8 +493,17 @@ int ccl8_dev(const T *d_data, int32_t *d_labels, int32_t *d_tmp, int64_t H, int6
         MH_TRY(wprefix.alloc(4 * (size_t)nwords));
         MH_TRY(bcounts.alloc(4 * (size_t)nwb));
         MH_HIP(hipMemsetAsync(bits.p, 0, 8 * (size_t)nwords, s));
-        hipLaunchKernelGGL((ccl_tile_kernel<T>), dim3((unsigned)ntiles), dim3(256), 0, s, d_data, parent, H, W, (int)ntc, roots.as<int32_t>(),
-                           rcount.as<int32_t>(), colpar.as<int32_t>());
+        bool from_bits = false;
+        if constexpr (std::is_same<T, float>::value) from_bits = wet && H >= 3 && W >= 3;
+        if constexpr (std::is_same<T, float>::value) {
+            if (from_bits)
+                hipLaunchKernelGGL((ccl_tile_kernel<T, true>), dim3((unsigned)ntiles), dim3(256), 0, s, d_data, parent, H, W, (int)ntc, roots.as<int32_t>(),
+                                   rcount.as<int32_t>(), colpar.as<int32_t>(), wet, (int)((H - 2 + ho::TI - 1) / ho::TI));
+            if (from_bits && wet_used) *wet_used = true;
+        }
+        if (!from_bits)
+            hipLaunchKernelGGL((ccl_tile_kernel<T, false>), dim3((unsigned)ntiles), dim3(256), 0, s, d_data, parent, H, W, (int)ntc, roots.as<int32_t>(),
+                               rcount.as<int32_t>(), colpar.as<int32_t>(), (const unsigned long long *)nullptr, 0);
         const int64_t nh = (ntr - 1) * W, nv = (ntc - 1) * H;
         if (nh + nv > 0)
             hipLaunchKernelGGL(ccl_seam_kernel, dim3((unsigned)cdiv(nh + nv, 256)), dim3(256), 0, s, parent, H, W, nh, nh + nv, colpar.as<int32_t>(), ntc);
@@ -545,9 +570,10 @@ int ccl8_dev(const T *d_data, int32_t *d_labels, int32_t *d_tmp, int64_t H, int6
 }  // namespace
 
 int ccl8_f32_dev(const float *d_data, int32_t *d_labels, int32_t *d_tmp, int64_t H, int64_t W, int64_t *nlabels,
-                 hipStream_t s, DevBuf *stats_out)
+                 hipStream_t s, DevBuf *stats_out, const unsigned long long *wet, bool *wet_used)
 {
-    return ccl8_dev<float>(d_data, d_labels, d_tmp, H, W, nlabels, s, stats_out);
+    if (wet_used) *wet_used = false;
+    return ccl8_dev<float>(d_data, d_labels, d_tmp, H, W, nlabels, s, stats_out, nullptr, wet, wet_used);
 }
 int ccl8_f32_begin_dev(const float *d_data, int32_t *d_labels, int32_t *d_tmp, int64_t H, int64_t W, int64_t *nlabels, hipStream_t s, CclKeep *keep)
 {

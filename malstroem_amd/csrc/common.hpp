@@ -235,6 +235,12 @@ struct FillHandover {
     int ntr = 0, ntc = 0;
     bool pending = false, queued = false, violated = false, repaired = false;
     bool suspect = false;               // the proof failed in the fused visit: the flood's own last pass decides (and is what ran last)
+    // The wet bits (handover_addr.hpp: wet_index): the caller's buffer of wet_words() words, or null.  The fused visit writes its
+    // proof bits "filled > dem" there; `wet_ok` once that visit's proof has passed: for the rest of THIS request the bits stand for
+    // the comparison at every cell (a finite DEM: the caller's business), and for "depths != 0"
+    unsigned long long *wet = nullptr;
+    bool wet_ok = false;
+    bool wet_pass = false;              // the no-flats fill's finishing pass read them instead of the DEM
     FillStats st_repair;                // the relaxation that repaired a surface whose proof failed
     FillHandover() = default;
     FillHandover(const FillHandover &) = delete;
@@ -320,6 +326,7 @@ struct GeoRun {
     bool defer_out = false;                           // with d8_out and an external `dist`: end() may leave `out` unwritten ...
     bool out_deferred = false;                        // ... set by end(): it did -- `out` is noflat_assemble_dev(filled, dist) whenever somebody wants it
     FillHandover *handover = nullptr;                 // pending: begin() computes, writes and proves `filled` (and the depths) in its first visit
+    bool wet_used = false;                            // set by end(): its pass took the DEM from the hand-over's wet bits
     struct Impl;
     Impl *impl;
     GeoRun();
@@ -430,8 +437,10 @@ int accum_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t W, hipStrea
 int accum_band_delta_dev(const uint8_t *d_fd, double *d_out, int64_t H, int64_t W, hipStream_t s, int fixed_top, int fixed_bot, AccumKeep *keep, bool *done);
 // ccl.hip   (d_tmp: H*W int32 scratch)
 // stats_out: the labelling's last pass also reduces label_stats(d_data, labels) into *stats_out (allocated here: nlabels + 1 records)
+// wet: "d_data != 0" of every cell as the wet bits of a hand-over (FillHandover::wet with wet_ok) -- the tile pass reads them and not
+// d_data (*wet_used); the emit / statistics pass keeps reading the values
 int ccl8_f32_dev(const float *d_data, int32_t *d_labels, int32_t *d_tmp, int64_t H, int64_t W, int64_t *nlabels,
-                 hipStream_t s, DevBuf *stats_out = nullptr);
+                 hipStream_t s, DevBuf *stats_out = nullptr, const unsigned long long *wet = nullptr, bool *wet_used = nullptr);
 int label_emit_stats_dev(const int32_t *d_parent, const unsigned long long *d_rootbits, const uint32_t *d_wordprefix, const float *d_data,
                          int32_t *d_labels, int64_t H, int64_t W, int64_t nlab, mhip_stat_record *d_rec, hipStream_t s);
 int ccl8_u8_dev(const uint8_t *d_data, int32_t *d_labels, int32_t *d_tmp, int64_t H, int64_t W, int64_t *nlabels,

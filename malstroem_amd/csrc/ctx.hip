@@ -450,6 +450,7 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "fill_tiles") *value = c->fill_st.tiles;
     else if (k == "fill_algorithm") *value = c->fill_st.algorithm;   // 0 iterative tile schedule, 1 tiled priority-flood
     else if (k == "fill_handover") *value = c->fill_handover;       // 1 the last request wrote FILLED / DEPTHS in the no-flats fill's first visit (ng_handover_kernel)
+    else if (k == "wetbits_used") *value = (c->wet_pass_used ? 1 : 0) | (c->wet_label_used ? 2 : 0);         // bit 0: ng_finish_kernel, bit 1: ccl_tile_kernel took the wet bits of the last request's hand-over (ctx_run.hip)
     else if (k == "fill_handover_rechecks") *value = c->fill_handover_rechecks;   // diagnostics: see ctx.hpp
     else if (k == "fill_overflow") *value = c->fill_st.overflow;     // the flood's capacities that gave out (0: it ran through / was not tried)
     else if (k == "fill_launches") *value = c->fill_st.rounds;

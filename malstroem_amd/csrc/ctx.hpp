@@ -153,6 +153,9 @@ struct mhip_ctx {
     int32_t fill_rounds = 0, noflat_rounds = 0;
     int64_t fill_handover_rechecks = 0;   // requests of this context whose fused visit failed the proof and went through the flood's own last pass
     int32_t fill_handover = 0;      // the last request's no-flats fill took the flood's last pass and proof into its first visit (ctx_run.hip)
+    // the last request read that visit's wet bits instead of floats: the finishing pass (the DEM), the labelling (the depths) -- a
+    // word each: the two are set by the two host threads of a request
+    int32_t wet_pass_used = 0, wet_label_used = 0;
     mh::FillStats fill_st, noflat_st;
     mh::StageTimer timers[mh::N_TIMERS];
     void *comm = nullptr;   // RCCL communicator over all bands (comm.hip); nullptr: the launcher moves the rows

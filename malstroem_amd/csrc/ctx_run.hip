@@ -1,16 +1,19 @@
 // ctx_run.hip -- the stages of the device-resident pipeline and their DAG (mhip_ctx_run): one host thread per branch, two or three
 // streams, HIP-event timing per stage.  Every stage that writes a resident raster says so with ctx_wrote (ctx.hpp).
 #include <atomic>
+#include <cmath>
 #include <future>
 #include <string>
 
 #include "ctx.hpp"
+#include "handover_addr.hpp"
 
 using namespace mh;
 
 constexpr int LABEL_START_DEFAULT = 3;      // chosen by measurement: DESIGN 4.5
 constexpr int FILL_HANDOVER_DEFAULT = 1;    // chosen by measurement: DESIGN 7
 constexpr int NOFLAT_LAZY_DEFAULT = 1;      // chosen by measurement: DESIGN 7
+constexpr int WETBITS_DEFAULT = 1;          // chosen by measurement: DESIGN 7
 
 // MHIP_FILL_HANDOVER = 0 | 1 (development knob, read per request): may a request that holds FILL and NOFLAT leave the flood's
 // last pass and its proof to the first visit of the no-flats fill?
@@ -26,6 +29,14 @@ static bool noflat_lazy_env()
 {
     const char *e = dev_env("MHIP_NOFLAT_LAZY");
     return e ? e[0] != '0' : NOFLAT_LAZY_DEFAULT != 0;
+}
+
+// MHIP_WETBITS = 0 | 1 (development knob, read per request): may the finishing pass and the labelling of a request whose flood
+// handed over to the no-flats fill read that visit's proof bits "filled > dem" instead of the DEM and the depths?
+static bool wetbits_env()
+{
+    const char *e = dev_env("MHIP_WETBITS");
+    return e ? e[0] != '0' : WETBITS_DEFAULT != 0;
 }
 
 static int stage_depths(mhip_ctx *c, hipStream_t s)
@@ -107,6 +118,10 @@ static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, Stag
         ctx_wrote(c, MHIP_R_FILLED);
         c->have[MHIP_R_FILLED] = true;
     }
+    // the wet bits stand for floats only where "filled > dem" is "filled - dem != 0": no NaN, no infinity in the DEM -- which the
+    // flood of this request has told (a DEM it did not fold: no bits)
+    if (ho && ho->wet && !(c->fill_st.have_minmax && !c->fill_st.dem_nan && std::isfinite(c->fill_st.dem_min) && std::isfinite(c->fill_st.dem_max)))
+        ho->wet = nullptr;
     D8Sink d8;
     static const bool fuse_d8 = [] { const char *e = dev_env("MHIP_D8_FUSE"); return !(e && e[0] == '0'); }();   // (development: 0 = D8 as a pass of its own)
     if (with_flowdir && fuse_d8 && !c->ht && !c->hb) {
@@ -126,6 +141,7 @@ static int stage_noflat(mhip_ctx *c, hipStream_t s, bool shdg_done = false, Stag
     const int rc_nf = fill_noflat_dev(c->r[MHIP_R_DEM].as<float>(), c->r[MHIP_R_NOFLAT].as<double>(), H, W, c->sh, c->dg, s, &st,
                                       c->r[MHIP_R_FILLED].as<float>(), tail_hook, d8.flowdir ? &d8 : nullptr, ho);
     ctx_handover_settled(c, ho);
+    if (ho && ho->wet_pass) c->wet_pass_used = 1;
     MH_TRY(rc_nf);
     if (flowdir_done) *flowdir_done = d8.done;
     MH_TRY(stage_end(c, MHIP_STAGE_NOFLAT, s));
@@ -188,7 +204,8 @@ static int stage_accum(mhip_ctx *c, hipStream_t s, PourLink *pour = nullptr, Acc
     return MHIP_OK;
 }
 
-static int stage_label(mhip_ctx *c, hipStream_t s)
+// ho: the hand-over of this request, if any -- its wet bits are the foreground of the depths its first visit wrote (wet_ok)
+static int stage_label(mhip_ctx *c, hipStream_t s, const FillHandover *ho = nullptr)
 {
     const int64_t H = c->H, W = c->W, n = H * W;
     MH_ARG(c->have[MHIP_R_DEPTHS] || c->have[MHIP_R_FILLED], "LABEL needs bluespot depths");
@@ -199,8 +216,11 @@ static int stage_label(mhip_ctx *c, hipStream_t s)
     // (label_stats of the raw labels rides on the labelling's last pass: as two passes 21.8 -> 22.2 ms a step, and with the statistics
     // behind the stage's event -- beside the watersheds, off the critical path -- 22.3: round 4)
     ctx_wrote(c, MHIP_R_LABELS);
+    const unsigned long long *wet = ho && ho->wet_ok && c->have[MHIP_R_DEPTHS] ? ho->wet : nullptr;
+    bool wet_used = false;
     MH_TRY(ccl8_f32_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), c->tmp_i32.as<int32_t>(), H, W,
-                        &c->nlabels_raw, s, &c->raw_stats));
+                        &c->nlabels_raw, s, &c->raw_stats, wet, &wet_used));
+    if (wet_used) c->wet_label_used = 1;
     MH_TRY(stage_end(c, MHIP_STAGE_LABEL, s));
     c->have[MHIP_R_LABELS] = true;
     c->labels_components = true;
@@ -328,6 +348,14 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     FillHandover *const ho =
         ((mask & MHIP_STAGE_FILL) && (mask & MHIP_STAGE_NOFLAT) && c->nranks == 1 && !c->ht && !c->hb && fill_handover_env()) ? &handover : nullptr;
     c->fill_handover = 0;
+    // the wet bits of the hand-over (handover_addr.hpp): a buffer of this request -- from the pool, back with the request; the stages
+    // that may read them run on this context, in this call, behind the visit that writes them
+    c->wet_pass_used = c->wet_label_used = 0;
+    DevBuf wetbuf;
+    if (ho && wetbits_env() && c->H >= 3 && c->W >= 3) {
+        MH_TRY(wetbuf.alloc(8 * (size_t)ho::wet_words(c->W, (int)((c->H - 2 + ho::TI - 1) / ho::TI))));
+        handover.wet = wetbuf.as<unsigned long long>();
+    }
 
     if (!overlap) {
         if (mask & MHIP_STAGE_FILL) MH_TRY(stage_fill(c, s, true, ho));
@@ -335,7 +363,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
         if (mask & MHIP_STAGE_NOFLAT) MH_TRY(stage_noflat(c, s, false, nullptr, (mask & MHIP_STAGE_FLOWDIR) != 0, &fd_done, ho));
         if (mask & MHIP_STAGE_FLOWDIR) MH_TRY(fd_done ? stage_flowdir_fused(c, s) : stage_flowdir(c, s));
         if (mask & MHIP_STAGE_ACCUM) MH_TRY(stage_accum(c, s));
-        if (mask & MHIP_STAGE_LABEL) MH_TRY(stage_label(c, s));
+        if (mask & MHIP_STAGE_LABEL) MH_TRY(stage_label(c, s, ho));
         if (mask & MHIP_STAGE_WATERSHED) MH_TRY(stage_watershed(c, s));
         if (mask & MHIP_STAGE_POURPOINTS) MH_TRY(stage_pourpoints(c, s));
         return MHIP_OK;
@@ -428,7 +456,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
             int rc_l = rc_e == MHIP_OK ? fill_fut.get() : rc_e;   // ev_fork has been recorded on the main stream
             if (rc_l == MHIP_OK) rc_l = tail_fut.get();           // ... and ev_tail behind it (or at the same place)
             if (rc_l == MHIP_OK && hipStreamWaitEvent(sb, c->ev_tail, 0) != hipSuccess) rc_l = MHIP_EHIP;
-            if (rc_l == MHIP_OK && (mask & MHIP_STAGE_LABEL)) rc_l = stage_label(c, sb);   // incl. the bluespot depths
+            if (rc_l == MHIP_OK && (mask & MHIP_STAGE_LABEL)) rc_l = stage_label(c, sb, ho);   // incl. the bluespot depths
             else if (rc_l == MHIP_OK && do_fill && !c->have[MHIP_R_DEPTHS]) rc_l = stage_depths(c, sb);
             // both consumers (WATERSHED here, POURPOINTS on the main thread) want the final labels: settle them once
             if (rc_l == MHIP_OK && (mask & (MHIP_STAGE_WATERSHED | MHIP_STAGE_POURPOINTS)) && c->have[MHIP_R_LABELS]) {

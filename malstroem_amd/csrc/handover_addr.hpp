@@ -89,5 +89,36 @@ MH_HD inline bool own_col(const Win &w, int lane)
 }
 MH_HD inline int64_t store_index(const Win &w, int r, int lane) { return (w.r0 + r) * w.W + w.c0 + lane; }
 
+// ---- the wet bits: "F > dem" of a window column as one 64-bit word (bit r = window row r), kept per (tile row, raster column):
+// word ti * W + c, written by the one tile that owns column c in tile row ti (own_col).  Lane = column in the visit that writes
+// the words and in both kernels that read them (ng_finish_kernel, ccl_tile_kernel), so every access is a coalesced 8-byte word a
+// lane.  A reader takes the bit of raster row R from the word of the tile row that OWNS R -- (R - 1) / TI, bit R - ti * TI, in
+// 1 .. TI -- never from the copy a neighbouring window holds of it (rows 0 and 63), and takes a raster border cell as dry without
+// looking: there F is the elevation bit for bit.
+MH_HD inline int64_t wet_words(int64_t W, int ntr) { return (int64_t)ntr * W; }
+MH_HD inline int64_t wet_index(const Win &w, int lane) { return (int64_t)w.ti * w.W + w.c0 + lane; }
+// bytes of tile row ti's words from column c0 on: the records of the buffer the visit stores through (a lane behind them is dropped)
+MH_HD inline int64_t wet_bytes_behind(const Win &w) { return (w.W - w.c0) * 8; }
+MH_HD inline int wet_tile_row(int64_t R, int ntr)      // of any row: clamped into the tile grid (the clamp bites on border rows only)
+{
+    const int64_t t = (R < 1 ? 0 : R - 1) / TI;
+    return (int)(t < ntr - 1 ? t : ntr - 1);
+}
+// The bits of the rows R0 .. R0 + 63 of one column (bit i = row R0 + i), from the words of the tile rows t0 = wet_tile_row(R0), t0 + 1
+// and t0 + 2 (clamped like wet_tile_row; a reader of 32 rows passes anything for w2 and uses the low half).  Rows outside 1 .. H - 2 are dry.
+MH_HD inline uint64_t wet_rows64(uint64_t w0, uint64_t w1, uint64_t w2, int64_t R0, int64_t H, int ntr)
+{
+    const int t0 = wet_tile_row(R0, ntr);
+    const int s = (int)(R0 - (int64_t)t0 * TI);                  // bit of row R0 in w0: 0 (R0 == 0) .. TI
+    const int n0 = TI - s;                                      // rows 0 .. n0 of the 64 are w0's
+    const uint64_t lo0 = (2ull << n0) - 1ull;                   // (n0 <= 62)
+    const uint64_t lo1 = n0 + TI >= 63 ? ~0ull : (2ull << (n0 + TI)) - 1ull;      // rows n0 + 1 .. n0 + TI are w1's
+    const uint64_t p2 = n0 + TI < 64 ? w2 << ((n0 + TI) & 63) : 0ull;             // the rest (n0 <= 1 only) w2's
+    uint64_t m = ((w0 >> s) & lo0) | ((w1 << n0) & ~lo0 & lo1) | (p2 & ~lo1);
+    const int64_t inner = H - 1 - R0;                           // rows R0 .. H - 2
+    m &= inner >= 64 ? ~0ull : (inner <= 0 ? 0ull : (1ull << inner) - 1ull);
+    return R0 == 0 ? m & ~1ull : m;
+}
+
 }  // namespace ho
 }  // namespace mh

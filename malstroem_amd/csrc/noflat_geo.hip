@@ -119,6 +119,7 @@ struct GeoArgs {
     const uint16_t *ho_bslot;       // [H * W] basin slot of every interior cell
     const uint32_t *ho_tabV;        // [nt * NBMAX] final level keys (behind pf_final_kernel)
     float *ho_F, *ho_depths;        // outputs: the filled surface, filled - dem (may be null)
+    unsigned long long *ho_wet;     // output (may be null): the proof bits "F > dem", one word per tile row and raster column (handover_addr.hpp)
 };
 
 // 64 x 64 transpose of 32-bit words through a wave-private LDS scratch [64][65].  The DS instructions are written out: one
@@ -749,6 +750,18 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
                 proof_bad |= below;
                 // (two words from here on: seen through, `raised & bit` is the row's own comparison again, and all 64 stay live)
                 asm volatile("" : "+v"(raised[0]), "+v"(raised[1]));
+                // the wet bits of the columns this tile owns, for the finishing pass and the labelling of the same request: one 8-byte
+                // word a lane, here, where elevations, slots and levels are dead and F has not come back yet (nobody wants them: a
+                // buffer of no records, like the depths; so are the lanes behind the raster's last column)
+                {
+                    const int64_t wet_left = ho::wet_bytes_behind(w);
+                    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(
+                        (void *)(a.ho_wet ? a.ho_wet + ho::wet_index(w, 0) : (unsigned long long *)a.ho_F), 0,
+                        a.ho_wet ? (int)(wet_left < 0x7fffffff ? wet_left : 0x7fffffff) : 0, 0x00020000);
+                    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                    const u32x2 word = {raised[0], raised[1]};
+                    if (ocol) __builtin_amdgcn_raw_buffer_store_b64(word, rW, lane * 8, 0, 0);
+                }
                 // (F comes back from the wave's LDS scratch under new names: elevations, slots, levels and depths all end here -- as one
                 // live range from the loads to the classification's last row the register allocator spilled a hundred of them)
                 lds_wait();
@@ -1305,10 +1318,21 @@ __device__ __forceinline__ double dright(double v)
 // STORE == false (a chain request on one undivided context): the one store of G is left out -- nobody reads the surface in
 // such a request, the directions come from the registers -- and nothing else changes; whoever asks for G later gets it from F and
 // the distances (noflat_assemble_dev).
-template <bool D8, bool STORE = true>
+// WET (a request whose first visit was ng_handover_kernel and passed its proof): the DEM is not read.  Its one use is
+// the term max(.., dem), and the visit's proof bit "F > dem" of the cell answers for it: clear, dem == F, which this pass holds;
+// set, dem < F <= G, and max(m, dem) == G exactly when m == G -- so -inf stands in (m < dem fails either way).  A raster border cell is
+// dry without a look.  The lane fetches the two words of its column that cover the block's 32 rows (handover_addr.hpp: wet_rows64).
+__device__ __forceinline__ uint32_t ng_wet_rows(const unsigned long long *__restrict__ wet, int64_t rb, int64_t cc, int64_t H, int64_t W, int ntr, bool inner_col)
+{
+    const int t0 = ho::wet_tile_row(rb, ntr), t1 = t0 + 1 < ntr ? t0 + 1 : ntr - 1;
+    const uint64_t w0 = wet[(int64_t)t0 * W + cc], w1 = wet[(int64_t)t1 * W + cc];
+    return inner_col ? (uint32_t)ho::wet_rows64(w0, w1, 0ull, rb, H, ntr) : 0u;
+}
+template <bool D8, bool STORE = true, bool WET = false>
 __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict__ F, const uint32_t *__restrict__ d, const float *__restrict__ dem,
                                                         double *__restrict__ G, int64_t H, int64_t W, double sh, double dg, double seed_add, int fixed_top,
-                                                        int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir, unsigned int *nodir)
+                                                        int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir, unsigned int *nodir,
+                                                        const unsigned long long *__restrict__ wet, int ntr)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t c = ((int64_t)blockIdx.x * 4 + wave) * TI + lane - 1;
@@ -1319,21 +1343,28 @@ __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict_
     const bool inner_col = c > 0 && c + 1 < W;
     const double PINF = __builtin_inf();
     unsigned unreached = 0, bad = 0, anynodir = 0;
+    float fb = 0.0f, fn = 0.0f;      // WET: F of row r (where the cell is dry, its elevation) and of the row just loaded
     auto value = [&](int64_t r) -> double {
         if (!(r >= 0 && r < H && col_in)) return PINF;
         bool beyond;
-        const double v = ng_value(F[r * W + cc], d[r * W + cc], seed_add, &beyond);
+        fn = F[r * W + cc];
+        const double v = ng_value(fn, d[r * W + cc], seed_add, &beyond);
         unreached += beyond && mine && r >= rb && r < rb + FRB ? 1u : 0u;
         return v;
     };
+    uint32_t wrows = 0u;
+    if constexpr (WET) wrows = ng_wet_rows(wet, rb, cc, H, W, ntr, inner_col);
     double a = value(rb - 1), b = value(rb);
+    fb = fn;
     for (int i = 0; i < FRB; ++i) {
         const int64_t r = rb + i;
         if (r >= H) break;
         const double n = value(r + 1);
         const double al = dleft(a), ar = dright(a), bl = dleft(b), br = dright(b), nl = dleft(n), nr = dright(n);
         if (mine) {
-            const double dv = (double)dem[r * W + c];
+            double dv;
+            if constexpr (WET) dv = (wrows >> i) & 1u ? -PINF : (double)fb;
+            else dv = (double)dem[r * W + c];
             double want = dv;
             if (r > 0 && r < H - 1 && inner_col) {
                 const double md = fmin(fmin(al, ar), fmin(nl, nr)) + dg;
@@ -1355,6 +1386,7 @@ __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict_
         }
         a = b;
         b = n;
+        fb = fn;
     }
     if (unreached) atomicAdd(&counters[C_UNREACHED], (unsigned long long)unreached);
     if (bad) atomicAdd(&counters[C_MISMATCH], (unsigned long long)bad);
@@ -1381,10 +1413,11 @@ __global__ __launch_bounds__(256) void ng_finish_kernel(const float *__restrict_
 #define NG_FINISH_RESIDENCY
 #endif
 #if NG_FINISH_AHEAD
-template <bool STORE>
+template <bool STORE, bool WET>
 __device__ __forceinline__ void ng_finish_ahead(const float *__restrict__ F, const uint32_t *__restrict__ d, const float *__restrict__ dem,
                                                 double *__restrict__ G, int64_t H, int64_t W, double sh, double dg, double seed_add, int fixed_top,
-                                                int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir, unsigned int *nodir)
+                                                int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir, unsigned int *nodir,
+                                                const unsigned long long *__restrict__ wet, int ntr)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t c = ((int64_t)blockIdx.x * 4 + wave) * TI + lane - 1;
@@ -1395,15 +1428,32 @@ __device__ __forceinline__ void ng_finish_ahead(const float *__restrict__ F, con
     const bool inner_col = c > 0 && c + 1 < W;
     const double PINF = __builtin_inf();
     unsigned unreached = 0, bad = 0, anynodir = 0;
-    struct Row {
+    struct RowZ {
         float f, z;         // filled surface, DEM
         uint32_t dd;
     };
+    struct RowW {           // WET: the DEM is a bit of `wrows` and, where that is clear, f
+        float f;
+        uint32_t dd;
+    };
+    typedef typename std::conditional<WET, RowW, RowZ>::type Row;
     // from a cell of the raster whatever r and c are: value() knows which rows count, and the DEM is used where this lane writes
     // (there cc == c)
     auto load = [&](int64_t r) -> Row {
         const int64_t at = (r < 0 ? 0 : (r < H ? r : H - 1)) * W + cc;
-        return Row{F[at], dem[at], d[at]};
+        if constexpr (WET) return Row{F[at], d[at]};
+        else return Row{F[at], dem[at], d[at]};
+    };
+    // the DEM at (r, c) as the check wants it; WET: the low bit of `wrows` is the row's, and goes
+    uint32_t wrows = 0u;
+    if constexpr (WET) wrows = ng_wet_rows(wet, rb, cc, H, W, ntr, inner_col);      // (once per block, in flight with the first rows)
+    auto dem_of = [&](const Row &x) -> double {
+        if constexpr (WET) {
+            const double v = wrows & 1u ? -PINF : (double)x.f;
+            wrows >>= 1;
+            return v;
+        } else
+            return (double)x.z;
     };
     auto value = [&](int64_t r, const Row &x) -> double {
         if (!(r >= 0 && r < H && col_in)) return PINF;
@@ -1413,9 +1463,9 @@ __device__ __forceinline__ void ng_finish_ahead(const float *__restrict__ F, con
         return v;
     };
     const Row xa = load(rb - 1), xb = load(rb);
-    Row x0 = load(rb + 1), x1{0.0f, 0.0f, 0u};
+    Row x0 = load(rb + 1), x1{};
     double a = value(rb - 1, xa), b = value(rb, xb);
-    double dvb = (double)xb.z;                  // the DEM at (r, c): converted where its row is waited for, so that no loaded word
+    double dvb = dem_of(xb);                    // the DEM at (r, c): converted where its row is waited for, so that no loaded word
                                                 // has to be copied (a copy would be a wait for the loads just issued)
     // one row.  `xn`: the words of row r + 1, loaded a row ago; `xnn`: those of row r + 2, fetched now if another row follows in this
     // block (`more` is a type, not a value: a branch around the loads, even a uniform one, makes the compiler wait for them where
@@ -1425,7 +1475,7 @@ __device__ __forceinline__ void ng_finish_ahead(const float *__restrict__ F, con
         const double dv = dvb;
         if (decltype(more)::value) xnn = load(r + 2);
         const double n = value(r + 1, xn);
-        dvb = (double)xn.z;
+        dvb = dem_of(xn);
         asm volatile("" : "+v"(dvb));           // (here, not at the end of the row: the word's register is free for the next load)
         const double al = dleft(a), ar = dright(a), bl = dleft(b), br = dright(b), nl = dleft(n), nr = dright(n);
         if (mine && r < H) {
@@ -1463,17 +1513,19 @@ __device__ __forceinline__ void ng_finish_ahead(const float *__restrict__ F, con
     if (bad) atomicAdd(&counters[C_MISMATCH], (unsigned long long)bad);
     if (__any(anynodir != 0u) && lane == 0) *nodir = 1u;      // ("none" / "some": a plain store of the same value)
 }
-#define NG_FINISH_AHEAD_KERNEL(STORE)                                                                                                                  \
+#define NG_FINISH_AHEAD_KERNEL(STORE, WET)                                                                                                             \
     template <>                                                                                                                                        \
-    __global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true, STORE>(                                                          \
+    __global__ __launch_bounds__(256) NG_FINISH_RESIDENCY void ng_finish_kernel<true, STORE, WET>(                                                     \
         const float *__restrict__ F, const uint32_t *__restrict__ d, const float *__restrict__ dem, double *__restrict__ G, int64_t H, int64_t W,      \
         double sh, double dg, double seed_add, int fixed_top, int fixed_bot, unsigned long long *counters, uint8_t *__restrict__ flowdir,              \
-        unsigned int *nodir)                                                                                                                           \
+        unsigned int *nodir, const unsigned long long *__restrict__ wet, int ntr)                                                                      \
     {                                                                                                                                                  \
-        ng_finish_ahead<STORE>(F, d, dem, G, H, W, sh, dg, seed_add, fixed_top, fixed_bot, counters, flowdir, nodir);                                  \
+        ng_finish_ahead<STORE, WET>(F, d, dem, G, H, W, sh, dg, seed_add, fixed_top, fixed_bot, counters, flowdir, nodir, wet, ntr);                   \
     }
-NG_FINISH_AHEAD_KERNEL(true)
-NG_FINISH_AHEAD_KERNEL(false)
+NG_FINISH_AHEAD_KERNEL(true, false)
+NG_FINISH_AHEAD_KERNEL(false, false)
+NG_FINISH_AHEAD_KERNEL(true, true)
+NG_FINISH_AHEAD_KERNEL(false, true)
 #undef NG_FINISH_AHEAD_KERNEL
 #endif
 
@@ -1553,7 +1605,7 @@ int GeoRun::launch_rounds(hipStream_t s, int nb)
     a.H = H; a.W = W; a.ntr = m.ntr; a.ntc = m.ntc; a.nt = (int)m.nt; a.F = filled; a.d = dist; a.tab = m.d_tab; a.counters = m.d_cnt;
     a.blk = m.d_blk; a.hdr = m.d_hdr; a.mark = m.d_mark; a.list = m.d_list; a.fixed_top = fixed_top; a.fixed_bot = fixed_bot;
     a.append = 0; a.round_next = 0; a.amark = m.d_amark; a.list_next = nullptr; a.count_next = nullptr;
-    a.ho_dem = nullptr; a.ho_bslot = nullptr; a.ho_tabV = nullptr; a.ho_F = nullptr; a.ho_depths = nullptr;
+    a.ho_dem = nullptr; a.ho_bslot = nullptr; a.ho_tabV = nullptr; a.ho_F = nullptr; a.ho_depths = nullptr; a.ho_wet = nullptr;
     const unsigned grid = (unsigned)std::min<int64_t>((m.nt + 3) / 4, 512);
     for (int k = 0; k < nb; ++k, ++m.round) {
         a.maxcyc = m.maxcyc;
@@ -1561,7 +1613,7 @@ int GeoRun::launch_rounds(hipStream_t s, int nb)
         if (!m.round && handover && handover->pending) {
             // the flood's last pass and its proof ride on the classification (the flood cut the raster into the same tiles: begin() checked)
             a.ho_dem = handover->dem; a.ho_bslot = handover->bslot; a.ho_tabV = handover->tabV;
-            a.ho_F = handover->filled; a.ho_depths = handover->depths;
+            a.ho_F = handover->filled; a.ho_depths = handover->depths; a.ho_wet = handover->wet;
             hipLaunchKernelGGL(ng_handover_kernel, dim3(grid), dim3(256), m.lds, s, a);
             handover->queued = true;
             (void)hipEventRecord(m.span.back().first, s);
@@ -1681,6 +1733,7 @@ int GeoRun::begin(hipStream_t s, bool *applicable, bool *active)
             return MHIP_OK;
         }
         handover->release();
+        handover->wet_ok = handover->wet != nullptr;      // (the proof has passed: `raised` is "filled > dem" at every cell)
     }
     m.used = 1;
     m.irregular = h_c[C_IRREGULAR];
@@ -1753,15 +1806,23 @@ int GeoRun::end(hipStream_t s, bool *ok, FillStats *st)
     if (tail_hook) tail_hook->fire_at(StageHook::FINISH, s);
     const bool no_store = with_d8 && defer_out;      // (dist is the caller's raster then: it outlives this run)
     out_deferred = false;
-    if (no_store)
-        hipLaunchKernelGGL((ng_finish_kernel<true, false>), dim3((unsigned)((W + 4 * TI - 1) / (4 * TI)), (unsigned)((H + FRB - 1) / FRB)), dim3(256), 0, s, filled, dist,
-                           dem, out, H, W, sh, dg, seed_add, fixed_top, fixed_bot, m.d_cnt, d8_out, d8_nodir);
-    else if (with_d8)
-        hipLaunchKernelGGL(ng_finish_kernel<true>, dim3((unsigned)((W + 4 * TI - 1) / (4 * TI)), (unsigned)((H + FRB - 1) / FRB)), dim3(256), 0, s, filled, dist, dem,
-                           out, H, W, sh, dg, seed_add, fixed_top, fixed_bot, m.d_cnt, d8_out, d8_nodir);
-    else if (!partial)
-        hipLaunchKernelGGL(ng_finish_kernel<false>, dim3((unsigned)((W + 4 * TI - 1) / (4 * TI)), (unsigned)((H + FRB - 1) / FRB)), dim3(256), 0, s, filled, dist, dem,
-                           out, H, W, sh, dg, seed_add, fixed_top, fixed_bot, m.d_cnt, (uint8_t *)nullptr, (unsigned int *)nullptr);
+    // the wet bits of this request's first visit stand in for the DEM (begin(): the visit ran here and its proof passed)
+    const unsigned long long *wet = handover && handover->wet_ok && !fixed_top && !fixed_bot ? handover->wet : nullptr;
+    wet_used = false;
+    const dim3 fgrid((unsigned)((W + 4 * TI - 1) / (4 * TI)), (unsigned)((H + FRB - 1) / FRB));
+    auto finish = [&](auto d8_tag, auto store_tag, auto wet_tag, uint8_t *fd, unsigned int *nd) {
+        hipLaunchKernelGGL((ng_finish_kernel<decltype(d8_tag)::value, decltype(store_tag)::value, decltype(wet_tag)::value>), fgrid, dim3(256), 0, s, filled, dist, dem,
+                           out, H, W, sh, dg, seed_add, fixed_top, fixed_bot, m.d_cnt, fd, nd, wet, m.ntr);
+        wet_used = decltype(wet_tag)::value;
+    };
+    const std::true_type yes;
+    const std::false_type no;
+    if (no_store && wet) finish(yes, no, yes, d8_out, d8_nodir);
+    else if (no_store) finish(yes, no, no, d8_out, d8_nodir);
+    else if (with_d8 && wet) finish(yes, yes, yes, d8_out, d8_nodir);
+    else if (with_d8) finish(yes, yes, no, d8_out, d8_nodir);
+    else if (!partial && wet) finish(no, yes, yes, nullptr, nullptr);
+    else if (!partial) finish(no, yes, no, nullptr, nullptr);
     else              // (a partial surface is checked by the caller once the relaxation has settled the irregular flats)
         hipLaunchKernelGGL(ng_assemble_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, filled, dist, out, n, seed_add, m.d_cnt);
     MH_HIP(hipGetLastError());
@@ -1886,6 +1947,7 @@ int fill_noflat_geodesic_dev(const float *d_dem, const float *d_filled, double *
     MH_TRY(g.end(s, &ok, st));
     if (partial) *partial = g.partial;
     if (d8) { d8->done = g.d8_done; d8->deferred = g.out_deferred; }
+    if (ho) ho->wet_pass = g.wet_used;
     if (!ok && st) st->geo_reject = 2;
     return ok ? MHIP_OK : MHIP_ELIMIT;
 }

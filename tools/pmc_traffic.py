@@ -25,7 +25,10 @@ import sys
 COMPULSORY = {
     "d8s_kernel": (8, 1), "d8_kernel": (8, 1), "minmax_kernel": (4, 0), "pf_apply_check_kernel": (6, 8), "pf_apply_kernel": (6, 8),
     "pf_tile_kernel": (4, 2), "ng_first_kernel": (4, 5.1), "ng_handover_kernel": (6.4, 13.1), "ng_finish_kernel": (12, 8),
-    "ng_finish_kernel<true, false>": (12, 1),      # (a chain request: the surface is not stored, the directions are)
+    "ng_finish_kernel<true, false, false>": (12, 1),      # (a chain request: the surface is not stored, the directions are)
+    # ... and the DEM comes as the hand-over's wet bits, 64 bits per 62 rows of a column; so does the labelling's foreground
+    "ng_finish_kernel<true, false, true>": (8.13, 1), "ng_finish_kernel<true, true, true>": (8.13, 9), "ng_finish_kernel<false, true, true>": (8.13, 8),
+    "ccl_tile_kernel<float, true>": (0.13, 4),
     "ccl_tile_kernel": (4, 4),
     "ccl_emit_ranked_kernel": (4, 4), "stats_kernel": (8, 0), "count_kernel": (4, 0), "ws_tile_kernel": (5, 4), "ws_assign_hop_kernel": (8, 4),
     "arg_packed_kernel": (12, 0), "accum_tile_kernel": (1, 2), "accum_final_walk_kernel": (3, 8), "fill_check_kernel": (8, 0), "depths_kernel": (8, 4),
