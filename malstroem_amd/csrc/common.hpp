@@ -510,9 +510,28 @@ int wet_at_dev(const float *d_data, const int32_t *d_labels, int64_t n, int64_t 
 bool flow_distance_scale_ok(double scale);      // finite and > 0
 int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int64_t W, double scale, int64_t nlab, float *d_out, mhip_index_record *d_rec,
                       int64_t *unresolved, hipStream_t s);
-// the perimeter jumps of the flow distance's engine on two node arrays of ntiles * 256 slots (`cur` written by a tile pass, `nxt`
-// scratch); d_open: two zeroable words.  Afterwards `cur` is the array the final pass reads.  Synchronises.  (hand.hip runs them too.)
-int fdist_jumps_dev(uint4 *&cur, uint4 *&nxt, int64_t W, int64_t ntc, int64_t ntiles, unsigned int *d_open, hipStream_t s);
+// The walk down the D8 forest of one call (flowdist.hip owns it; flow_distance_dev, hand_dev and reach_catchments_dev run it): the
+// scratch words of the tile pass and, in `cur`, the node array a final pass reads behind the jumps.
+struct FlowWalk {
+    struct Misc {
+        unsigned int open[2];         // the jumps' `open` words of two launches
+        unsigned int bad, pad;        // the flow distance's "a label out of range"
+        unsigned long long count;     // the count of the final pass
+    };
+    DevBuf S, NA, NB, misc;
+    uint4 *cur = nullptr;
+    int64_t ntc = 0;
+    unsigned int *bad() { return &misc.as<Misc>()->bad; }
+    unsigned long long *count() { return &misc.as<Misc>()->count; }
+};
+bool flow_walk_fits(int64_t n);      // the int32 index domain of the scratch word
+// The limit check (MHIP_ELIMIT, `who` in the message), the buffers, `misc` cleared, the tile pass and the jumps.  An END of a walk is
+// a cell with d_acc >= threshold (d_acc != nullptr; float64, a NaN is none) or, with d_lab, a label != 0; without d_acc also a cell
+// that steps nowhere (flowdist.hip: walk_tile_kernel).  Synchronises.
+int flow_walk_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, const char *who, FlowWalk &w,
+                  hipStream_t s);
+// the count and the `bad` word of the final pass, once the stream is idle (the scratch and the nodes go back to the pool with `w`)
+int flow_walk_count(FlowWalk &w, int64_t *count, bool *bad, hipStream_t s);
 // hand.hip: height above the nearest drainage and the distance to it along the flow path.  A drainage cell:
 // d_acc >= threshold (float64; a NaN is none) or, with d_lab, a label != 0.  d_hand = elev[c] - elev[D(c)] (a NaN result is the
 // canonical quiet NaN), `nodata` for a cell whose walk ends without drainage; d_dist (optional) as flow_distance_dev's raster, -1
@@ -636,7 +655,8 @@ __device__ __forceinline__ int64_t ws_node_of(int32_t cell, uint32_t W, int ntc)
     return slot < 0 ? -1 : (int64_t)((r >> 6) * (uint32_t)ntc + (c >> 6)) * 256 + slot;
 }
 
-// ---- the scratch word, the node and the step pair of the flow distance's engine (flowdist.hip; hand.hip) ----------------------
+// ---- the scratch word, the node and the step pair of the walk (written by flowdist.hip: walk_tile_kernel, fdist_jump_kernel; read
+//      by the final passes of flowdist.hip and hand.hip) ---------------------------------------------------------------------------
 constexpr int32_t FD_NONE = 0x7fffffff;              // unresolved
 constexpr int32_t FD_DONE = (int32_t)0x80000000;     // | the global index of the terminal; without it: an entry cell (>= 0)
 constexpr double FD_SQRT2 = 1.4142135623730951;
@@ -671,6 +691,15 @@ template <int V> __device__ __forceinline__ void fd_load(const uint2 *__restrict
         s[0] = S[i0];
     }
 }
+// the count tail of a final pass: the wavefront's sum of `cnt`, one atomic per wavefront that counted anything
+__device__ __forceinline__ void fd_count_add(unsigned int cnt, unsigned long long *total)
+{
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) cnt += __shfl_xor(cnt, w);
+    if (cnt && (threadIdx.x & 63) == 0) atomicAdd(total, (unsigned long long)cnt);
+}
+// the instantiation of a final-pass kernel for a launch: four cells a thread where the rasters allow 16-byte accesses, else one
+template <typename K> inline K pick_v(bool vec, K k4, K k1) { return vec ? k4 : k1; }
 
 // open-addressing slot of `key` in an LDS table of TS (power of two) slots, -1 when the probe limit is hit (the caller
 // then falls back to the global atomics); keys[] holds -1 for an empty slot

@@ -1,6 +1,6 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
 // getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, the flow paths, the reach catchments and their flood depths, and the one
-// rule for what a write of a resident raster invalidates (ctx_wrote).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
+// rule for what a write of a resident raster invalidates (ctx_wrote) and the one test for a raster held outside mhip_raster (ctx_held).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
 #include <mutex>
 #include <new>
 #include <string>
@@ -119,6 +119,33 @@ int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, 
     MH_HIP(hipMemcpyAsync(up ? (void *)dev : host, up ? host : (void *)dev, rowb * (size_t)nrows, kind, cs(c)));
     MH_HIP(stream_sync(cs(c)));      // (an upload's caller reuses its window buffer)
     return MHIP_OK;
+}
+
+int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes)
+{
+    const struct { bool held; const DevBuf &buf; const char *needs; } t[HELD_COUNT_] = {      // (in the order of the enumeration)
+        {c->wetat_events > 0, c->wetat_out, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels"},
+        {c->fdist_unresolved >= 0, c->fdist_out, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels"},
+        {c->hand_undrained >= 0, c->hand_out, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters"},      // (the two are made and dropped
+        {c->hand_undrained >= 0, c->hand_dist, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters"},     // together: one is there, both are)
+        {c->rcatch_nreach >= 0, c->rcatch_out, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters"},
+        {c->inund_held > 0, c->inund_out, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments"},
+        {c->nzone >= 0, c->zones, "ctx_zones_rows needs mhip_ctx_rasterize_zones"},
+    };
+    MH_ARG(t[id].held && t[id].buf.p, t[id].needs);
+    *ptr = t[id].buf.p;
+    if (elem_bytes) *elem_bytes = 4;      // (float32 or int32, every one)
+    return MHIP_OK;
+}
+
+// every mhip_ctx_*_rows getter of a held raster: the window check (`sig` names the call), the validity test, the copy
+static int held_rows(mhip_ctx *c, int id, int64_t row0, int64_t nrows, void *dst, const char *sig)
+{
+    MH_ARG(c && dst && id >= 0 && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, sig);
+    void *p = nullptr;
+    size_t eb = 0;
+    MH_TRY(ctx_held(c, id, &p, &eb));
+    return ctx_copy_rows(c, p, eb, row0, nrows, dst, hipMemcpyDeviceToHost);
 }
 
 int ctx_noflat(mhip_ctx *c, double **g)
@@ -640,9 +667,7 @@ int mhip_ctx_wet_at(mhip_ctx *c, int32_t K, const double *q, const float *values
 
 int mhip_ctx_wet_at_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
 {
-    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_wet_at_rows(ctx, row0, nrows, dst)");
-    MH_ARG(c->wetat_events > 0 && c->wetat_out.p, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels");
-    return ctx_copy_rows(c, c->wetat_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+    return held_rows(c, HELD_WETAT, row0, nrows, dst, "ctx_wet_at_rows(ctx, row0, nrows, dst)");
 }
 
 /* ---- flow distance to the receiving bluespot, longest flow path per watershed (flowdist.hip) ------------------------------------ */
@@ -670,9 +695,7 @@ int mhip_ctx_flow_distance(mhip_ctx *c, double scale, int64_t *unresolved)
 
 int mhip_ctx_flow_distance_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
 {
-    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_flow_distance_rows(ctx, row0, nrows, dst)");
-    MH_ARG(c->fdist_unresolved >= 0 && c->fdist_out.p, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels");
-    return ctx_copy_rows(c, c->fdist_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+    return held_rows(c, HELD_FLOWDIST, row0, nrows, dst, "ctx_flow_distance_rows(ctx, row0, nrows, dst)");
 }
 
 int mhip_ctx_flow_distance_records(mhip_ctx *c, mhip_index_record *records)
@@ -714,9 +737,7 @@ int mhip_ctx_hand(mhip_ctx *c, int32_t elev_source, double threshold, int32_t st
 
 int mhip_ctx_hand_rows(mhip_ctx *c, int32_t which, int64_t row0, int64_t nrows, float *dst)
 {
-    MH_ARG(c && dst && (which == 0 || which == 1) && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_hand_rows(ctx, which, row0, nrows, dst)");
-    MH_ARG(c->hand_undrained >= 0 && c->hand_out.p && c->hand_dist.p, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters");
-    return ctx_copy_rows(c, which ? c->hand_dist.p : c->hand_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+    return held_rows(c, which == 0 ? HELD_HAND : which == 1 ? HELD_DRAINDIST : -1, row0, nrows, dst, "ctx_hand_rows(ctx, which, row0, nrows, dst)");
 }
 
 /* ---- DEM adaptations: culvert and dike lines into the resident DEM (burn.hip) ---------------------------------------------------- */
@@ -755,45 +776,25 @@ int mhip_ctx_rasterize_zones(mhip_ctx *c, int64_t nvert, const double *xy, int64
 
 int mhip_ctx_zones_rows(mhip_ctx *c, int64_t row0, int64_t nrows, int32_t *dst)
 {
-    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_zones_rows(ctx, row0, nrows, dst)");
-    MH_ARG(c->nzone >= 0 && c->zones.p, "ctx_zones_rows needs mhip_ctx_rasterize_zones");
-    return ctx_copy_rows(c, c->zones.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+    return held_rows(c, HELD_ZONES, row0, nrows, dst, "ctx_zones_rows(ctx, row0, nrows, dst)");
 }
 
 int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
 {
     MH_ARG(c && records, "ctx_zone_stats(ctx, source, records)");
     MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
-    const float *src = nullptr;
-    switch (source) {
-    case MHIP_R_DEM: case MHIP_R_FILLED: case MHIP_R_DEPTHS: case MHIP_R_FINALDEPTHS:
-        MH_ARG(c->have[source], "raster has not been computed or uploaded");
-        src = c->r[source].as<float>();
-        break;
-    case MHIP_ZSRC_WETAT:
-        MH_ARG(c->wetat_events > 0 && c->wetat_out.p, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels");
-        src = c->wetat_out.as<float>();
-        break;
-    case MHIP_ZSRC_FLOWDIST:
-        MH_ARG(c->fdist_unresolved >= 0 && c->fdist_out.p, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels");
-        src = c->fdist_out.as<float>();
-        break;
-    case MHIP_ZSRC_HAND: case MHIP_ZSRC_DRAINDIST:
-        MH_ARG(c->hand_undrained >= 0 && c->hand_out.p && c->hand_dist.p, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters");
-        src = source == MHIP_ZSRC_HAND ? c->hand_out.as<float>() : c->hand_dist.as<float>();
-        break;
-    case MHIP_ZSRC_INUNDATION:
-        MH_ARG(c->inund_held > 0 && c->inund_out.p, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments");
-        src = c->inund_out.as<float>();
-        break;
-    default:
-        MH_ARG(false, "ctx_zone_stats: the source is no float32 raster of the context");
-    }
+    const bool member = source == MHIP_R_DEM || source == MHIP_R_FILLED || source == MHIP_R_DEPTHS || source == MHIP_R_FINALDEPTHS;
+    const int id = source == MHIP_ZSRC_WETAT ? HELD_WETAT : source == MHIP_ZSRC_FLOWDIST ? HELD_FLOWDIST : source == MHIP_ZSRC_HAND ? HELD_HAND :
+                   source == MHIP_ZSRC_DRAINDIST ? HELD_DRAINDIST : source == MHIP_ZSRC_INUNDATION ? HELD_INUNDATION : -1;
+    MH_ARG(member || id >= 0, "ctx_zone_stats: the source is no float32 raster of the context");
+    void *src = member ? c->r[source].p : nullptr;
+    if (member) MH_ARG(c->have[source], "raster has not been computed or uploaded");
+    else MH_TRY(ctx_held(c, id, &src));
     MH_ARG(c->nzone >= 0 && c->zones.p, "ctx_zone_stats needs mhip_ctx_rasterize_zones");
     MH_HIP(hipSetDevice(c->device));
     DevBuf d_rec;
     MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(c->nzone + 1)));
-    MH_TRY(zone_stats_dev(src, c->zones.as<int32_t>(), c->H * c->W, c->W, c->nzone, d_rec.as<mhip_zone_record>(), c->stream));
+    MH_TRY(zone_stats_dev((const float *)src, c->zones.as<int32_t>(), c->H * c->W, c->W, c->nzone, d_rec.as<mhip_zone_record>(), c->stream));
     return ctx_fetch(c, d_rec, sizeof(mhip_zone_record) * (size_t)(c->nzone + 1), records);
 }
 
@@ -804,7 +805,8 @@ int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
     MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS || source == MHIP_PSRC_REACHCATCH,
            "ctx_polygonize: the source is MHIP_R_LABELS or MHIP_R_WATERSHEDS, or MHIP_PSRC_REACHCATCH for the reach catchments");
     MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "outlines on a row band are not built (a ring crosses the seams: a later step); use an undivided context");
-    if (source == MHIP_PSRC_REACHCATCH) MH_ARG(c->rcatch_nreach >= 0 && c->rcatch_out.p, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters");
+    void *held = nullptr;
+    if (source == MHIP_PSRC_REACHCATCH) MH_TRY(ctx_held(c, HELD_REACHCATCH, &held));
     else MH_ARG(c->have[source], "raster has not been computed or uploaded");
     if (source == MHIP_R_LABELS) MH_ARG(c->labels_filtered && !c->ccl_pending, "ctx_polygonize needs mhip_ctx_apply_keep after the LABEL run");
     MH_TRY(polygonize_check(c->H, c->W));
@@ -815,7 +817,7 @@ int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
         return MHIP_EHIP;
     }
     p->device = c->device;
-    const int32_t *d_src = source == MHIP_PSRC_REACHCATCH ? c->rcatch_out.as<int32_t>() : c->r[source].as<int32_t>();
+    const int32_t *d_src = held ? (const int32_t *)held : c->r[source].as<int32_t>();
     const int rc = polygonize_dev(d_src, c->H, c->W, p->xy, p->ring_offsets, p->ring_label, &p->nring, &p->nvert, c->stream);      // (synchronises)
     if (rc != MHIP_OK) {
         delete p;
@@ -894,17 +896,16 @@ int mhip_ctx_reach_catchments(mhip_ctx *c, double threshold, int32_t stop_at_lab
 
 int mhip_ctx_reach_catchments_rows(mhip_ctx *c, int64_t row0, int64_t nrows, int32_t *dst)
 {
-    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_reach_catchments_rows(ctx, row0, nrows, dst)");
-    MH_ARG(c->rcatch_nreach >= 0 && c->rcatch_out.p, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters");
-    return ctx_copy_rows(c, c->rcatch_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+    return held_rows(c, HELD_REACHCATCH, row0, nrows, dst, "ctx_reach_catchments_rows(ctx, row0, nrows, dst)");
 }
 
 int mhip_ctx_inundate(mhip_ctx *c, int64_t nreach, const float *stage, mhip_zone_record *records)
 {
     MH_ARG(c && stage, "ctx_inundate(ctx, nreach, stage, records)");
     MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "inundation on a row band is not built (a path crosses the seams: a later step); use an undivided context");
-    MH_ARG(c->hand_undrained >= 0 && c->hand_out.p, "ctx_inundate needs mhip_ctx_hand on the resident rasters");
-    MH_ARG(c->rcatch_nreach >= 0 && c->rcatch_out.p, "ctx_inundate needs mhip_ctx_reach_catchments on the resident rasters");
+    void *hand = nullptr, *rcatch = nullptr;
+    MH_ARG(ctx_held(c, HELD_HAND, &hand) == MHIP_OK, "ctx_inundate needs mhip_ctx_hand on the resident rasters");
+    MH_ARG(ctx_held(c, HELD_REACHCATCH, &rcatch) == MHIP_OK, "ctx_inundate needs mhip_ctx_reach_catchments on the resident rasters");
     MH_ARG(c->hand_thr == c->rcatch_thr, "ctx_inundate: the hand and the reach catchments were made with different thresholds");
     MH_ARG(c->hand_labels == c->rcatch_labels, "ctx_inundate: the hand and the reach catchments were made with different stop_at_labels");
     MH_ARG(nreach == c->rcatch_nreach, "ctx_inundate: nreach is not the number of reaches of the catchments held");
@@ -915,7 +916,7 @@ int mhip_ctx_inundate(mhip_ctx *c, int64_t nreach, const float *stage, mhip_zone
     MH_TRY(upload(d_stage, stage, 4 * ((size_t)nreach + 1), c->stream));
     if (records) MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(nreach + 1)));
     MH_TRY(c->inund_out.alloc(4 * (size_t)n));
-    const int rc = inundate_dev(c->hand_out.as<float>(), c->rcatch_out.as<int32_t>(), n, c->W, nreach, d_stage.as<float>(), c->hand_nodata,
+    const int rc = inundate_dev((const float *)hand, (const int32_t *)rcatch, n, c->W, nreach, d_stage.as<float>(), c->hand_nodata,
                                 c->inund_out.as<float>(), records ? d_rec.as<mhip_zone_record>() : nullptr, c->stream);      // (synchronises)
     if (rc != MHIP_OK) {
         c->inund_out.release();
@@ -928,9 +929,7 @@ int mhip_ctx_inundate(mhip_ctx *c, int64_t nreach, const float *stage, mhip_zone
 
 int mhip_ctx_inundation_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
 {
-    MH_ARG(c && dst && row0 >= 0 && nrows >= 1 && row0 + nrows <= c->H_owned, "ctx_inundation_rows(ctx, row0, nrows, dst)");
-    MH_ARG(c->inund_held > 0 && c->inund_out.p, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments");
-    return ctx_copy_rows(c, c->inund_out.p, 4, row0, nrows, dst, hipMemcpyDeviceToHost);
+    return held_rows(c, HELD_INUNDATION, row0, nrows, dst, "ctx_inundation_rows(ctx, row0, nrows, dst)");
 }
 
 }  // extern "C"

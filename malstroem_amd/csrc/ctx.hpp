@@ -1,6 +1,8 @@
 // ctx.hpp -- the device-resident context behind the mhip_ctx_* entry points (DemTool / BluespotTool pipeline, reference dem.py:53-93,
 // bluespots.py:138-216), shared by ctx.hip (life cycle, transfers, getters, records, hypsometry), ctx_run.hip (the stage DAG of
 // mhip_ctx_run) and ctx_band.hip (the row-band protocol).
+//   ctx_wrote   ctx.hip   what a write of a resident raster invalidates: every writer calls it
+//   ctx_held    ctx.hip   whether a raster held outside mhip_raster is valid, and where it is: every reader calls it
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -253,6 +255,12 @@ inline int ctx_settle(mhip_ctx *c, int which, bool write)
 // included) of `elem_bytes` per cell, to or from `host` by `kind`: one copy on cs(c), then one synchronisation.  The caller has
 // checked the window against H_owned.  Every whole-raster and windowed transfer of ctx.hip is this call.
 int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, int64_t nrows, void *host, hipMemcpyKind kind);
+// ---- the rasters a context holds outside mhip_raster, wherever they are read (ctx.hip) ------------------------------------------
+// wet_at, flow distance, hand and the distance to the drainage, reach catchments, inundation depths, zones: each lives behind a
+// sentinel of its own, which the drop_* functions of ctx.hip clear.  ctx_held is the one test "is it held, and where": MHIP_EINVAL
+// with the message of that raster's mhip_ctx_*_rows getter, or the device pointer and (optional) the bytes of an element.
+enum HeldRaster { HELD_WETAT, HELD_FLOWDIST, HELD_HAND, HELD_DRAINDIST, HELD_REACHCATCH, HELD_INUNDATION, HELD_ZONES, HELD_COUNT_ };
+int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes = nullptr);
 // `bytes` of a record buffer to `host` on the main stream, synchronised: every record getter after its validity test
 int ctx_fetch(mhip_ctx *c, const DevBuf &buf, size_t bytes, void *host);
 // the fork / join events of the two branches (mhip_ctx_side_begin, mhip_ctx_run), created once

@@ -9,6 +9,8 @@
 // The engine is the watersheds' fast path (watershed.hip) with a payload: a tile pass resolves the 64 x 64 tiles in LDS, the tiles'
 // perimeter cells -- the only cells a path enters a tile at -- are jumped on their compact array, a final pass takes the last hop.
 // The same kernels take flow directions of any origin: a no-direction cell is a terminal, a cycle is what never reaches one.
+// This file owns the walk -- the tile pass, the jumps and their setup (FlowWalk, flow_walk_dev: common.hpp); hand.hip runs it with the
+// drainage test and ends it in final passes of its own.
 #include <algorithm>
 #include <cmath>
 
@@ -18,25 +20,32 @@ namespace mh {
 namespace {
 
 constexpr int WT = WS_TILE;
-constexpr int FD_HOPS = 5;      // (FD_NONE, FD_DONE, the step pair and the decoding of a scratch word: common.hpp, shared with hand.hip)
+constexpr int FD_HOPS = 5;      // (FD_NONE, FD_DONE, the step pair and the decoding of a scratch word: common.hpp, shared with hand.hip's final passes)
 
 // ---- tile pass ---------------------------------------------------------------------------------------------------------------
 // One workgroup per 64 x 64 tile; pull-only pointer doubling on 16-bit tile-local indices as in ws_tile_kernel, and every cell
 // carries the pair of its pointer: pair[c] += pair[ptr[c]]; ptr[c] = ptr[ptr[c]].  Unlike the bare pointers the (pointer, pair) of a
 // cell must be read as one state, so a round reads, meets at the vote's barrier, then writes.  12 rounds cover 4096 steps: a
-// pointer that is not at a terminal or an exit after them is caught in a cycle of the tile.
-// Scratch S, 8 bytes a cell: x = terminal | FD_DONE (a terminal of this tile), the entry cell of the neighbouring tile the path
-// continues at (>= 0), or FD_NONE; y = the packed pair up to there.  The perimeter cells also go to their nodes (x, no, nd, 0).
+// pointer that is not at an end or an exit after them is caught in a cycle of the tile.
+// The ends of a walk, in both instantiations (the flow distance runs <false>; hand and the reach catchments run <true>):
+//   END    a cell whose mask bit is set -- DRAIN: accum >= thr or, with `lab`, a label != 0; !DRAIN: with `lab`, a label != 0 --
+//          and, !DRAIN only, a cell without the bit that steps nowhere (a code > 7, or a step out of the raster)
+//   dead   DRAIN only: a cell without the bit that steps nowhere
+//   entry  the cell of the neighbouring tile at which a path that leaves this tile continues
+// Scratch S, 8 bytes a cell: x = END | FD_DONE (an END of this tile), the entry cell (>= 0), or FD_NONE (the walk reaches a dead
+// cell, or still moves after the rounds: a flow cycle); y = the packed pair up to there, 0 with FD_NONE.  The perimeter cells also go
+// to their nodes (x, no, nd, 0): the jumps and the decoding know no third kind of end.
 // LDS: ptr 8 KB + val 4 KB + pairs 16 KB = 28 KB: five workgroups a CU.
-__global__ __launch_bounds__(256) void fdist_tile_kernel(const uint8_t *__restrict__ fd, const int32_t *__restrict__ lab, uint2 *__restrict__ S,
-                                                        int64_t H, int64_t W, int ntc, uint4 *__restrict__ Nn)
+template <bool DRAIN>
+__global__ __launch_bounds__(256) void walk_tile_kernel(const uint8_t *__restrict__ fd, const double *__restrict__ acc, const int32_t *__restrict__ lab,
+                                                       double thr, uint2 *__restrict__ S, int64_t H, int64_t W, int ntc, uint4 *__restrict__ Nn)
 {
     __shared__ uint16_t ptr[WT * WT];
-    // V_TERM a terminal, 0..7 the direction in which the path leaves the tile here, V_MOVE a cell that steps on inside the tile.  (A
+    // V_END, V_DEAD: above; 0..7 the direction in which the path leaves the tile here, V_MOVE a cell that steps on inside the tile.  (A
     // pointer on a cycle whose length divides 2**round points at its own cell: only `val` tells that cell from a fixed point.)
     __shared__ uint8_t val[WT * WT];
     __shared__ uint32_t pr[WT * WT];
-    constexpr uint8_t V_TERM = 8, V_MOVE = 9;
+    constexpr uint8_t V_END = 8, V_MOVE = 9, V_DEAD = 10;
     const int ti = blockIdx.x / ntc, tj = blockIdx.x - ti * ntc;
     const int64_t r0 = (int64_t)ti * WT, c0 = (int64_t)tj * WT;
     // global I/O: a thread owns 16 consecutive cells of a tile row
@@ -44,16 +53,23 @@ __global__ __launch_bounds__(256) void fdist_tile_kernel(const uint8_t *__restri
     const int64_t r = r0 + lr, cbase = c0 + lc0;
     const bool vec = (W & 15) == 0 && r < H && cbase + 16 <= W;     // whole, 16-byte aligned group
     uint8_t code[16];
-    uint32_t lmask = 0;      // my labelled cells
+    uint32_t mask = 0;      // my cells whose bit is set
     if (vec) {
         const uint4 cv = *reinterpret_cast<const uint4 *>(fd + r * W + cbase);
         memcpy(code, &cv, 16);
+        if constexpr (DRAIN) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const double2 av = *reinterpret_cast<const double2 *>(acc + r * W + cbase + 2 * q);
+                mask |= (av.x >= thr ? 1u : 0u) << (2 * q) | (av.y >= thr ? 2u : 0u) << (2 * q);
+            }
+        }
         if (lab) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int4 lv = *reinterpret_cast<const int4 *>(lab + r * W + cbase + 4 * q);
-                lmask |= (lv.x != 0 ? 1u : 0u) << (4 * q) | (lv.y != 0 ? 2u : 0u) << (4 * q) | (lv.z != 0 ? 4u : 0u) << (4 * q) |
-                         (lv.w != 0 ? 8u : 0u) << (4 * q);
+                mask |= (lv.x != 0 ? 1u : 0u) << (4 * q) | (lv.y != 0 ? 2u : 0u) << (4 * q) | (lv.z != 0 ? 4u : 0u) << (4 * q) |
+                        (lv.w != 0 ? 8u : 0u) << (4 * q);
             }
         }
     } else {
@@ -61,19 +77,22 @@ __global__ __launch_bounds__(256) void fdist_tile_kernel(const uint8_t *__restri
         for (int k = 0; k < 16; ++k) {
             const bool in = r < H && cbase + k < W;
             code[k] = in ? fd[r * W + cbase + k] : (uint8_t)8;
-            if (in && lab && lab[r * W + cbase + k] != 0) lmask |= 1u << k;
+            bool bit = in && lab && lab[r * W + cbase + k] != 0;
+            if constexpr (DRAIN) bit = bit || (in && acc[r * W + cbase + k] >= thr);
+            if (bit) mask |= 1u << k;
         }
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const int li = lr * WT + lc0 + k;
+        const bool bit = (mask >> k) & 1u;
         uint16_t p = (uint16_t)li;
-        uint8_t v = V_TERM;
+        uint8_t v = (bit || !DRAIN) ? V_END : V_DEAD;      // (a cell outside the raster: nothing points at it)
         uint32_t a = 0;
-        if (r < H && cbase + k < W && !((lmask >> k) & 1u) && code[k] <= 7u) {
+        if (r < H && cbase + k < W && !bit && code[k] <= 7u) {
             const int lr2 = lr + dir_dr((int)code[k]), lc2 = lc0 + k + dir_dc((int)code[k]);
             const int64_t nr = r0 + lr2, nc = c0 + lc2;
-            if (nr >= 0 && nr < H && nc >= 0 && nc < W) {      // (else: the step leaves the raster, the cell is a terminal)
+            if (nr >= 0 && nr < H && nc >= 0 && nc < W) {      // (else: the step leaves the raster, the cell steps nowhere)
                 if (lr2 >= 0 && lr2 < WT && lc2 >= 0 && lc2 < WT) {
                     p = (uint16_t)(lr2 * WT + lc2);
                     v = V_MOVE;
@@ -109,6 +128,7 @@ __global__ __launch_bounds__(256) void fdist_tile_kernel(const uint8_t *__restri
         }
         __syncthreads();
     }
+    // (every value is computed and then selected, not set in the arms of a branch: fdist_final_kernel's note on the compiler)
 #pragma unroll
     for (int k = 0; k < 16; k += 2) {
         uint2 o[2];
@@ -116,19 +136,12 @@ __global__ __launch_bounds__(256) void fdist_tile_kernel(const uint8_t *__restri
         for (int e = 0; e < 2; ++e) {
             const int li = lr * WT + lc0 + k + e;
             const int t = ptr[li];
-            uint32_t a = pr[li];
-            int32_t tgt = FD_NONE;
             const unsigned vb = val[t];
-            if (vb != V_MOVE) {      // (else: a flow cycle inside the tile)
-                const int64_t tr = r0 + (t >> 6), tc = c0 + (t & 63);
-                if (vb == V_TERM) tgt = (int32_t)(tr * W + tc) | FD_DONE;
-                else {
-                    tgt = (int32_t)((tr + dir_dr((int)vb)) * W + tc + dir_dc((int)vb));
-                    a += fd_step(vb);
-                }
-            } else {
-                a = 0;
-            }
+            const int64_t tr = r0 + (t >> 6), tc = c0 + (t & 63);
+            const bool leaves = vb <= 7u;      // (V_MOVE: a flow cycle inside the tile; V_DEAD: an end without drainage)
+            const int32_t entry = (int32_t)((tr + dir_dr((int)(vb & 7u))) * W + tc + dir_dc((int)(vb & 7u)));
+            const int32_t tgt = vb == V_END ? ((int32_t)(tr * W + tc) | FD_DONE) : leaves ? entry : FD_NONE;
+            const uint32_t a = vb == V_END ? pr[li] : leaves ? pr[li] + fd_step(vb) : 0u;
             o[e] = make_uint2((uint32_t)tgt, a);
             const int slot = ws_perim_slot(lr, lc0 + k + e);
             if (slot >= 0) {
@@ -207,9 +220,7 @@ __global__ __launch_bounds__(256) void fdist_final_kernel(const uint2 *__restric
         if constexpr (V == 4) *reinterpret_cast<float4 *>(out + i0) = make_float4(o[0], o[1], o[2], o[3]);
         else out[i0] = o[0];
     }
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) cnt += __shfl_xor(cnt, w);
-    if (cnt && (threadIdx.x & 63) == 0) atomicAdd(unres, (unsigned long long)cnt);
+    fd_count_add(cnt, unres);
 }
 
 // The raster and the largest key per label of the terminal.  The pair is exact in registers here, so u is compared in float64
@@ -290,9 +301,7 @@ __global__ __launch_bounds__(256) void fdist_final_rec_kernel(const uint2 *__res
         }
         __syncthreads();
     }
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) cnt += __shfl_xor(cnt, w);
-    if (cnt && (threadIdx.x & 63) == 0) atomicAdd(unres, (unsigned long long)cnt);
+    fd_count_add(cnt, unres);
     if (any_bad) atomicOr(bad, 1u);
 }
 
@@ -340,7 +349,9 @@ __global__ __launch_bounds__(256) void fdist_records_kernel(const unsigned long 
 
 bool flow_distance_scale_ok(double scale) { return std::isfinite(scale) && scale > 0.0; }
 
-int fdist_jumps_dev(uint4 *&cur, uint4 *&nxt, int64_t W, int64_t ntc, int64_t ntiles, unsigned int *d_open, hipStream_t s)
+// the perimeter jumps on two node arrays of ntiles * 256 slots (`cur` written by the tile pass, `nxt` scratch); d_open: two zeroable
+// words.  Afterwards `cur` is the array the final pass reads.  Synchronises.
+static int fdist_jumps_dev(uint4 *&cur, uint4 *&nxt, int64_t W, int64_t ntc, int64_t ntiles, unsigned int *d_open, hipStream_t s)
 {
     constexpr int MAX_ROUNDS = 40;      // the watersheds' cap; nodes on a cycle across tiles are still open then
     for (int round = 0; round < MAX_ROUNDS;) {
@@ -359,57 +370,74 @@ int fdist_jumps_dev(uint4 *&cur, uint4 *&nxt, int64_t W, int64_t ntc, int64_t nt
     return MHIP_OK;
 }
 
+bool flow_walk_fits(int64_t n) { return n < (int64_t)FD_NONE - 1; }
+
+int flow_walk_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab, int64_t H, int64_t W, double threshold, const char *who, FlowWalk &w,
+                  hipStream_t s)
+{
+    const int64_t n = H * W;
+    if (!flow_walk_fits(n)) {
+        set_error("%s: %lld cells exceed the int32 index domain", who, (long long)n);
+        return MHIP_ELIMIT;
+    }
+    const int64_t ntr = cdiv(H, WT), ntc = cdiv(W, WT), ntiles = ntr * ntc, nnodes = ntiles * 256;
+    MH_TRY(w.S.alloc(8 * (size_t)n));
+    MH_TRY(w.NA.alloc(16 * (size_t)nnodes));
+    MH_TRY(w.NB.alloc(16 * (size_t)nnodes));
+    MH_TRY(w.misc.alloc(sizeof(FlowWalk::Misc)));
+    MH_HIP(hipMemsetAsync(w.misc.p, 0, sizeof(FlowWalk::Misc), s));
+    hipLaunchKernelGGL(d_acc ? walk_tile_kernel<true> : walk_tile_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, s, d_fd, d_acc, d_lab, threshold,
+                       w.S.as<uint2>(), H, W, (int)ntc, w.NA.as<uint4>());
+    uint4 *nxt = w.NB.as<uint4>();
+    w.cur = w.NA.as<uint4>();
+    w.ntc = ntc;
+    return fdist_jumps_dev(w.cur, nxt, W, ntc, ntiles, w.misc.as<FlowWalk::Misc>()->open, s);
+}
+
+int flow_walk_count(FlowWalk &w, int64_t *count, bool *bad, hipStream_t s)
+{
+    MH_HIP(hipGetLastError());
+    FlowWalk::Misc h = {};
+    MH_HIP(hipMemcpyAsync(&h, w.misc.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
+    if (count) *count = (int64_t)h.count;
+    if (bad) *bad = h.bad != 0;
+    return MHIP_OK;
+}
+
 int flow_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, int64_t H, int64_t W, double scale, int64_t nlab, float *d_out, mhip_index_record *d_rec,
                       int64_t *unresolved, hipStream_t s)
 {
     const int64_t n = H * W;
-    if (n >= (int64_t)FD_NONE - 1) {
-        set_error("flow_distance: %lld cells exceed the int32 index domain", (long long)n);
-        return MHIP_ELIMIT;
-    }
-    const int64_t ntr = cdiv(H, WT), ntc = cdiv(W, WT), ntiles = ntr * ntc, nnodes = ntiles * 256;
-    DevBuf S, NA, NB, misc, key, head;
-    MH_TRY(S.alloc(8 * (size_t)n));
-    MH_TRY(NA.alloc(16 * (size_t)nnodes));
-    MH_TRY(NB.alloc(16 * (size_t)nnodes));
-    // misc: [0], [1] the `open` words of two launches, [2] a label out of range, [4..5] the unresolved cells (64 bits)
-    MH_TRY(misc.alloc(32));
-    MH_HIP(hipMemsetAsync(misc.p, 0, 32, s));
-    unsigned int *d_open = misc.as<unsigned int>(), *d_bad = d_open + 2;
-    unsigned long long *d_unres = misc.as<unsigned long long>() + 2;
+    FlowWalk w;
+    MH_TRY(flow_walk_dev(d_fd, nullptr, d_lab, H, W, 0.0, "flow_distance", w, s));
+    const uint2 *S = w.S.as<uint2>();
+    const int ntc = (int)w.ntc;
+    const bool vec = W % 4 == 0 && ((uintptr_t)d_out | (uintptr_t)w.S.p) % 16 == 0;
+    const dim3 grid((unsigned)cdiv(cdiv(n, vec ? 4 : 1), 256)), block(256);
+    DevBuf key, head;
     if (d_rec) {
         MH_TRY(key.alloc(8 * (size_t)(nlab + 1)));
         MH_TRY(head.alloc(4 * (size_t)(nlab + 1)));
         MH_HIP(hipMemsetAsync(key.p, 0, 8 * (size_t)(nlab + 1), s));
         MH_HIP(hipMemsetAsync(head.p, 0xff, 4 * (size_t)(nlab + 1), s));
-    }
-    hipLaunchKernelGGL(fdist_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, d_fd, d_lab, S.as<uint2>(), H, W, (int)ntc, NA.as<uint4>());
-    uint4 *cur = NA.as<uint4>(), *nxt = NB.as<uint4>();
-    MH_TRY(fdist_jumps_dev(cur, nxt, W, ntc, ntiles, d_open, s));
-    const bool vec = W % 4 == 0 && ((uintptr_t)d_out | (uintptr_t)S.p) % 16 == 0;
-    const int V = vec ? 4 : 1;
-    const dim3 grid((unsigned)cdiv(cdiv(n, V), 256)), block(256);
-    unsigned long long *d_key = d_rec ? key.as<unsigned long long>() : nullptr;
-    if (d_rec) {
+        unsigned long long *d_key = key.as<unsigned long long>();
         const TileGeom g = tile_geom(n, W);
-        if (vec) hipLaunchKernelGGL(fdist_final_rec_kernel<4>, dim3(tile_grid(g)), block, 0, s, S.as<uint2>(), cur, d_lab, g, (int)ntc, scale, nlab, d_out, d_key, d_unres, d_bad);
-        else hipLaunchKernelGGL(fdist_final_rec_kernel<1>, dim3(tile_grid(g)), block, 0, s, S.as<uint2>(), cur, d_lab, g, (int)ntc, scale, nlab, d_out, d_key, d_unres, d_bad);
-        if (vec) hipLaunchKernelGGL(fdist_head_kernel<4>, grid, block, 0, s, S.as<uint2>(), cur, d_lab, n, W, (int)ntc, nlab, d_key, head.as<uint32_t>());
-        else hipLaunchKernelGGL(fdist_head_kernel<1>, grid, block, 0, s, S.as<uint2>(), cur, d_lab, n, W, (int)ntc, nlab, d_key, head.as<uint32_t>());
+        hipLaunchKernelGGL(pick_v(vec, fdist_final_rec_kernel<4>, fdist_final_rec_kernel<1>), dim3(tile_grid(g)), block, 0, s, S, w.cur, d_lab, g, ntc, scale,
+                           nlab, d_out, d_key, w.count(), w.bad());
+        hipLaunchKernelGGL(pick_v(vec, fdist_head_kernel<4>, fdist_head_kernel<1>), grid, block, 0, s, S, w.cur, d_lab, n, W, ntc, nlab, d_key, head.as<uint32_t>());
         hipLaunchKernelGGL(fdist_records_kernel, dim3((unsigned)cdiv(nlab + 1, 256)), dim3(256), 0, s, d_key, head.as<uint32_t>(), nlab + 1, W, scale, d_rec);
     } else {
-        if (vec) hipLaunchKernelGGL(fdist_final_kernel<4>, grid, block, 0, s, S.as<uint2>(), cur, n, W, (int)ntc, scale, d_out, d_unres);
-        else hipLaunchKernelGGL(fdist_final_kernel<1>, grid, block, 0, s, S.as<uint2>(), cur, n, W, (int)ntc, scale, d_out, d_unres);
+        hipLaunchKernelGGL(pick_v(vec, fdist_final_kernel<4>, fdist_final_kernel<1>), grid, block, 0, s, S, w.cur, n, W, ntc, scale, d_out, w.count());
     }
-    MH_HIP(hipGetLastError());
-    unsigned long long hm[4] = {0, 0, 0, 0};
-    MH_HIP(hipMemcpyAsync(hm, misc.p, 32, hipMemcpyDeviceToHost, s));
-    MH_HIP(stream_sync(s));      // (the scratch, the nodes and the keys go back to the pool)
-    if ((unsigned int)hm[1]) {
+    bool bad = false;
+    int64_t u = 0;
+    MH_TRY(flow_walk_count(w, &u, &bad, s));      // (synchronises: the scratch, the nodes and the keys go back to the pool)
+    if (bad) {
         set_error("flow_distance: label outside [0, nlabels]");
         return MHIP_EINVAL;
     }
-    if (unresolved) *unresolved = (int64_t)hm[2];
+    if (unresolved) *unresolved = u;
     return MHIP_OK;
 }
 

@@ -55,6 +55,15 @@ class HydroPipeline(CtxHandle):
         """Stream raster ``name`` into a writer with ``open`` / ``write_window`` / ``close``; falls back to ``write(array)``."""
         write_windows(writer, self.shape, RASTER_DTYPE[RASTERS[name]], lambda row0, n: self.download_rows(name, row0, n), max_rows)
 
+    def _held_rows(self, entry, dtype, row0, nrows, lead=(), key=None, missing=None):
+        """Rows ``[row0, row0 + nrows)`` of a raster the context holds outside ``RASTERS``, through the C entry point ``entry`` (its
+        leading arguments ``lead``); with ``key``, ``ValueError(missing)`` from here when ``get_int(key)`` says that none is held."""
+        if key is not None and self.get_int(key) < 0:
+            raise ValueError(missing)
+        out = np.empty((int(nrows), self.shape[1]), dtype=dtype)
+        _lib.call(entry, self._ctx, *lead, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
+        return out
+
     # ---- stages ------------------------------------------------------------------------------------
     def run(self, *stages):
         mask = 0
@@ -170,9 +179,7 @@ class HydroPipeline(CtxHandle):
         return rec
 
     def download_wet_at_rows(self, row0, nrows):
-        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
-        _lib.call("mhip_ctx_wet_at_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
+        return self._held_rows("mhip_ctx_wet_at_rows", np.float32, row0, nrows)
 
     def download_wet_at(self):
         """The raster of the last ``wet_at`` (float32); ``ValueError`` once the depths or labels it was made from are gone."""
@@ -203,9 +210,7 @@ class HydroPipeline(CtxHandle):
         return rec
 
     def download_flow_distance_rows(self, row0, nrows):
-        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
-        _lib.call("mhip_ctx_flow_distance_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
+        return self._held_rows("mhip_ctx_flow_distance_rows", np.float32, row0, nrows)
 
     def download_flow_distance(self):
         """The raster of the last ``flow_distance`` (float32); ``ValueError`` once the flow directions or labels it was made from are
@@ -237,11 +242,8 @@ class HydroPipeline(CtxHandle):
         return undrained.value
 
     def _hand_rows(self, which, row0, nrows):
-        if self.get_int("hand_undrained") < 0:
-            raise ValueError("hand() has not been run on the resident rasters")
-        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
-        _lib.call("mhip_ctx_hand_rows", self._ctx, ctypes.c_int32(which), _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
+        return self._held_rows("mhip_ctx_hand_rows", np.float32, row0, nrows, lead=(ctypes.c_int32(which),), key="hand_undrained",
+                               missing="hand() has not been run on the resident rasters")
 
     def download_hand_rows(self, row0, nrows):
         return self._hand_rows(0, row0, nrows)
@@ -307,9 +309,7 @@ class HydroPipeline(CtxHandle):
         return rec
 
     def download_zones_rows(self, row0, nrows):
-        out = np.empty((int(nrows), self.shape[1]), dtype=np.int32)
-        _lib.call("mhip_ctx_zones_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
+        return self._held_rows("mhip_ctx_zones_rows", np.int32, row0, nrows)
 
     def download_zones(self):
         """The zone raster of the last ``rasterize_zones`` (int32); ``ValueError`` when there is none."""
@@ -359,11 +359,8 @@ class HydroPipeline(CtxHandle):
         return take_flowpaths(handle) + (assigned.value,)
 
     def download_reach_catchments_rows(self, row0, nrows):
-        if self.get_int("reach_catchments") < 0:
-            raise ValueError("reach_catchments() has not been run on the resident rasters")
-        out = np.empty((int(nrows), self.shape[1]), dtype=np.int32)
-        _lib.call("mhip_ctx_reach_catchments_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
+        return self._held_rows("mhip_ctx_reach_catchments_rows", np.int32, row0, nrows, key="reach_catchments",
+                               missing="reach_catchments() has not been run on the resident rasters")
 
     def download_reach_catchments(self):
         """The catchment raster of the last ``reach_catchments`` (int32); ``ValueError`` once a raster it was made from is gone."""
@@ -386,11 +383,8 @@ class HydroPipeline(CtxHandle):
         return rec
 
     def download_inundation_rows(self, row0, nrows):
-        if self.get_int("inundation") < 0:
-            raise ValueError("inundate() has not been run on the held hand and reach catchments")
-        out = np.empty((int(nrows), self.shape[1]), dtype=np.float32)
-        _lib.call("mhip_ctx_inundation_rows", self._ctx, _lib.i64(row0), _lib.i64(nrows), _lib.ptr(out))
-        return out
+        return self._held_rows("mhip_ctx_inundation_rows", np.float32, row0, nrows, key="inundation",
+                               missing="inundate() has not been run on the held hand and reach catchments")
 
     def download_inundation(self):
         """The depth raster of the last ``inundate`` (float32); ``ValueError`` once a result it was made from is gone."""

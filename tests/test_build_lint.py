@@ -134,13 +134,20 @@ def test_tile_kernels_keep_their_resident_workgroups(tmp_path):
     registers or kilobytes too many cost a quarter of it without a test failing (end of round 3: the labelling's tile union-find ran
     5 of 8 workgroups, the statistics 6, the watersheds' tile pass 4 after the pour-point candidates were added)."""
     want = {"ccl.hip": {"ccl_tile_kernelIf": 8}, "label_ops.hip": {"stats_kernelILb1ELi1E": 8, "stats_kernelILb1ELi2E": 8}, "watershed.hip": {"ws_tile_kernel": 8},
-            "accum.hip": {"accum_tile_kernelILb0ELb0ELb1E": 4, "accum_final_walk_kernel": 6}}
+            "accum.hip": {"accum_tile_kernelILb0ELb0ELb1E": 4, "accum_final_walk_kernel": 6},
+            # the walk of the flow distance (<false>) and of hand / the reach catchments (<true>): 28 KB of LDS, five workgroups
+            "flowdist.hip": {"walk_tile_kernelILb0E": 5, "walk_tile_kernelILb1E": 5}}
+    import lint_exec_spills
     for fn, kernels in want.items():
-        res = _residency(_isa(CSRC / fn, tmp_path / (fn + ".s")).read_text())
+        asm = _isa(CSRC / fn, tmp_path / (fn + ".s"))
+        res = _residency(asm.read_text())
         for frag, n in kernels.items():
             hit = [v for k, v in res.items() if frag in k]
             assert hit, (fn, frag, sorted(res)[:5])
             assert all(v[3] >= n for v in hit), (fn, frag, hit)
+        if fn == "flowdist.hip":      # neither instantiation of the merged tile pass may spill
+            walk = {k: v for k, v in lint_exec_spills.private_segments(str(asm)).items() if "walk_tile_kernel" in k}
+            assert len(walk) == 2 and all(v == 0 for v in walk.values()), walk
 
 
 def _dpp_hazards(asm_text, kernel_frag):

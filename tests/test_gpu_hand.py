@@ -393,3 +393,36 @@ def test_complete_chain_with_hand(tmp_path):
                 assert p.pop("hand_dist_min") == (float(zd["vmin_pos"][k + 1]) if zd["pos"][k + 1] else None)
                 assert p == b["properties"] and g["geometry"] == b["geometry"]
             assert layer[-1]["properties"]["hand_min"] is None and sum(g["properties"]["hand_min"] is not None for g in layer) >= 10
+
+
+_WALK_CASES = {}
+
+
+def _walk_case(shape):
+    """random codes 0..8, 3 % of the cells labelled; the terminal of every cell by the flow distance's model (computed once a shape)"""
+    if shape not in _WALK_CASES:
+        import _flowdist as FD
+        rng = np.random.default_rng(5 + sum(shape))
+        fd = rng.integers(0, 9, shape, dtype=np.uint8)
+        lab = np.where(rng.random(shape) < 0.03, rng.integers(1, 6, shape), 0).astype(np.int32)
+        _WALK_CASES[shape] = fd, lab, FD.resolve(fd, lab)[2].reshape(shape)
+    return _WALK_CASES[shape]
+
+
+@pytest.mark.parametrize("scale", [1.0, 2.5])
+@pytest.mark.parametrize("shape", [(65, 63), (130, 256)])
+def test_both_instantiations_of_the_tile_pass_walk_the_same_paths(alg, shape, scale):
+    """walk_tile_kernel<true> (hand) and <false> (flow distance) on one forest whose only drainage is its labels (accumulation 0,
+    threshold 1): a drained cell holds the flow distance's bits; an undrained cell has no flow distance either, or the flow distance
+    to an unlabelled terminal -- a dead end of the one is an END of the other"""
+    fd, lab, term = _walk_case(shape)
+    zero = np.zeros(shape, np.float32)
+    _, dist, undrained = alg.flow.hand(fd, np.zeros(shape, np.float64), zero, 1, labelled=lab, cellsize=scale, distance=True)
+    fdist = alg.flow.flow_distance(fd, labelled=lab, cellsize=scale)
+    drained, dead = dist >= 0, dist.view(np.uint32) == np.float32(-1.0).view(np.uint32)
+    assert (drained | dead).all() and undrained == int(dead.sum())
+    assert drained.mean() >= 0.05 and dead.mean() >= 0.05, (drained.mean(), dead.mean())
+    assert np.array_equal(dist.view(np.uint32)[drained], fdist.view(np.uint32)[drained])
+    unlabelled_end = (term >= 0) & (lab.ravel()[np.maximum(term, 0)] == 0)
+    no_end = fdist.view(np.uint32) == np.float32(-1.0).view(np.uint32)
+    assert (no_end | unlabelled_end)[dead].all(), int((~(no_end | unlabelled_end))[dead].sum())
