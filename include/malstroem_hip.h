@@ -513,7 +513,9 @@ int mhip_ctx_kernel_ms(mhip_ctx *ctx, const char *kernel, float *ms_total, int32
  * "flowdir_computed" (1 the resident flow directions are the library's own D8, 0 they were uploaded or there are none),
  * "noflat_pending" (1 MHIP_R_NOFLAT is resident but not written yet: a request that held NOFLAT and FLOWDIR on an undivided context
  * took its directions from the surface in registers and left the store to whoever reads the raster first -- a download, a stage,
- * a band call: that call writes it from MHIP_R_FILLED and MHIP_R_NGDIST, which stays resident for it, 4 bytes a cell) */
+ * a band call: that call writes it from MHIP_R_FILLED and MHIP_R_NGDIST, which stays resident for it, 4 bytes a cell),
+ * "noflat_rowstore" (what a later visit of the transform's rounds stored in the last request: 1 the six-row blocks of its tile in
+ * which a cell moved, 0 all 62 rows) and "noflat_rows_stored" (the rows of distances that came to, over all those visits) */
 int mhip_ctx_get_i64(mhip_ctx *ctx, const char *key, int64_t *value);
 int mhip_ctx_get_f64(mhip_ctx *ctx, const char *key, double *value);  /* "short", "diag" */
 /* label filter between MHIP_STAGE_LABEL and MHIP_STAGE_WATERSHED (reference bluespots.py:165-172):

@@ -188,6 +188,10 @@ struct FillStats {
     // 0 it did not, 1 not applicable (irregular levels / NaN cells / epsilons without weights), 2 its final check failed
     int32_t geo_reject = 0;
     int64_t geo_irregular = 0, geo_unreached = 0, geo_mismatch = 0;
+    // the geodesic transform's rounds: what a visit stored (0 every row of its tile, 1 the six-row blocks in which a cell moved) and
+    // the rows of distances that came to, over all visits behind the first
+    int32_t rowstore = 0;
+    int64_t rows_stored = 0;
 };
 
 // fill.hip

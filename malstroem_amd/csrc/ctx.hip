@@ -494,6 +494,8 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "noflat_reject_unreached") *value = c->noflat_st.geo_unreached;
     else if (k == "noflat_reject_mismatch") *value = c->noflat_st.geo_mismatch;
     else if (k == "noflat_cycles") *value = c->noflat_st.cycles;
+    else if (k == "noflat_rowstore") *value = c->noflat_st.rowstore;        // what the last request's rounds stored per visit (noflat_geo.hip: MHIP_NG_ROWSTORE)
+    else if (k == "noflat_rows_stored") *value = c->noflat_st.rows_stored;  // ... and the rows of distances that came to
     else if (k == "hyps_bins") *value = c->hyps_total;               // -1: no table (mhip_ctx_hyps)
     else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
     else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels

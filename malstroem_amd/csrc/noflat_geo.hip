@@ -65,6 +65,15 @@ constexpr int DPP_WF_SR1 = 0x138;          // lane i <- lane i-1
 #define NG_MAXCYC 1      // local (down, up, right, left) cycles per visit; a visit that is cut off re-queues its own tile
 #endif
 enum { C_IRREGULAR = 0, C_UNREACHED = 1, C_MISMATCH = 2, C_FATAL = 3, C_PROOF = 4, C_STATS = 8 };   // counters[]; C_PROOF: the flood's surface failed its proof (ng_handover_kernel); C_STATS: 64 x {visits, cycles}
+enum { C_ROWS = C_STATS + 128 + 16, C_END = C_ROWS + 64 };   // (C_STATS + 128 ..: NG_PROFILE's ticks) C_ROWS: 64 x rows of distances the rounds stored
+// Which rows of its tile a later visit stores (NG_ROWSTORE / MHIP_NG_ROWSTORE): 0 all 62 once anything moved, 1 the rows of the
+// six-row blocks in which a cell moved (block_rows), 2 exactly the rows in which one did (NG_TRK: two more instructions a row in the
+// first half of a cycle).  A row that no pass changed still holds what was loaded, nobody else stores a tile's interior, and a wall is
+// 0 in memory and cannot move: memory after the visit is the same either way.
+#ifndef NG_ROWSTORE
+#define NG_ROWSTORE 1
+#endif
+constexpr int NACC = 12;      // change accumulators of a first-half pass: row 1, rows 2..7, 8..13, .. 56..61, row 62
 static_assert(WN == ho::WN && TI == ho::TI, "handover_addr.hpp cuts the raster like this file");
 
 __device__ __forceinline__ uint32_t from_left(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, DPP_WF_SR1, 0xf, 0xf, true); }
@@ -213,7 +222,7 @@ __device__ __forceinline__ void pass(uint32_t (&d)[WN], uint32_t (&ni)[WN], cons
 
 template <typename WT>
 __device__ __forceinline__ void relax(uint32_t (&d)[WN], uint32_t (&ni)[WN], const WT wt, const uint32_t *tab_l, uint32_t scr_b, int lane, int maxcyc,
-                                      unsigned &wake, bool &changed, bool &capped, unsigned &cycles)
+                                      unsigned &wake, bool &changed, bool &capped, unsigned &cycles, uint64_t &rows)
 {
     // wake bits = neighbour k of the 3 x 3 block around the tile (k = 3 * (di + 1) + dj + 1)
     const uint64_t INNER = ((1ull << TI) - 1) << 1, B1 = 2ull, B62 = 1ull << TI;
@@ -229,6 +238,9 @@ __device__ __forceinline__ void relax(uint32_t (&d)[WN], uint32_t (&ni)[WN], con
             pass<false>(d, ni, wt, tab_l, acc_all, acc_first, acc_last);
             const uint64_t all = __ballot(acc_all != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
             chg |= all;
+            // the rows that moved: in the second half a lane is a row; the first half is not tracked here (64 adjacency words live:
+            // no registers for it) -- a window of three or more classes that moved there stores every row
+            rows |= half == 0 ? (all ? ~0ull : 0ull) : all;
             // half 0: lane = column, first / last = row 1 / 62.  half 1: lane = row, first / last = column 1 / 62.
             const unsigned e_first = (fst & INNER) ? 1u : 0u, e_last = (lst & INNER) ? 1u : 0u;
             const unsigned l1 = (all & B1) ? 1u : 0u, l62 = (all & B62) ? 1u : 0u;
@@ -258,6 +270,51 @@ __device__ __forceinline__ void relax(uint32_t (&d)[WN], uint32_t (&ni)[WN], con
 // mk[0..1] immovable / mk[2..3] wall bits by register row of the row layout, mk[4..7] the same of the transposed layout,
 // mk[8] = bit 0 / 1: row 1 / 62 of this lane is adjacent to something across the seam (row layout), bits 2 / 3: transposed layout.
 constexpr int NMK = 9;
+// TRK: the mask words of a first half's two passes -> this lane's rows.  The down pass shifted rows 1 .. 31 into rm_dn[0] and 32 .. 62
+// into rm_dn[1], first row first: row r sits at bit 31 - r / 62 - r.  The up pass took them last row first: bit r - 1 / r - 32.
+__device__ __forceinline__ void lane_rows_of(const uint32_t (&rm_dn)[2], const uint32_t (&rm_up)[2], uint32_t (&lane_rows)[2])
+{
+    lane_rows[0] |= __builtin_bitreverse32(rm_dn[0]) | (rm_up[0] << 1);
+    lane_rows[1] |= (__builtin_bitreverse32(rm_dn[1]) >> 1) | rm_up[1];
+}
+// ... and, once per visit, the OR of all lanes' rows as a wave-uniform mask
+__device__ __forceinline__ uint64_t wave_rows(const uint32_t (&lane_rows)[2], int lane)
+{
+    uint32_t lo = lane_rows[0], hi = lane_rows[1];
+    int at = lane << 2;
+    asm volatile("" : "+v"(at));      // (a new name per visit: or the six partner addresses are hoisted out of the tile loop and live through all of it)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        lo |= (uint32_t)__builtin_amdgcn_ds_bpermute(at ^ (o << 2), (int)lo);
+        hi |= (uint32_t)__builtin_amdgcn_ds_bpermute(at ^ (o << 2), (int)hi);
+    }
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)lo) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32);
+}
+// The change accumulators of a pass with lane = column.  BLK: one per block of rows (NACC of them; the rows as text take the
+// accumulator as an operand, so this costs no instruction inside a row), else one for the whole pass.  block_rows: the blocks in which
+// some lane moved a cell, as a mask of their rows -- the rows a visit has to store after the first half (the second half, lane = row,
+// gives its rows exactly: the ballot of its one accumulator)
+template <bool BLK> __device__ __forceinline__ constexpr int acc_of(int r) { return !BLK ? 0 : (r == 1 ? 0 : (r == TI ? NACC - 1 : 1 + (r - 2) / 6)); }
+template <bool BLK> __device__ __forceinline__ uint32_t acc_any(const uint32_t (&acc)[NACC])
+{
+    uint32_t v = acc[0];
+    if constexpr (BLK) {
+#pragma unroll
+        for (int k = 1; k < NACC; ++k) v |= acc[k];
+    }
+    return v;
+}
+template <bool BLK> __device__ __forceinline__ uint64_t block_rows(const uint32_t (&acc)[NACC], const uint64_t all)
+{
+    if constexpr (!BLK) return all ? ~0ull : 0ull;
+    uint64_t m = 0;
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        const uint64_t rows_k = k == 0 ? 2ull : (k == NACC - 1 ? 1ull << TI : 0x3full << (2 + 6 * (k - 1)));
+        m |= __ballot(acc[k] != 0u) ? rows_k : 0ull;
+    }
+    return m;
+}
 // One row of a pass as text: 8 instructions in 8 issue slots.  A DPP operand must not have been written by one of the two instructions in
 // front of the DPP instruction (the compiler pads with s_nop; left to itself it spent 13 slots on the row -- and turned the bit test into
 // and + compare + select with two more wait states): `b`, the row behind, is written by the v_bfi of the row before, the v_bitop3 and
@@ -272,78 +329,92 @@ constexpr int NMK = 9;
     "v_min_u32 %[" O "], %[t], %[" I "]\n\t"                                                                                                \
     "v_bfi_b32 %[" O "], %[k], %[" I "], %[" O "]\n\t"                                                                                      \
     "v_bitop3_b32 %[acc], %[" O "], %[acc], %[" I "] bitop3:0xde\n\t"
+// TRK (row store 2): every lane keeps a bit per row it moved a cell in -- the row's "new != old" shifted into a mask word, two more
+// instructions a row; a pass shifts its rows in in the order it takes them (lane_rows_of turns the words into row masks)
+#define NG_TRK(O, I)                                                                                                                         \
+    "v_cmp_ne_u32_e32 vcc, %[" O "], %[" I "]\n\t"                                                                                          \
+    "v_addc_co_u32_e32 %[rm], vcc, %[rm], %[rm], vcc\n\t"
+#define NG_ROW_T(O, I, B, BIT) NG_ROW(O, I, B, BIT) NG_TRK(O, I)
+#define NG_NONE
+#define NG_TRK_OUT , [rm] "+v"(rm)
+#define NG_TRK_CLOB : "vcc"
+// (six rows of one family as one statement: ROW the row's text, SGN the direction of the bit numbers, XO / XC what tracking adds)
+#define NG_SIX(ROW, SGN) ROW("o0", "i0", "b", "%[bit]") ROW("o1", "i1", "o0", "%[bit]" SGN "1") ROW("o2", "i2", "o1", "%[bit]" SGN "2")       \
+    ROW("o3", "i3", "o2", "%[bit]" SGN "3") ROW("o4", "i4", "o3", "%[bit]" SGN "4") ROW("o5", "i5", "o4", "%[bit]" SGN "5")
+#define NG_SIX_OUT [o0] "=&v"(o0), [o1] "=&v"(o1), [o2] "=&v"(o2), [o3] "=&v"(o3), [o4] "=&v"(o4), [o5] "=&v"(o5), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k)
+#define NG_SIX_IN [b] "v"(d[R - DIR]), [i0] "v"(d[R]), [i1] "v"(d[R + DIR]), [i2] "v"(d[R + 2 * DIR]), [i3] "v"(d[R + 3 * DIR]), [i4] "v"(d[R + 4 * DIR]), [i5] "v"(d[R + 5 * DIR])
+#define NG_WL_SIX(ROW, SGN, XO, XC)                                                                                                          \
+    asm volatile(NG_SIX(ROW, SGN) : NG_SIX_OUT, [acc] "+v"(acc) XO : NG_SIX_IN, [S] "v"(S), [G] "v"(G), [m] "v"(m), [bit] "n"(R & 31) XC)
+#define NG_WL_ONE(ROW, XO, XC)                                                                                                               \
+    asm volatile("s_nop 1\n\t" ROW("o0", "i0", "b", "%[bit]") "s_nop 1"                                                                     \
+                 : [o0] "=&v"(o0), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k), [acc] "+v"(acc) XO                                               \
+                 : [b] "v"(d[R - DIR]), [i0] "v"(cu), [S] "v"(S), [G] "v"(G), [m] "v"(m), [bit] "n"(R & 31) XC)
 // rows R, R + dir, .. R + 5 dir from the row behind R (six rows a block: the compiler puts an s_nop in front of every block)
-template <int R, int DIR>
-__device__ __forceinline__ void rows6_wl(uint32_t (&d)[WN], const uint32_t m, const uint32_t S, const uint32_t G, uint32_t &acc)
+template <int R, int DIR, bool TRK>
+__device__ __forceinline__ void rows6_wl(uint32_t (&d)[WN], const uint32_t m, const uint32_t S, const uint32_t G, uint32_t &acc, uint32_t &rm)
 {
     static_assert((R >> 5) == ((R + 5 * DIR) >> 5), "one mask word a block");
     uint32_t o0, o1, o2, o3, o4, o5, u, t, k;
-    if constexpr (DIR > 0)
-        asm volatile(NG_ROW("o0", "i0", "b", "%[bit]") NG_ROW("o1", "i1", "o0", "%[bit]+1") NG_ROW("o2", "i2", "o1", "%[bit]+2")
-                     NG_ROW("o3", "i3", "o2", "%[bit]+3") NG_ROW("o4", "i4", "o3", "%[bit]+4") NG_ROW("o5", "i5", "o4", "%[bit]+5")
-                     : [o0] "=&v"(o0), [o1] "=&v"(o1), [o2] "=&v"(o2), [o3] "=&v"(o3), [o4] "=&v"(o4), [o5] "=&v"(o5), [u] "=&v"(u), [t] "=&v"(t),
-                       [k] "=&v"(k), [acc] "+v"(acc)
-                     : [b] "v"(d[R - DIR]), [i0] "v"(d[R]), [i1] "v"(d[R + DIR]), [i2] "v"(d[R + 2 * DIR]), [i3] "v"(d[R + 3 * DIR]),
-                       [i4] "v"(d[R + 4 * DIR]), [i5] "v"(d[R + 5 * DIR]), [S] "v"(S), [G] "v"(G), [m] "v"(m), [bit] "n"(R & 31));
-    else
-        asm volatile(NG_ROW("o0", "i0", "b", "%[bit]") NG_ROW("o1", "i1", "o0", "%[bit]-1") NG_ROW("o2", "i2", "o1", "%[bit]-2")
-                     NG_ROW("o3", "i3", "o2", "%[bit]-3") NG_ROW("o4", "i4", "o3", "%[bit]-4") NG_ROW("o5", "i5", "o4", "%[bit]-5")
-                     : [o0] "=&v"(o0), [o1] "=&v"(o1), [o2] "=&v"(o2), [o3] "=&v"(o3), [o4] "=&v"(o4), [o5] "=&v"(o5), [u] "=&v"(u), [t] "=&v"(t),
-                       [k] "=&v"(k), [acc] "+v"(acc)
-                     : [b] "v"(d[R - DIR]), [i0] "v"(d[R]), [i1] "v"(d[R + DIR]), [i2] "v"(d[R + 2 * DIR]), [i3] "v"(d[R + 3 * DIR]),
-                       [i4] "v"(d[R + 4 * DIR]), [i5] "v"(d[R + 5 * DIR]), [S] "v"(S), [G] "v"(G), [m] "v"(m), [bit] "n"(R & 31));
+    if constexpr (DIR > 0 && !TRK) NG_WL_SIX(NG_ROW, "+", NG_NONE, NG_NONE);
+    else if constexpr (DIR > 0) NG_WL_SIX(NG_ROW_T, "+", NG_TRK_OUT, NG_TRK_CLOB);
+    else if constexpr (!TRK) NG_WL_SIX(NG_ROW, "-", NG_NONE, NG_NONE);
+    else NG_WL_SIX(NG_ROW_T, "-", NG_TRK_OUT, NG_TRK_CLOB);
     d[R] = o0; d[R + DIR] = o1; d[R + 2 * DIR] = o2; d[R + 3 * DIR] = o3; d[R + 4 * DIR] = o4; d[R + 5 * DIR] = o5;
 }
 // one row on its own (rows 1 and 62: their differences are looked at separately); returns old ^ new
-template <int R, int DIR>
-__device__ __forceinline__ uint32_t row1_wl(uint32_t (&d)[WN], const uint32_t m, const uint32_t S, const uint32_t G, uint32_t &acc)
+template <int R, int DIR, bool TRK>
+__device__ __forceinline__ uint32_t row1_wl(uint32_t (&d)[WN], const uint32_t m, const uint32_t S, const uint32_t G, uint32_t &acc, uint32_t &rm)
 {
     uint32_t o0, u, t, k;
     const uint32_t cu = d[R];
-    asm volatile("s_nop 1\n\t" NG_ROW("o0", "i0", "b", "%[bit]") "s_nop 1"
-                 : [o0] "=&v"(o0), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k), [acc] "+v"(acc)
-                 : [b] "v"(d[R - DIR]), [i0] "v"(cu), [S] "v"(S), [G] "v"(G), [m] "v"(m), [bit] "n"(R & 31));
+    if constexpr (!TRK) NG_WL_ONE(NG_ROW, NG_NONE, NG_NONE);
+    else NG_WL_ONE(NG_ROW_T, NG_TRK_OUT, NG_TRK_CLOB);
     d[R] = o0;
     return o0 ^ cu;
 }
-template <int R, int DIR, int N>
-__device__ __forceinline__ void blocks_wl(uint32_t (&d)[WN], const uint32_t lo, const uint32_t hi, const uint32_t S, const uint32_t G, uint32_t &acc)
+template <int R, int DIR, int N, bool BLK, bool TRK>
+__device__ __forceinline__ void blocks_wl(uint32_t (&d)[WN], const uint32_t lo, const uint32_t hi, const uint32_t S, const uint32_t G, uint32_t (&acc)[NACC],
+                                          uint32_t (&rm)[2])
 {
     if constexpr (N > 0) {
-        rows6_wl<R, DIR>(d, R < 32 ? lo : hi, S, G, acc);
+        rows6_wl<R, DIR, TRK>(d, R < 32 ? lo : hi, S, G, acc[acc_of<BLK>(R)], rm[R >> 5]);
         __builtin_amdgcn_sched_barrier(0);
-        blocks_wl<R + 6 * DIR, DIR, N - 1>(d, lo, hi, S, G, acc);
+        blocks_wl<R + 6 * DIR, DIR, N - 1, BLK, TRK>(d, lo, hi, S, G, acc, rm);
     }
 }
-template <bool DOWN>
+template <bool DOWN, bool BLK, bool TRK>
 __device__ __forceinline__ void pass_wl(uint32_t (&d)[WN], const uint32_t imm_lo, const uint32_t imm_hi, const uint32_t S, const uint32_t G,
-                                        const bool edge_first, const bool edge_last, uint32_t &acc_all, uint32_t &acc_first, uint32_t &acc_last)
+                                        const bool edge_first, const bool edge_last, uint32_t (&acc)[NACC], uint32_t (&rm)[2], uint32_t &acc_first,
+                                        uint32_t &acc_last)
 {
 #pragma unroll
     for (int r = 0; r < WN; ++r) asm volatile("" : "+v"(d[r]));
     uint32_t lo = imm_lo, hi = imm_hi;
     asm volatile("" : "+v"(lo), "+v"(hi));
     if constexpr (DOWN) {
-        const uint32_t x1 = row1_wl<1, 1>(d, lo, S, G, acc_all);
+        const uint32_t x1 = row1_wl<1, 1, TRK>(d, lo, S, G, acc[acc_of<BLK>(1)], rm[0]);
         acc_first |= edge_first ? x1 : 0u;
         __builtin_amdgcn_sched_barrier(0);
-        blocks_wl<2, 1, 10>(d, lo, hi, S, G, acc_all);              // rows 2 .. 61
-        const uint32_t x2 = row1_wl<TI, 1>(d, hi, S, G, acc_all);
+        blocks_wl<2, 1, 10, BLK, TRK>(d, lo, hi, S, G, acc, rm);              // rows 2 .. 61
+        const uint32_t x2 = row1_wl<TI, 1, TRK>(d, hi, S, G, acc[acc_of<BLK>(TI)], rm[1]);
         acc_last |= edge_last ? x2 : 0u;
     } else {
-        const uint32_t x2 = row1_wl<TI, -1>(d, hi, S, G, acc_all);
+        const uint32_t x2 = row1_wl<TI, -1, TRK>(d, hi, S, G, acc[acc_of<BLK>(TI)], rm[1]);
         acc_last |= edge_last ? x2 : 0u;
         __builtin_amdgcn_sched_barrier(0);
-        blocks_wl<TI - 1, -1, 10>(d, lo, hi, S, G, acc_all);         // rows 61 .. 2
-        const uint32_t x1 = row1_wl<1, -1>(d, lo, S, G, acc_all);
+        blocks_wl<TI - 1, -1, 10, BLK, TRK>(d, lo, hi, S, G, acc, rm);         // rows 61 .. 2
+        const uint32_t x1 = row1_wl<1, -1, TRK>(d, lo, S, G, acc[acc_of<BLK>(1)], rm[0]);
         acc_first |= edge_first ? x1 : 0u;
     }
     __builtin_amdgcn_sched_barrier(0);
 }
 
+template <int RS>
 __device__ __forceinline__ void relax_wl(uint32_t (&d)[WN], const uint32_t (&mk)[13], const uint32_t S, const uint32_t G, uint32_t scr_b, int lane, int maxcyc,
-                                         unsigned &wake, bool &changed, bool &capped, unsigned &cycles)
+                                         unsigned &wake, bool &changed, bool &capped, unsigned &cycles, uint64_t &rows)
 {
+    constexpr bool BLK = RS == 1, TRK = RS == 2;
+    uint32_t lane_rows[2] = {0u, 0u};      // TRK: bit r & 31 of word r >> 5 = this lane moved its cell of row r in a first half
     const uint64_t INNER = ((1ull << TI) - 1) << 1, B1 = 2ull, B62 = 1ull << TI;
     capped = true;
 #pragma nounroll
@@ -351,11 +422,13 @@ __device__ __forceinline__ void relax_wl(uint32_t (&d)[WN], const uint32_t (&mk)
         uint64_t chg = 0;
         ++cycles;
         {   // lane = column, first / last = row 1 / 62
-            uint32_t acc_all = 0, acc_first = 0, acc_last = 0;
-            pass_wl<true>(d, mk[0], mk[1], S, G, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc_all, acc_first, acc_last);
-            pass_wl<false>(d, mk[0], mk[1], S, G, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc_all, acc_first, acc_last);
-            const uint64_t all = __ballot(acc_all != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
+            uint32_t acc[NACC] = {}, acc_first = 0, acc_last = 0, rm_dn[2] = {0u, 0u}, rm_up[2] = {0u, 0u};
+            pass_wl<true, BLK, TRK>(d, mk[0], mk[1], S, G, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc, rm_dn, acc_first, acc_last);
+            pass_wl<false, BLK, TRK>(d, mk[0], mk[1], S, G, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc, rm_up, acc_first, acc_last);
+            const uint64_t all = __ballot(acc_any<BLK>(acc) != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
             chg |= all;
+            if constexpr (TRK) lane_rows_of(rm_dn, rm_up, lane_rows);
+            else rows |= block_rows<BLK>(acc, all);
             const unsigned e_first = (fst & INNER) ? 1u : 0u, e_last = (lst & INNER) ? 1u : 0u;
             const unsigned l1 = (all & B1) ? 1u : 0u, l62 = (all & B62) ? 1u : 0u;
             const unsigned f1 = (fst & B1) ? 1u : 0u, f62 = (fst & B62) ? 1u : 0u, g1 = (lst & B1) ? 1u : 0u, g62 = (lst & B62) ? 1u : 0u;
@@ -363,11 +436,12 @@ __device__ __forceinline__ void relax_wl(uint32_t (&d)[WN], const uint32_t (&mk)
             transpose32(d, scr_b, lane);
         }
         {   // lane = row, first / last = column 1 / 62
-            uint32_t acc_all = 0, acc_first = 0, acc_last = 0;
-            pass_wl<true>(d, mk[4], mk[5], S, G, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc_all, acc_first, acc_last);
-            pass_wl<false>(d, mk[4], mk[5], S, G, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc_all, acc_first, acc_last);
-            const uint64_t all = __ballot(acc_all != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
+            uint32_t acc[NACC] = {}, acc_first = 0, acc_last = 0, rm[2] = {0u, 0u};
+            pass_wl<true, false, false>(d, mk[4], mk[5], S, G, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc, rm, acc_first, acc_last);
+            pass_wl<false, false, false>(d, mk[4], mk[5], S, G, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc, rm, acc_first, acc_last);
+            const uint64_t all = __ballot(acc[0] != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
             chg |= all;
+            rows |= all;      // (lane = row)
             const unsigned e_first = (fst & INNER) ? 1u : 0u, e_last = (lst & INNER) ? 1u : 0u;
             const unsigned l1 = (all & B1) ? 1u : 0u, l62 = (all & B62) ? 1u : 0u;
             const unsigned f1 = (fst & B1) ? 1u : 0u, f62 = (fst & B62) ? 1u : 0u, g1 = (lst & B1) ? 1u : 0u, g62 = (lst & B62) ? 1u : 0u;
@@ -380,6 +454,7 @@ __device__ __forceinline__ void relax_wl(uint32_t (&d)[WN], const uint32_t (&mk)
             break;
         }
     }
+    if constexpr (TRK) rows |= wave_rows(lane_rows, lane);
 }
 
 // ---- a window of TWO classes (a seventh of the benchmark's tiles: it straddles one power of two): the same passes with one more bit per
@@ -401,80 +476,77 @@ constexpr int NMK2 = 13;
 struct TwoWeights {
     uint32_t S1, G1, S2, G2;
 };
-template <int R, int DIR>
-__device__ __forceinline__ void rows6_wl2(uint32_t (&d)[WN], const uint32_t m, const uint32_t c, const TwoWeights w, uint32_t &acc)
+#define NG_ROW2_T(O, I, B, BIT) NG_ROW2(O, I, B, BIT) NG_TRK(O, I)
+#define NG_WL2_W [S1] "v"(w.S1), [G1] "v"(w.G1), [S2] "v"(w.S2), [G2] "v"(w.G2), [m] "v"(m), [c] "v"(c), [bit] "n"(R & 31)
+#define NG_WL2_SIX(ROW, SGN, XO, XC)                                                                                                         \
+    asm volatile(NG_SIX(ROW, SGN) : NG_SIX_OUT, [s] "=&v"(sw), [g] "=&v"(gw), [acc] "+v"(acc) XO : NG_SIX_IN, NG_WL2_W XC)
+#define NG_WL2_ONE(ROW, XO, XC)                                                                                                              \
+    asm volatile("s_nop 1\n\t" ROW("o0", "i0", "b", "%[bit]") "s_nop 1"                                                                     \
+                 : [o0] "=&v"(o0), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k), [s] "=&v"(sw), [g] "=&v"(gw), [acc] "+v"(acc) XO                 \
+                 : [b] "v"(d[R - DIR]), [i0] "v"(cu), NG_WL2_W XC)
+template <int R, int DIR, bool TRK>
+__device__ __forceinline__ void rows6_wl2(uint32_t (&d)[WN], const uint32_t m, const uint32_t c, const TwoWeights w, uint32_t &acc, uint32_t &rm)
 {
     static_assert((R >> 5) == ((R + 5 * DIR) >> 5), "one mask word a block");
     uint32_t o0, o1, o2, o3, o4, o5, u, t, k, sw, gw;
-    if constexpr (DIR > 0)
-        asm volatile(NG_ROW2("o0", "i0", "b", "%[bit]") NG_ROW2("o1", "i1", "o0", "%[bit]+1") NG_ROW2("o2", "i2", "o1", "%[bit]+2")
-                     NG_ROW2("o3", "i3", "o2", "%[bit]+3") NG_ROW2("o4", "i4", "o3", "%[bit]+4") NG_ROW2("o5", "i5", "o4", "%[bit]+5")
-                     : [o0] "=&v"(o0), [o1] "=&v"(o1), [o2] "=&v"(o2), [o3] "=&v"(o3), [o4] "=&v"(o4), [o5] "=&v"(o5), [u] "=&v"(u), [t] "=&v"(t),
-                       [k] "=&v"(k), [s] "=&v"(sw), [g] "=&v"(gw), [acc] "+v"(acc)
-                     : [b] "v"(d[R - DIR]), [i0] "v"(d[R]), [i1] "v"(d[R + DIR]), [i2] "v"(d[R + 2 * DIR]), [i3] "v"(d[R + 3 * DIR]),
-                       [i4] "v"(d[R + 4 * DIR]), [i5] "v"(d[R + 5 * DIR]), [S1] "v"(w.S1), [G1] "v"(w.G1), [S2] "v"(w.S2), [G2] "v"(w.G2), [m] "v"(m),
-                       [c] "v"(c), [bit] "n"(R & 31));
-    else
-        asm volatile(NG_ROW2("o0", "i0", "b", "%[bit]") NG_ROW2("o1", "i1", "o0", "%[bit]-1") NG_ROW2("o2", "i2", "o1", "%[bit]-2")
-                     NG_ROW2("o3", "i3", "o2", "%[bit]-3") NG_ROW2("o4", "i4", "o3", "%[bit]-4") NG_ROW2("o5", "i5", "o4", "%[bit]-5")
-                     : [o0] "=&v"(o0), [o1] "=&v"(o1), [o2] "=&v"(o2), [o3] "=&v"(o3), [o4] "=&v"(o4), [o5] "=&v"(o5), [u] "=&v"(u), [t] "=&v"(t),
-                       [k] "=&v"(k), [s] "=&v"(sw), [g] "=&v"(gw), [acc] "+v"(acc)
-                     : [b] "v"(d[R - DIR]), [i0] "v"(d[R]), [i1] "v"(d[R + DIR]), [i2] "v"(d[R + 2 * DIR]), [i3] "v"(d[R + 3 * DIR]),
-                       [i4] "v"(d[R + 4 * DIR]), [i5] "v"(d[R + 5 * DIR]), [S1] "v"(w.S1), [G1] "v"(w.G1), [S2] "v"(w.S2), [G2] "v"(w.G2), [m] "v"(m),
-                       [c] "v"(c), [bit] "n"(R & 31));
+    if constexpr (DIR > 0 && !TRK) NG_WL2_SIX(NG_ROW2, "+", NG_NONE, NG_NONE);
+    else if constexpr (DIR > 0) NG_WL2_SIX(NG_ROW2_T, "+", NG_TRK_OUT, NG_TRK_CLOB);
+    else if constexpr (!TRK) NG_WL2_SIX(NG_ROW2, "-", NG_NONE, NG_NONE);
+    else NG_WL2_SIX(NG_ROW2_T, "-", NG_TRK_OUT, NG_TRK_CLOB);
     d[R] = o0; d[R + DIR] = o1; d[R + 2 * DIR] = o2; d[R + 3 * DIR] = o3; d[R + 4 * DIR] = o4; d[R + 5 * DIR] = o5;
 }
-template <int R, int DIR>
-__device__ __forceinline__ uint32_t row1_wl2(uint32_t (&d)[WN], const uint32_t m, const uint32_t c, const TwoWeights w, uint32_t &acc)
+template <int R, int DIR, bool TRK>
+__device__ __forceinline__ uint32_t row1_wl2(uint32_t (&d)[WN], const uint32_t m, const uint32_t c, const TwoWeights w, uint32_t &acc, uint32_t &rm)
 {
     uint32_t o0, u, t, k, sw, gw;
     const uint32_t cu = d[R];
-    asm volatile("s_nop 1\n\t" NG_ROW2("o0", "i0", "b", "%[bit]") "s_nop 1"
-                 : [o0] "=&v"(o0), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k), [s] "=&v"(sw), [g] "=&v"(gw), [acc] "+v"(acc)
-                 : [b] "v"(d[R - DIR]), [i0] "v"(cu), [S1] "v"(w.S1), [G1] "v"(w.G1), [S2] "v"(w.S2), [G2] "v"(w.G2), [m] "v"(m), [c] "v"(c),
-                   [bit] "n"(R & 31));
+    if constexpr (!TRK) NG_WL2_ONE(NG_ROW2, NG_NONE, NG_NONE);
+    else NG_WL2_ONE(NG_ROW2_T, NG_TRK_OUT, NG_TRK_CLOB);
     d[R] = o0;
     return o0 ^ cu;
 }
-template <int R, int DIR, int N>
+template <int R, int DIR, int N, bool BLK, bool TRK>
 __device__ __forceinline__ void blocks_wl2(uint32_t (&d)[WN], const uint32_t lo, const uint32_t hi, const uint32_t clo, const uint32_t chi, const TwoWeights w,
-                                           uint32_t &acc)
+                                           uint32_t (&acc)[NACC], uint32_t (&rm)[2])
 {
     if constexpr (N > 0) {
-        rows6_wl2<R, DIR>(d, R < 32 ? lo : hi, R < 32 ? clo : chi, w, acc);
+        rows6_wl2<R, DIR, TRK>(d, R < 32 ? lo : hi, R < 32 ? clo : chi, w, acc[acc_of<BLK>(R)], rm[R >> 5]);
         __builtin_amdgcn_sched_barrier(0);
-        blocks_wl2<R + 6 * DIR, DIR, N - 1>(d, lo, hi, clo, chi, w, acc);
+        blocks_wl2<R + 6 * DIR, DIR, N - 1, BLK, TRK>(d, lo, hi, clo, chi, w, acc, rm);
     }
 }
-template <bool DOWN>
+template <bool DOWN, bool BLK, bool TRK>
 __device__ __forceinline__ void pass_wl2(uint32_t (&d)[WN], const uint32_t imm_lo, const uint32_t imm_hi, const uint32_t cls_lo, const uint32_t cls_hi,
-                                         const TwoWeights w, const bool edge_first, const bool edge_last, uint32_t &acc_all, uint32_t &acc_first,
-                                         uint32_t &acc_last)
+                                         const TwoWeights w, const bool edge_first, const bool edge_last, uint32_t (&acc)[NACC], uint32_t (&rm)[2],
+                                         uint32_t &acc_first, uint32_t &acc_last)
 {
 #pragma unroll
     for (int r = 0; r < WN; ++r) asm volatile("" : "+v"(d[r]));
     uint32_t lo = imm_lo, hi = imm_hi, clo = cls_lo, chi = cls_hi;
     asm volatile("" : "+v"(lo), "+v"(hi), "+v"(clo), "+v"(chi));
     if constexpr (DOWN) {
-        const uint32_t x1 = row1_wl2<1, 1>(d, lo, clo, w, acc_all);
+        const uint32_t x1 = row1_wl2<1, 1, TRK>(d, lo, clo, w, acc[acc_of<BLK>(1)], rm[0]);
         acc_first |= edge_first ? x1 : 0u;
         __builtin_amdgcn_sched_barrier(0);
-        blocks_wl2<2, 1, 10>(d, lo, hi, clo, chi, w, acc_all);
-        const uint32_t x2 = row1_wl2<TI, 1>(d, hi, chi, w, acc_all);
+        blocks_wl2<2, 1, 10, BLK, TRK>(d, lo, hi, clo, chi, w, acc, rm);
+        const uint32_t x2 = row1_wl2<TI, 1, TRK>(d, hi, chi, w, acc[acc_of<BLK>(TI)], rm[1]);
         acc_last |= edge_last ? x2 : 0u;
     } else {
-        const uint32_t x2 = row1_wl2<TI, -1>(d, hi, chi, w, acc_all);
+        const uint32_t x2 = row1_wl2<TI, -1, TRK>(d, hi, chi, w, acc[acc_of<BLK>(TI)], rm[1]);
         acc_last |= edge_last ? x2 : 0u;
         __builtin_amdgcn_sched_barrier(0);
-        blocks_wl2<TI - 1, -1, 10>(d, lo, hi, clo, chi, w, acc_all);
-        const uint32_t x1 = row1_wl2<1, -1>(d, lo, clo, w, acc_all);
+        blocks_wl2<TI - 1, -1, 10, BLK, TRK>(d, lo, hi, clo, chi, w, acc, rm);
+        const uint32_t x1 = row1_wl2<1, -1, TRK>(d, lo, clo, w, acc[acc_of<BLK>(1)], rm[0]);
         acc_first |= edge_first ? x1 : 0u;
     }
     __builtin_amdgcn_sched_barrier(0);
 }
+template <int RS>
 __device__ __forceinline__ void relax_wl2(uint32_t (&d)[WN], const uint32_t (&mk)[NMK2], const TwoWeights w, uint32_t scr_b, int lane, int maxcyc, unsigned &wake,
-                                          bool &changed, bool &capped, unsigned &cycles)
+                                          bool &changed, bool &capped, unsigned &cycles, uint64_t &rows)
 {
+    constexpr bool BLK = RS == 1, TRK = RS == 2;
+    uint32_t lane_rows[2] = {0u, 0u};      // TRK: bit r & 31 of word r >> 5 = this lane moved its cell of row r in a first half
     const uint64_t INNER = ((1ull << TI) - 1) << 1, B1 = 2ull, B62 = 1ull << TI;
     capped = true;
 #pragma nounroll
@@ -482,11 +554,13 @@ __device__ __forceinline__ void relax_wl2(uint32_t (&d)[WN], const uint32_t (&mk
         uint64_t chg = 0;
         ++cycles;
         {   // lane = column, first / last = row 1 / 62
-            uint32_t acc_all = 0, acc_first = 0, acc_last = 0;
-            pass_wl2<true>(d, mk[0], mk[1], mk[9], mk[10], w, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc_all, acc_first, acc_last);
-            pass_wl2<false>(d, mk[0], mk[1], mk[9], mk[10], w, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc_all, acc_first, acc_last);
-            const uint64_t all = __ballot(acc_all != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
+            uint32_t acc[NACC] = {}, acc_first = 0, acc_last = 0, rm_dn[2] = {0u, 0u}, rm_up[2] = {0u, 0u};
+            pass_wl2<true, BLK, TRK>(d, mk[0], mk[1], mk[9], mk[10], w, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc, rm_dn, acc_first, acc_last);
+            pass_wl2<false, BLK, TRK>(d, mk[0], mk[1], mk[9], mk[10], w, (mk[8] & 1u) != 0u, (mk[8] & 2u) != 0u, acc, rm_up, acc_first, acc_last);
+            const uint64_t all = __ballot(acc_any<BLK>(acc) != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
             chg |= all;
+            if constexpr (TRK) lane_rows_of(rm_dn, rm_up, lane_rows);
+            else rows |= block_rows<BLK>(acc, all);
             const unsigned e_first = (fst & INNER) ? 1u : 0u, e_last = (lst & INNER) ? 1u : 0u;
             const unsigned l1 = (all & B1) ? 1u : 0u, l62 = (all & B62) ? 1u : 0u;
             const unsigned f1 = (fst & B1) ? 1u : 0u, f62 = (fst & B62) ? 1u : 0u, g1 = (lst & B1) ? 1u : 0u, g62 = (lst & B62) ? 1u : 0u;
@@ -494,11 +568,12 @@ __device__ __forceinline__ void relax_wl2(uint32_t (&d)[WN], const uint32_t (&mk
             transpose32(d, scr_b, lane);
         }
         {   // lane = row, first / last = column 1 / 62
-            uint32_t acc_all = 0, acc_first = 0, acc_last = 0;
-            pass_wl2<true>(d, mk[4], mk[5], mk[11], mk[12], w, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc_all, acc_first, acc_last);
-            pass_wl2<false>(d, mk[4], mk[5], mk[11], mk[12], w, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc_all, acc_first, acc_last);
-            const uint64_t all = __ballot(acc_all != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
+            uint32_t acc[NACC] = {}, acc_first = 0, acc_last = 0, rm[2] = {0u, 0u};
+            pass_wl2<true, false, false>(d, mk[4], mk[5], mk[11], mk[12], w, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc, rm, acc_first, acc_last);
+            pass_wl2<false, false, false>(d, mk[4], mk[5], mk[11], mk[12], w, (mk[8] & 4u) != 0u, (mk[8] & 8u) != 0u, acc, rm, acc_first, acc_last);
+            const uint64_t all = __ballot(acc[0] != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
             chg |= all;
+            rows |= all;      // (lane = row)
             const unsigned e_first = (fst & INNER) ? 1u : 0u, e_last = (lst & INNER) ? 1u : 0u;
             const unsigned l1 = (all & B1) ? 1u : 0u, l62 = (all & B62) ? 1u : 0u;
             const unsigned f1 = (fst & B1) ? 1u : 0u, f62 = (fst & B62) ? 1u : 0u, g1 = (lst & B1) ? 1u : 0u, g62 = (lst & B62) ? 1u : 0u;
@@ -511,6 +586,7 @@ __device__ __forceinline__ void relax_wl2(uint32_t (&d)[WN], const uint32_t (&mk
             break;
         }
     }
+    if constexpr (TRK) rows |= wave_rows(lane_rows, lane);
 }
 
 // ---- a tile that is ONE flat (every cell of the 62 x 62 interior is adjacent to all of its 8 neighbours, one class): no masks --
@@ -524,63 +600,70 @@ __device__ __forceinline__ void relax_wl2(uint32_t (&d)[WN], const uint32_t (&mk
     "v_min_u32 %[" O "], %[t], %[" I "]\n\t"                                                                                                \
     "v_cndmask_b32_e64 %[" O "], %[" O "], %[" I "], %[ring]\n\t"                                                                            \
     "v_bitop3_b32 %[acc], %[" O "], %[acc], %[" I "] bitop3:0xde\n\t"
-template <int R, int DIR>
-__device__ __forceinline__ void rows6_open(uint32_t (&d)[WN], const uint64_t ring, const uint32_t S, const uint32_t G, uint32_t &acc)
+#define NG_ROW_OPEN4(O, I, B, BIT) NG_ROW_OPEN(O, I, B)
+#define NG_ROW_OPEN_T(O, I, B, BIT) NG_ROW_OPEN(O, I, B) NG_TRK(O, I)
+#define NG_OPEN_SIX(ROW, XO, XC)                                                                                                             \
+    asm volatile(NG_SIX(ROW, "+") : NG_SIX_OUT, [acc] "+v"(acc) XO : NG_SIX_IN, [S] "v"(S), [G] "v"(G), [ring] "s"(ring) XC)
+#define NG_OPEN_ONE(ROW, XO, XC)                                                                                                             \
+    asm volatile("s_nop 1\n\t" ROW("o0", "i0", "b", "") "s_nop 1"                                                                           \
+                 : [o0] "=&v"(o0), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k), [acc] "+v"(acc) XO                                               \
+                 : [b] "v"(d[R - DIR]), [i0] "v"(cu), [S] "v"(S), [G] "v"(G), [ring] "s"(ring) XC)
+template <int R, int DIR, bool TRK>
+__device__ __forceinline__ void rows6_open(uint32_t (&d)[WN], const uint64_t ring, const uint32_t S, const uint32_t G, uint32_t &acc, uint32_t &rm)
 {
+    static_assert((R >> 5) == ((R + 5 * DIR) >> 5), "one mask word a block");
     uint32_t o0, o1, o2, o3, o4, o5, u, t, k;
-    asm volatile(NG_ROW_OPEN("o0", "i0", "b") NG_ROW_OPEN("o1", "i1", "o0") NG_ROW_OPEN("o2", "i2", "o1") NG_ROW_OPEN("o3", "i3", "o2")
-                 NG_ROW_OPEN("o4", "i4", "o3") NG_ROW_OPEN("o5", "i5", "o4")
-                 : [o0] "=&v"(o0), [o1] "=&v"(o1), [o2] "=&v"(o2), [o3] "=&v"(o3), [o4] "=&v"(o4), [o5] "=&v"(o5), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k),
-                   [acc] "+v"(acc)
-                 : [b] "v"(d[R - DIR]), [i0] "v"(d[R]), [i1] "v"(d[R + DIR]), [i2] "v"(d[R + 2 * DIR]), [i3] "v"(d[R + 3 * DIR]), [i4] "v"(d[R + 4 * DIR]),
-                   [i5] "v"(d[R + 5 * DIR]), [S] "v"(S), [G] "v"(G), [ring] "s"(ring));
+    if constexpr (!TRK) NG_OPEN_SIX(NG_ROW_OPEN4, NG_NONE, NG_NONE);
+    else NG_OPEN_SIX(NG_ROW_OPEN_T, NG_TRK_OUT, NG_TRK_CLOB);
     d[R] = o0; d[R + DIR] = o1; d[R + 2 * DIR] = o2; d[R + 3 * DIR] = o3; d[R + 4 * DIR] = o4; d[R + 5 * DIR] = o5;
 }
-template <int R, int DIR>
-__device__ __forceinline__ uint32_t row1_open(uint32_t (&d)[WN], const uint64_t ring, const uint32_t S, const uint32_t G, uint32_t &acc)
+template <int R, int DIR, bool TRK>
+__device__ __forceinline__ uint32_t row1_open(uint32_t (&d)[WN], const uint64_t ring, const uint32_t S, const uint32_t G, uint32_t &acc, uint32_t &rm)
 {
     uint32_t o0, u, t, k;
     const uint32_t cu = d[R];
-    asm volatile("s_nop 1\n\t" NG_ROW_OPEN("o0", "i0", "b") "s_nop 1"
-                 : [o0] "=&v"(o0), [u] "=&v"(u), [t] "=&v"(t), [k] "=&v"(k), [acc] "+v"(acc)
-                 : [b] "v"(d[R - DIR]), [i0] "v"(cu), [S] "v"(S), [G] "v"(G), [ring] "s"(ring));
+    if constexpr (!TRK) NG_OPEN_ONE(NG_ROW_OPEN4, NG_NONE, NG_NONE);
+    else NG_OPEN_ONE(NG_ROW_OPEN_T, NG_TRK_OUT, NG_TRK_CLOB);
     d[R] = o0;
     return o0 ^ cu;
 }
-template <int R, int DIR, int N>
-__device__ __forceinline__ void blocks_open(uint32_t (&d)[WN], const uint64_t ring, const uint32_t S, const uint32_t G, uint32_t &acc)
+template <int R, int DIR, int N, bool BLK, bool TRK>
+__device__ __forceinline__ void blocks_open(uint32_t (&d)[WN], const uint64_t ring, const uint32_t S, const uint32_t G, uint32_t (&acc)[NACC], uint32_t (&rm)[2])
 {
     if constexpr (N > 0) {
-        rows6_open<R, DIR>(d, ring, S, G, acc);
+        rows6_open<R, DIR, TRK>(d, ring, S, G, acc[acc_of<BLK>(R)], rm[R >> 5]);
         __builtin_amdgcn_sched_barrier(0);
-        blocks_open<R + 6 * DIR, DIR, N - 1>(d, ring, S, G, acc);
+        blocks_open<R + 6 * DIR, DIR, N - 1, BLK, TRK>(d, ring, S, G, acc, rm);
     }
 }
 // (the rows as text, like pass_wl: 7 instructions in 7 issue slots; the compiler's version had two s_nop in front of the DPP reads)
-template <bool DOWN>
-__device__ __forceinline__ void pass_open(uint32_t (&d)[WN], const uint32_t S, const uint32_t G, const bool ring_lane, uint32_t &acc_all, uint32_t &acc_first,
-                                          uint32_t &acc_last)
+template <bool DOWN, bool BLK, bool TRK>
+__device__ __forceinline__ void pass_open(uint32_t (&d)[WN], const uint32_t S, const uint32_t G, const bool ring_lane, uint32_t (&acc)[NACC], uint32_t (&rm)[2],
+                                          uint32_t &acc_first, uint32_t &acc_last)
 {
 #pragma unroll
     for (int r = 0; r < WN; ++r) asm volatile("" : "+v"(d[r]));
     const uint64_t ring = __ballot(ring_lane);
     if constexpr (DOWN) {
-        acc_first |= row1_open<1, 1>(d, ring, S, G, acc_all);
+        acc_first |= row1_open<1, 1, TRK>(d, ring, S, G, acc[acc_of<BLK>(1)], rm[0]);
         __builtin_amdgcn_sched_barrier(0);
-        blocks_open<2, 1, 10>(d, ring, S, G, acc_all);
-        acc_last |= row1_open<TI, 1>(d, ring, S, G, acc_all);
+        blocks_open<2, 1, 10, BLK, TRK>(d, ring, S, G, acc, rm);
+        acc_last |= row1_open<TI, 1, TRK>(d, ring, S, G, acc[acc_of<BLK>(TI)], rm[1]);
     } else {
-        acc_last |= row1_open<TI, -1>(d, ring, S, G, acc_all);
+        acc_last |= row1_open<TI, -1, TRK>(d, ring, S, G, acc[acc_of<BLK>(TI)], rm[1]);
         __builtin_amdgcn_sched_barrier(0);
-        blocks_open<TI - 1, -1, 10>(d, ring, S, G, acc_all);
-        acc_first |= row1_open<1, -1>(d, ring, S, G, acc_all);
+        blocks_open<TI - 1, -1, 10, BLK, TRK>(d, ring, S, G, acc, rm);
+        acc_first |= row1_open<1, -1, TRK>(d, ring, S, G, acc[acc_of<BLK>(1)], rm[0]);
     }
     __builtin_amdgcn_sched_barrier(0);
 }
 
+template <int RS>
 __device__ __forceinline__ void relax_open(uint32_t (&d)[WN], const uint32_t S, const uint32_t G, uint32_t scr_b, int lane, int maxcyc, unsigned &wake,
-                                           bool &changed, bool &capped, unsigned &cycles)
+                                           bool &changed, bool &capped, unsigned &cycles, uint64_t &rows)
 {
+    constexpr bool BLK = RS == 1, TRK = RS == 2;
+    uint32_t lane_rows[2] = {0u, 0u};      // TRK: bit r & 31 of word r >> 5 = this lane moved its cell of row r in a first half
     const uint64_t INNER = ((1ull << TI) - 1) << 1, B1 = 2ull, B62 = 1ull << TI;
     const bool ring_lane = (lane == 0) | (lane == WN - 1);
     capped = true;
@@ -590,11 +673,20 @@ __device__ __forceinline__ void relax_open(uint32_t (&d)[WN], const uint32_t S, 
         ++cycles;
 #pragma nounroll
         for (int half = 0; half < 2; ++half) {
-            uint32_t acc_all = 0, acc_first = 0, acc_last = 0;
-            pass_open<true>(d, S, G, ring_lane, acc_all, acc_first, acc_last);
-            pass_open<false>(d, S, G, ring_lane, acc_all, acc_first, acc_last);
-            const uint64_t all = __ballot(acc_all != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
+            // (one body for both halves: the second half's rows are the lanes of `all`, its blocks are not looked at)
+            uint32_t acc[NACC] = {}, acc_first = 0, acc_last = 0, rm_dn[2] = {0u, 0u}, rm_up[2] = {0u, 0u};
+            if (TRK && half == 0) {      // (the per-lane bits are the first half's alone: the second half runs the passes without them)
+                pass_open<true, false, TRK>(d, S, G, ring_lane, acc, rm_dn, acc_first, acc_last);
+                pass_open<false, false, TRK>(d, S, G, ring_lane, acc, rm_up, acc_first, acc_last);
+                lane_rows_of(rm_dn, rm_up, lane_rows);
+            } else {
+                pass_open<true, BLK, false>(d, S, G, ring_lane, acc, rm_dn, acc_first, acc_last);
+                pass_open<false, BLK, false>(d, S, G, ring_lane, acc, rm_up, acc_first, acc_last);
+            }
+            const uint64_t all = __ballot(acc_any<BLK>(acc) != 0), fst = __ballot(acc_first != 0), lst = __ballot(acc_last != 0);
             chg |= all;
+            if (half == 1) rows |= all;
+            else if (!TRK) rows |= block_rows<BLK>(acc, all);
             const unsigned e_first = (fst & INNER) ? 1u : 0u, e_last = (lst & INNER) ? 1u : 0u;
             const unsigned l1 = (all & B1) ? 1u : 0u, l62 = (all & B62) ? 1u : 0u;
             const unsigned f1 = (fst & B1) ? 1u : 0u, f62 = (fst & B62) ? 1u : 0u, g1 = (lst & B1) ? 1u : 0u, g62 = (lst & B62) ? 1u : 0u;
@@ -608,6 +700,7 @@ __device__ __forceinline__ void relax_open(uint32_t (&d)[WN], const uint32_t S, 
             break;
         }
     }
+    if constexpr (TRK) rows |= wave_rows(lane_rows, lane);
 }
 
 // One tile visit.  FIRST (ng_first_kernel, every tile once): the window's words are built from the classification -- ring
@@ -615,9 +708,11 @@ __device__ __forceinline__ void relax_open(uint32_t (&d)[WN], const uint32_t S, 
 // with a header word (seams, class, "holds a flat cell at all"); distances start from the classification alone.  Later visits
 // (ng_round_kernel) load header, block and distances and go straight to the passes.
 constexpr uint32_t HDR_ACTIVE = 1u << 31, HDR_UNIFORM = 1u << 9, HDR_OPEN = 1u << 10, HDR_TWO = 1u << 11;   // (HDR_TWO: bits 24..30 = second class - first + 64)
-template <bool FIRST, bool HANDOVER = false>
-__device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *tab_l, uint32_t scr_b, int lane, unsigned &visits, unsigned &cycles)
+template <bool FIRST, bool HANDOVER = false, int RS = 0>
+__device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *tab_l, uint32_t scr_b, int lane, unsigned &visits, unsigned &cycles,
+                                      unsigned &rows_stored)
 {
+
 #ifdef NG_PROFILE
     const long long tp0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1067,12 +1162,15 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
     const uint32_t eref = (hdr >> 16) & 0xffu;
     unsigned wake = 0;
     bool changed = false, capped = false;
-    if (hdr & HDR_OPEN) relax_open(d, tab_l[eref], tab_l[256 + eref], scr_b, lane, a.maxcyc, wake, changed, capped, cycles);
+    uint64_t rows = 0;      // RS: bit r = some pass of this visit moved a cell of window row r (wave-uniform)
+    bool walls = false;     // RS: the window's walls read "not reached" in d[]: 0 again in the rows that are stored
+    if (hdr & HDR_OPEN) relax_open<RS>(d, tab_l[eref], tab_l[256 + eref], scr_b, lane, a.maxcyc, wake, changed, capped, cycles, rows);
     else if (hdr & HDR_UNIFORM) {
 #pragma unroll
         for (int r = 0; r < WN; ++r) d[r] |= (uint32_t)__builtin_amdgcn_sbfe((int)mk[2 + (r >> 5)], r & 31, 1) & DINF;      // the walls (0 in memory)
-        relax_wl(d, mk, tab_l[eref], tab_l[256 + eref], scr_b, lane, a.maxcyc, wake, changed, capped, cycles);
-        if (changed) {
+        relax_wl<RS>(d, mk, tab_l[eref], tab_l[256 + eref], scr_b, lane, a.maxcyc, wake, changed, capped, cycles, rows);
+        walls = true;
+        if (RS == 0 && changed) {
 #pragma unroll
             for (int r = 1; r <= TI; ++r) d[r] &= ~(uint32_t)__builtin_amdgcn_sbfe((int)mk[2 + (r >> 5)], r & 31, 1);
         }
@@ -1081,12 +1179,13 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
         const uint32_t c2 = (eref + ((hdr >> 24) & 0x7fu) - 64u) & 0xffu;
 #pragma unroll
         for (int r = 0; r < WN; ++r) d[r] |= (uint32_t)__builtin_amdgcn_sbfe((int)mk[2 + (r >> 5)], r & 31, 1) & DINF;
-        relax_wl2(d, mk, TwoWeights{tab_l[eref], tab_l[256 + eref], tab_l[c2], tab_l[256 + c2]}, scr_b, lane, a.maxcyc, wake, changed, capped, cycles);
-        if (changed) {
+        relax_wl2<RS>(d, mk, TwoWeights{tab_l[eref], tab_l[256 + eref], tab_l[c2], tab_l[256 + c2]}, scr_b, lane, a.maxcyc, wake, changed, capped, cycles, rows);
+        walls = true;
+        if (RS == 0 && changed) {
 #pragma unroll
             for (int r = 1; r <= TI; ++r) d[r] &= ~(uint32_t)__builtin_amdgcn_sbfe((int)mk[2 + (r >> 5)], r & 31, 1);
         }
-    } else relax(d, ni, LaneW{}, tab_l, scr_b, lane, a.maxcyc, wake, changed, capped, cycles);
+    } else relax(d, ni, LaneW{}, tab_l, scr_b, lane, a.maxcyc, wake, changed, capped, cycles, rows);
     wake &= hdr & 0x1ffu;
 #ifdef NG_PROFILE
     const long long tp3 = __builtin_amdgcn_s_memtime();
@@ -1094,14 +1193,38 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
 
     if (changed) {
         const bool lane_ok = (lane >= 1) & (lane <= TI) & (cc < W - 1);
-        if (lane_ok) {
-            if (last_row == WN - 1) {
+        const uint64_t mine = ((1ull << last_row) - 1ull) & ~1ull;      // rows 1 .. 62 in front of the raster's last row (row H - 1 is a border row)
+        if constexpr (RS == 0) {
+            rows_stored += (unsigned)__builtin_popcountll(mine);
+            if (lane_ok) {
+                if (last_row == WN - 1) {
 #pragma unroll
-                for (int r = 1; r <= TI; ++r) __builtin_amdgcn_raw_buffer_store_b32(d[r], rd, lane * 4, r * Wi * 4, 0);
-            } else {
+                    for (int r = 1; r <= TI; ++r) __builtin_amdgcn_raw_buffer_store_b32(d[r], rd, lane * 4, r * Wi * 4, 0);
+                } else {
 #pragma unroll
-                for (int r = 1; r <= TI; ++r)
-                    if (r < last_row) __builtin_amdgcn_raw_buffer_store_b32(d[r], rd, lane * 4, r * Wi * 4, 0);   // row H - 1 is a border row
+                    for (int r = 1; r <= TI; ++r)
+                        if (r < last_row) __builtin_amdgcn_raw_buffer_store_b32(d[r], rd, lane * 4, r * Wi * 4, 0);
+                }
+            }
+        } else {
+            // only the rows that moved: one scalar branch a row on the wave's row mask (never a per-lane predicate: EXEC stays what
+            // lane_ok made it), the walls put back in the same rows
+            rows &= mine;
+            rows_stored += (unsigned)__builtin_popcountll(rows);
+            const uint32_t rows_lo = (uint32_t)rows, rows_hi = (uint32_t)(rows >> 32);      // (32-bit tests: there is no scalar 64-bit one)
+            auto store_rows = [&](auto wall_tag) {
+#pragma unroll
+                for (int r = 1; r <= TI; ++r) {
+                    if (((r < 32 ? rows_lo : rows_hi) >> (r & 31)) & 1u) {
+                        uint32_t v = d[r];
+                        if constexpr (decltype(wall_tag)::value) v &= ~(uint32_t)__builtin_amdgcn_sbfe((int)mk[2 + (r >> 5)], r & 31, 1);
+                        __builtin_amdgcn_raw_buffer_store_b32(v, rd, lane * 4, r * Wi * 4, 0);
+                    }
+                }
+            };
+            if (lane_ok) {
+                if (walls) store_rows(std::true_type{});
+                else store_rows(std::false_type{});
             }
         }
     }
@@ -1145,7 +1268,7 @@ __device__ __forceinline__ void visit(const GeoArgs &a, int t, const uint32_t *t
 // waves only fits a CU from which half of the labelling's workgroups have gone -- and the dispatcher refills every gap with the
 // labelling's small ones first, because THEY fit (no-flats stage 6.8 -> 9.5 ms in round 3 and again in round 4) --, a single wave with
 // 18.7 KB fits as soon as one of them leaves.
-template <bool FIRST, int WPB = 4, bool HANDOVER = false>
+template <bool FIRST, int WPB = 4, bool HANDOVER = false, int RS = 0>
 __device__ __forceinline__ void round_body(const GeoArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -1164,20 +1287,31 @@ __device__ __forceinline__ void round_body(const GeoArgs &a)
 #pragma unroll
     for (int k = 0; k < 512 / (64 * WPB); ++k) tab_l[threadIdx.x + k * 64 * WPB] = tw[k];
     __syncthreads();
-    unsigned visits = 0, cycles = 0;
+    unsigned visits = 0, cycles = 0, rows_stored = 0;
     for (int i = gw; i < n; i += nwaves) {
         const int t = FIRST ? i : __builtin_amdgcn_readfirstlane(i == gw ? t_first : a.list[i]);
-        visit<FIRST, HANDOVER>(a, t, tab_l, scr_b, lane, visits, cycles);
+        visit<FIRST, HANDOVER, RS>(a, t, tab_l, scr_b, lane, visits, cycles, rows_stored);
     }
     if (lane == 0 && visits) {
         unsigned long long *st = a.counters + C_STATS + 2 * (gw & 63);
         atomicAdd(&st[0], (unsigned long long)visits);
         atomicAdd(&st[1], (unsigned long long)cycles);
+        if (!FIRST && rows_stored) atomicAdd(&a.counters[C_ROWS + (gw & 63)], (unsigned long long)rows_stored);
     }
 }
 __global__ __launch_bounds__(256, 2) void ng_first_kernel(GeoArgs a) { round_body<true>(a); }
-__global__ __launch_bounds__(256, 2) void ng_round_kernel(GeoArgs a) { round_body<false>(a); }
-__global__ __launch_bounds__(64, 2) void ng_round_w1_kernel(GeoArgs a) { round_body<false, 1>(a); }
+// the rounds, by what a visit stores (NG_ROWSTORE: the build's default, under the names the profiles know; MHIP_NG_ROWSTORE: the other one)
+__global__ __launch_bounds__(256, 2) void ng_round_kernel(GeoArgs a) { round_body<false, 4, false, NG_ROWSTORE>(a); }
+__global__ __launch_bounds__(64, 2) void ng_round_w1_kernel(GeoArgs a) { round_body<false, 1, false, NG_ROWSTORE>(a); }
+template <int RS> __global__ __launch_bounds__(256, 2) void ng_round_alt_kernel(GeoArgs a) { round_body<false, 4, false, RS>(a); }
+template <int RS> __global__ __launch_bounds__(64, 2) void ng_round_alt_w1_kernel(GeoArgs a) { round_body<false, 1, false, RS>(a); }
+typedef void (*RoundKernel)(GeoArgs);
+template <int RS> RoundKernel round_kernel(bool w1)
+{
+    if constexpr (RS == NG_ROWSTORE) return w1 ? ng_round_w1_kernel : ng_round_kernel;
+    else return w1 ? ng_round_alt_w1_kernel<RS> : ng_round_alt_kernel<RS>;
+}
+RoundKernel round_kernel(int rs, bool w1) { return rs == 0 ? round_kernel<0>(w1) : (rs == 1 ? round_kernel<1>(w1) : round_kernel<2>(w1)); }
 // the first visit of a request that holds the plain fill as well: the flood's last pass and its proof ride on the classification
 __global__ __launch_bounds__(256, 2) void ng_handover_kernel(GeoArgs a) { round_body<true, 4, true>(a); }
 
@@ -1562,6 +1696,7 @@ struct GeoRun::Impl {
     int64_t nt = 0;
     size_t lds = 0;
     int maxcyc = NG_MAXCYC;
+    int rowstore = NG_ROWSTORE;  // what a later visit stores (MHIP_NG_ROWSTORE, read per request): 0 every row of its tile, 1 the blocks, 2 the rows that moved
     bool debug = false;
     unsigned long long irregular = 0;
 };
@@ -1637,9 +1772,10 @@ int GeoRun::launch_rounds(hipStream_t s, int nb)
             a.count_next = m.d_any + m.round + 1;
         }
         if (m.light && tail_hook && tail_hook->at == StageHook::TAIL_ROUNDS)      // (the label branch runs beside these rounds: one wavefront per workgroup, see round_body)
-            hipLaunchKernelGGL(ng_round_w1_kernel, dim3((unsigned)std::min<int64_t>(m.nt, 2048)), dim3(64), (WN * (WN + 1) + 512) * sizeof(uint32_t), s, a);
+            hipLaunchKernelGGL(round_kernel(m.rowstore, true), dim3((unsigned)std::min<int64_t>(m.nt, 2048)), dim3(64),
+                               (WN * (WN + 1) + 512) * sizeof(uint32_t), s, a);
         else
-            hipLaunchKernelGGL(ng_round_kernel, dim3(grid), dim3(256), m.lds, s, a);
+            hipLaunchKernelGGL(round_kernel(m.rowstore, false), dim3(grid), dim3(256), m.lds, s, a);
     }
     MH_HIP(hipGetLastError());
     return MHIP_OK;
@@ -1652,6 +1788,10 @@ int GeoRun::begin(hipStream_t s, bool *applicable, bool *active)
     Impl &m = *impl;
     static const bool off = [] { const char *e = dev_env("MHIP_NOFLAT"); return e && std::string(e) == "iterative"; }();
     m.debug = dev_env("MHIP_NG_DEBUG") != nullptr;
+    {   // MHIP_NG_ROWSTORE = 0 | 1 | 2 (development knob, read per request)
+        const char *e = dev_env("MHIP_NG_ROWSTORE");
+        m.rowstore = e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : NG_ROWSTORE;
+    }
     *applicable = false;
     *active = false;
     if (off || !filled || H < 3 || W < 3) return MHIP_OK;
@@ -1674,7 +1814,7 @@ int GeoRun::begin(hipStream_t s, bool *applicable, bool *active)
     m.nt = (int64_t)m.ntr * m.ntc;
     auto align = [](size_t x) { return (x + 255) & ~size_t(255); };
     const size_t o_d = 0, o_tab = align(o_d + (dist ? 0 : 4 * (size_t)n)), o_cnt = align(o_tab + 2048);
-    const size_t o_any = align(o_cnt + 8 * (C_STATS + 128 + 16)), o_mark = align(o_any + 4 * (size_t)(MAXR + BATCH));
+    const size_t o_any = align(o_cnt + 8 * C_END), o_mark = align(o_any + 4 * (size_t)(MAXR + BATCH));
     const size_t o_amark = align(o_mark + (size_t)m.nt + 8), o_list = align(o_amark + 4 * (size_t)m.nt), o_list2 = align(o_list + 4 * (size_t)m.nt);
     const size_t o_hdr = align(o_list2 + 4 * (size_t)m.nt), o_blk = align(o_hdr + 4 * (size_t)m.nt);
     MH_TRY(m.ws.alloc(o_blk + 4 * (size_t)m.nt * WN * WN + 256));
@@ -1703,7 +1843,8 @@ int GeoRun::begin(hipStream_t s, bool *applicable, bool *active)
         MH_HIP(hipGetDevice(&dev));
         std::lock_guard<std::mutex> lk(mu);
         if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            MH_HIP(hipFuncSetAttribute((const void *)ng_round_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds));
+            for (int rs = 0; rs <= 2; ++rs)
+                MH_HIP(hipFuncSetAttribute((const void *)round_kernel(rs, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds));
             MH_HIP(hipFuncSetAttribute((const void *)ng_first_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds));
             MH_HIP(hipFuncSetAttribute((const void *)ng_handover_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds));
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
@@ -1826,7 +1967,7 @@ int GeoRun::end(hipStream_t s, bool *ok, FillStats *st)
     else              // (a partial surface is checked by the caller once the relaxation has settled the irregular flats)
         hipLaunchKernelGGL(ng_assemble_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, filled, dist, out, n, seed_add, m.d_cnt);
     MH_HIP(hipGetLastError());
-    unsigned long long h_all[C_STATS + 128 + 16];
+    unsigned long long h_all[C_END];
     MH_HIP(hipMemcpyAsync(h_all, m.d_cnt, sizeof(h_all), hipMemcpyDeviceToHost, s));
     MH_HIP(stream_sync(s));
     if (allow_partial && h_all[C_UNREACHED]) partial = true;      // (the verification above then reported those cells: ignored)
@@ -1847,17 +1988,21 @@ int GeoRun::end(hipStream_t s, bool *ok, FillStats *st)
         for (int k = 0; k < 64; ++k) {
             st->visits += (int64_t)h_all[C_STATS + 2 * k];
             st->cycles += (int64_t)h_all[C_STATS + 2 * k + 1];
+            st->rows_stored += (int64_t)h_all[C_ROWS + k];
         }
+        st->rowstore = m.rowstore;
     }
     if (m.debug) {
         std::vector<uint32_t> cnt((size_t)m.round);
         MH_HIP(hipMemcpy(cnt.data(), m.d_any, 4 * (size_t)m.round, hipMemcpyDeviceToHost));
-        unsigned long long v = 0, cy = 0;
+        unsigned long long v = 0, cy = 0, rw = 0;
         for (int k = 0; k < 64; ++k) {
             v += h_all[C_STATS + 2 * k];
             cy += h_all[C_STATS + 2 * k + 1];
+            rw += h_all[C_ROWS + k];
         }
-        fprintf(stderr, "[noflat geodesic] tiles %lld, visits %llu, cycles %llu; tiles per round:", (long long)m.nt, v, cy);
+        fprintf(stderr, "[noflat geodesic] tiles %lld, visits %llu, cycles %llu, rows stored %llu (row store %d); tiles per round:", (long long)m.nt, v, cy, rw,
+                m.rowstore);
         for (int k = 1; k < m.round && k < 200; ++k) fprintf(stderr, " %u", cnt[k]);
 #ifdef NG_PROFILE
         for (int o = 0; o < 2; ++o) {
