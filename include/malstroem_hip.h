@@ -67,6 +67,16 @@ typedef struct { double vmax, vmin_pos; int64_t cells, pos; } mhip_zone_record;
 #define MHIP_ZSRC_DRAINDIST 103
 /* ... and the depth raster of the last mhip_ctx_inundate */
 #define MHIP_ZSRC_INUNDATION 104      /* mhip_ctx_zone_stats */
+/* ... and the raster of the last mhip_ctx_travel_time */
+#define MHIP_ZSRC_TRAVELTIME 105      /* mhip_ctx_zone_stats */
+/* travel time along the flow paths (mhip_step_cost below): the parameters of the velocity method v = k * sqrt(s) --
+ * k in m/s for overland cells and for channel cells (accum >= channel_threshold; +inf: one class), the least slope, the largest
+ * velocity, the length of a tick in seconds.  All float64, finite (channel_threshold may be +inf) and > 0.  numpy
+ * [('k_overland','<f8'),('k_channel','<f8'),('channel_threshold','<f8'),('smin','<f8'),('vmax','<f8'),('tick','<f8')] */
+typedef struct { double k_overland, k_channel, channel_threshold, smin, vmax, tick; } mhip_traveltime_params;
+/* the largest cost of one step in ticks, and the most bins of a time-area table */
+#define MHIP_TRAVELTIME_COST_MAX 1048575u
+#define MHIP_TRAVELTIME_MAX_BINS 256
 /* a source of mhip_ctx_polygonize that is no member of enum mhip_raster: the catchment raster of the last mhip_ctx_reach_catchments */
 #define MHIP_PSRC_REACHCATCH 110      /* mhip_ctx_polygonize */
 
@@ -183,6 +193,31 @@ int mhip_watersheds_i32(const uint8_t *flowdir, int32_t *labels_inout, int64_t H
  * MHIP_EINVAL.  unresolved (optional): the number of cells that hold -1. */
 int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H, int64_t W, double scale, int64_t nlab, float *out_dist,
                        mhip_index_record *records, int64_t *unresolved);
+
+/* Travel time along the flow paths (no reference counterpart; the definition is tests/_traveltime.py).
+ * step_cost: the time in ticks of the step that leaves every cell, by the velocity method of NRCS TR-55.  For a cell c with a code
+ * <= 7 whose downstream neighbour d lies inside the raster, every line one IEEE float64 rounding:
+ *     len  = (code & 1) ? cellsize * 1.4142135623730951 : cellsize
+ *     drop = double(z[c]) - double(z[d])
+ *     s    = drop / len;       if not (s >= smin): s = smin
+ *     k    = (accum given and accum[c] >= channel_threshold) ? k_channel : k_overland
+ *     v    = k * sqrt(s);      if v > vmax: v = vmax
+ *     q    = rint((len / v) / tick)                            (ties to even)
+ *     cost = q > MHIP_TRAVELTIME_COST_MAX ? MHIP_TRAVELTIME_COST_MAX : uint32(q)
+ * and 0 for every other cell.  accum may be NULL; saturated (optional): the cells clipped to the cap.  cellsize and the parameters
+ * are checked before any device work.
+ * flow_cost_distance: `cost` summed down the flow path.  Terminals, unresolved cells and labels are mhip_flow_distance's; ticks(c) =
+ * the sum of cost over the cells of the path from c up to, not including, its terminal, exact in 64 bits.  A cost above the cap
+ * anywhere in the raster is MHIP_EINVAL.  out = float(double(ticks) * tick), -1 where unresolved.  records (optional, nlab + 1): for
+ * label l the cell of the largest ticks among the cells whose terminal carries l (l = 0: an unlabelled terminal), compared as
+ * integers, the first in raster order among equals; value = double(ticks) * tick; (-inf, -1, -1) where nothing competes.  hist
+ * (optional, uint32 [nlab + 1][nbins], nbins in [1, MHIP_TRAVELTIME_MAX_BINS], bin_ticks >= 1; without it nbins = 0): a resolved cell
+ * with terminal label l adds one to hist[l][min(ticks / bin_ticks, nbins - 1)].  With records or hist a label outside [0, nlab] is
+ * MHIP_EINVAL; without them any label != 0 is a terminal.  unresolved (optional): the number of cells that hold -1. */
+int mhip_step_cost(const uint8_t *flowdir, const float *z, const double *accum, int64_t H, int64_t W, double cellsize,
+                   const mhip_traveltime_params *params, uint32_t *cost, int64_t *saturated);
+int mhip_flow_cost_distance(const uint8_t *flowdir, const int32_t *labels, const uint32_t *cost, int64_t H, int64_t W, double tick, int64_t nlab,
+                            float *out, mhip_index_record *records, int64_t nbins, uint64_t bin_ticks, uint32_t *hist, int64_t *unresolved);
 
 /* Height above the nearest drainage and the distance to it along the flow path (no reference counterpart; the definition is
  * tests/_hand.py).  A cell is a drainage cell when accum >= threshold (compared in float64; a NaN is none) or, with
@@ -549,6 +584,19 @@ int mhip_ctx_wet_at_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst)
 int mhip_ctx_flow_distance(mhip_ctx *ctx, double scale, int64_t *unresolved);
 int mhip_ctx_flow_distance_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
 int mhip_ctx_flow_distance_records(mhip_ctx *ctx, mhip_index_record *records);
+/* mhip_step_cost on the resident FLOWDIR, FILLED and -- with a finite channel_threshold -- ACCUM, then mhip_flow_cost_distance on
+ * that cost (pool scratch of the call), FLOWDIR and the (filtered or uploaded) LABELS of an undivided context, nlab = its "nlabels",
+ * with records; nbins = 0: no table, else nbins in [1, MHIP_TRAVELTIME_MAX_BINS] and bin_ticks >= 1.  A row band is refused.  The
+ * raster, the records and the table stay in buffers of the context (no members of enum mhip_raster) until FLOWDIR, LABELS, FILLED or
+ * ACCUM are written again: travel_time_rows copies rows [row0, row0 + nrows) of the raster, travel_time_records the nlabels + 1
+ * records, travel_time_hist the table [nlabels + 1][nbins] (MHIP_EINVAL unless nbins is the held table's).  mhip_ctx_get_i64
+ * "travel_time_unresolved" / "travel_time_saturated" / "travel_time_bins": the unresolved cells, the cells whose cost was clipped and
+ * the bins of the table (0: none) of the result held, -1: none. */
+int mhip_ctx_travel_time(mhip_ctx *ctx, double cellsize, const mhip_traveltime_params *params, int64_t nbins, uint64_t bin_ticks,
+                         int64_t *unresolved);
+int mhip_ctx_travel_time_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
+int mhip_ctx_travel_time_records(mhip_ctx *ctx, mhip_index_record *records);
+int mhip_ctx_travel_time_hist(mhip_ctx *ctx, int64_t nbins, uint32_t *hist);
 /* mhip_hand_f32 on the resident FLOWDIR, ACCUM and the elevation raster elev_source (MHIP_R_FILLED or MHIP_R_DEM) of an undivided
  * context, with stop_at_labels also on its (filtered or uploaded) LABELS; a row band is refused.  Both rasters stay in buffers of
  * the context (no members of enum mhip_raster) until FLOWDIR, ACCUM, the elevation raster or -- when they were used -- LABELS are
@@ -565,7 +613,7 @@ int mhip_ctx_burn_lines(mhip_ctx *ctx, int64_t nseg, const mhip_burn_segment *se
  * of the context (no member of enum mhip_raster).  The zones come from outside: no write of a raster drops them, a new rasterize
  * replaces them.  zones_rows copies rows [row0, row0 + nrows) of the raster.  zone_stats: mhip_zone_stats_f32 of a resident
  * float32 raster over the zones, records[nzone + 1]; source: MHIP_R_DEM, MHIP_R_FILLED, MHIP_R_DEPTHS, MHIP_R_FINALDEPTHS,
- * MHIP_ZSRC_WETAT, MHIP_ZSRC_FLOWDIST, MHIP_ZSRC_HAND, MHIP_ZSRC_DRAINDIST or MHIP_ZSRC_INUNDATION; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
+ * MHIP_ZSRC_WETAT, MHIP_ZSRC_FLOWDIST, MHIP_ZSRC_HAND, MHIP_ZSRC_DRAINDIST, MHIP_ZSRC_INUNDATION or MHIP_ZSRC_TRAVELTIME; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
  * without zones.  mhip_ctx_get_i64 "zones": nzone of the raster held, -1: none. */
 int mhip_ctx_rasterize_zones(mhip_ctx *ctx, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
                              const int32_t *ring_zone, int64_t nzone, int32_t grow);

@@ -26,7 +26,7 @@ BURN_RESULT_DTYPE = np.dtype([("z0", "<f8"), ("z1", "<f8"), ("cells", "<i8"), ("
 
 # object exposure (objects.py): mhip_zone_record; sources of mhip_ctx_zone_stats that are no member of mhip_raster
 ZONE_DTYPE = np.dtype([("vmax", "<f8"), ("vmin_pos", "<f8"), ("cells", "<i8"), ("pos", "<i8")])
-ZSRC_WETAT, ZSRC_FLOWDIST, ZSRC_HAND, ZSRC_DRAINDIST, ZSRC_INUNDATION = 100, 101, 102, 103, 104
+ZSRC_WETAT, ZSRC_FLOWDIST, ZSRC_HAND, ZSRC_DRAINDIST, ZSRC_INUNDATION, ZSRC_TRAVELTIME = 100, 101, 102, 103, 104, 105
 PSRC_REACHCATCH = 110      # a source of mhip_ctx_polygonize that is no member of mhip_raster
 
 # flow paths (flowpaths.py): mhip_reach_record; the end kinds of a reach
@@ -34,6 +34,11 @@ REACH_DTYPE = np.dtype([("first_cell", "<i8"), ("last_cell", "<i8"), ("end_cell"
                         ("n_orth", "<i4"), ("n_diag", "<i4"), ("end_kind", "<i4"), ("to_reach", "<i4"), ("to_label", "<i4"),
                         ("from_label", "<i4"), ("order", "<i4"), ("reserved", "<i4")])
 REACH_END = ("confluence", "edge", "sink", "bluespot", "below_threshold")
+
+# travel time (algorithms/flow.py): mhip_traveltime_params; the largest cost of a step in ticks, the most bins of a time-area table
+TRAVELTIME_DTYPE = np.dtype([("k_overland", "<f8"), ("k_channel", "<f8"), ("channel_threshold", "<f8"), ("smin", "<f8"), ("vmax", "<f8"),
+                             ("tick", "<f8")])
+TRAVELTIME_COST_MAX, TRAVELTIME_MAX_BINS = 2 ** 20 - 1, 256
 
 WETAT_MAX_EVENTS = 16    # MHIP_WETAT_MAX_EVENTS: most rain events of one wet_at call
 
@@ -71,6 +76,8 @@ SYMBOLS = [
     "mhip_label_hyps_layout", "mhip_label_hyps_f32", "mhip_hyps_levels", "mhip_final_depths_f32", "mhip_ctx_hyps", "mhip_ctx_hyps_fetch",
     "mhip_ctx_final_depths", "mhip_label_wet_at_f32", "mhip_ctx_wet_at", "mhip_ctx_wet_at_rows",
     "mhip_flow_distance", "mhip_ctx_flow_distance", "mhip_ctx_flow_distance_rows", "mhip_ctx_flow_distance_records",
+    "mhip_step_cost", "mhip_flow_cost_distance", "mhip_ctx_travel_time", "mhip_ctx_travel_time_rows", "mhip_ctx_travel_time_records",
+    "mhip_ctx_travel_time_hist",
     "mhip_hand_f32", "mhip_ctx_hand", "mhip_ctx_hand_rows",
     "mhip_reach_catchments_i32", "mhip_inundate_f32", "mhip_ctx_reach_catchments", "mhip_ctx_reach_catchments_rows", "mhip_ctx_inundate",
     "mhip_ctx_inundation_rows",

@@ -135,6 +135,108 @@ def flow_distance(flowdir, labelled=None, cellsize=1.0, records=False):
     return (out, rec, unresolved.value) if records else out
 
 
+# ---- travel time along the flow paths ---------------------------------------------------
+TRAVELTIME_DEFAULTS = dict(k_overland=4.918, k_channel=None, channel_threshold=float("inf"), smin=0.001, vmax=10.0, tick=0.001)
+
+
+def _positive(name, value, inf_ok=False):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (name, value))
+    if not (v > 0.0 and (np.isfinite(v) or (inf_ok and v == np.inf))):
+        raise ValueError("%s must be %s> 0, got %r" % (name, "" if inf_ok else "finite and ", value))
+    return v
+
+
+def check_traveltime_params(**params):
+    """The parameters of the velocity method ``v = k * sqrt(s)`` as a one-element ``_lib.TRAVELTIME_DTYPE`` array, the defaults
+    filled in: ``k_overland`` 4.918 m/s (NRCS TR-55, shallow concentrated flow, unpaved), ``k_channel`` = ``k_overland`` for the
+    cells with ``accum >= channel_threshold`` (``inf``: one class), ``smin`` 0.001, ``vmax`` 10 m/s, ``tick`` 0.001 s.  Every one
+    finite (``channel_threshold`` may be ``inf``) and > 0; ``ValueError`` otherwise, ``TypeError`` for a name that is none of them.
+    Nothing touches the library."""
+    unknown = sorted(set(params) - set(TRAVELTIME_DEFAULTS))
+    if unknown:
+        raise TypeError("unknown travel-time parameters %s; the parameters are %s" % (unknown, sorted(TRAVELTIME_DEFAULTS)))
+    p = dict(TRAVELTIME_DEFAULTS)
+    p.update(params)
+    if p["k_channel"] is None:
+        p["k_channel"] = p["k_overland"]
+    rec = np.zeros(1, dtype=_lib.TRAVELTIME_DTYPE)
+    for name in rec.dtype.names:
+        rec[name] = _positive(name, p[name], inf_ok=name == "channel_threshold")
+    return rec
+
+
+def check_bins(bins, tick):
+    """``bins = (nbins, seconds)`` of a time-area table as ``(nbins, bin_ticks)``: ``nbins`` in [1, 256], ``seconds`` finite and
+    > 0, ``bin_ticks = max(1, rint(seconds / tick))``; ``None`` is ``(0, 0)``: no table.  ``ValueError`` otherwise."""
+    if bins is None:
+        return 0, 0
+    try:
+        nbins, seconds = bins
+        ok = int(nbins) == nbins
+    except (TypeError, ValueError):
+        raise ValueError("bins must be (nbins, seconds), got %r" % (bins,))
+    if not ok or not 1 <= int(nbins) <= _lib.TRAVELTIME_MAX_BINS:
+        raise ValueError("bins: nbins must be an integer in [1, %d], got %r" % (_lib.TRAVELTIME_MAX_BINS, nbins))
+    seconds = _positive("bins: seconds", seconds)
+    bin_ticks = max(1, int(np.rint(seconds / tick)))
+    if bin_ticks >= 2 ** 63:
+        raise ValueError("bins: %r seconds are too many ticks of %r" % (seconds, tick))
+    return int(nbins), bin_ticks
+
+
+def step_cost(flowdir, surface, accum=None, cellsize=1.0, **params):
+    """The time of the step that leaves every cell, in ticks (uint32), by the velocity method of NRCS TR-55: ``v = k * sqrt(s)``
+    with the slope ``s`` between the cell and its downstream neighbour on ``surface`` (float32), at least ``smin``, ``v`` at most
+    ``vmax``, ``k = k_channel`` where ``accum`` (float64, optional) reaches ``channel_threshold``; 0 for a cell that steps nowhere.
+    The parameters: ``check_traveltime_params``.  Returns ``(cost, saturated)``: ``saturated`` counts the cells whose cost was
+    clipped to ``2**20 - 1`` ticks -- choose a coarser ``tick`` when there are any.  Evaluated in float64, bit for bit as
+    ``tests/_traveltime.py`` writes it.  No reference counterpart."""
+    scale, p = check_cellsize(cellsize), check_traveltime_params(**params)
+    fd = _flowdir(flowdir)
+    z = _like("surface", surface, fd.shape, np.float32)
+    acc = _like("accum", accum, fd.shape, DTYPE_ACCUM) if accum is not None else None
+    cost = np.empty(fd.shape, dtype=np.uint32)
+    saturated = ctypes.c_int64(0)
+    _lib.call("mhip_step_cost", _lib.ptr(fd), _lib.ptr(z), _lib.ptr(acc) if acc is not None else None, _lib.i64(fd.shape[0]), _lib.i64(fd.shape[1]),
+              ctypes.c_double(scale), _lib.ptr(p), _lib.ptr(cost), ctypes.byref(saturated))
+    return cost, saturated.value
+
+
+def travel_time(flowdir, cost, labelled=None, tick=0.001, records=False, bins=None):
+    """``cost`` (uint32 ticks per cell, at most ``2**20 - 1``: ``step_cost``, or any cost of the caller's) summed along the flow
+    path from every cell to the terminal it drains to -- ``flow_distance``'s terminals -- as float32 seconds
+    ``float32(float64(ticks) * tick)``; -1 where the walk never ends.  The sums are exact integers.  No reference counterpart
+    (DESIGN.md 18).
+
+    ``records=True`` or ``bins=(nbins, seconds)``: ``(raster, records, unresolved[, table])`` -- ``records[l]``
+    (``_lib.INDEX_DTYPE``, ``max(labelled) + 1`` entries) is the cell with the largest travel time among the cells whose terminal
+    carries label ``l`` (``l = 0``: an unlabelled terminal), compared as integer ticks, the first in raster order among equals: the
+    time of concentration of that watershed; ``table[l][b]`` (uint32) counts the cells of ``l`` whose travel time falls into bin
+    ``b`` of ``seconds`` each (``max(1, rint(seconds / tick))`` ticks), the last bin taking all that is later: the time-area table."""
+    tick = _positive("tick", tick)
+    nbins, bin_ticks = check_bins(bins, tick)
+    fd = _flowdir(flowdir)
+    cst = _like("cost", cost, fd.shape, np.uint32)
+    lab = _like("labelled", labelled, fd.shape, np.int32) if labelled is not None else None
+    full = bool(records) or nbins > 0
+    nlab = 0
+    if lab is not None and full:
+        nlab = max(int(lab.max()), 0) if lab.size else 0
+    out = np.empty(fd.shape, dtype=np.float32)
+    rec = np.zeros(nlab + 1, dtype=_lib.INDEX_DTYPE) if full else None
+    table = np.zeros((nlab + 1, nbins), dtype=np.uint32) if nbins else None
+    unresolved = ctypes.c_int64(0)
+    _lib.call("mhip_flow_cost_distance", _lib.ptr(fd), _lib.ptr(lab) if lab is not None else None, _lib.ptr(cst), _lib.i64(fd.shape[0]),
+              _lib.i64(fd.shape[1]), ctypes.c_double(tick), _lib.i64(nlab), _lib.ptr(out), _lib.ptr(rec) if full else None, _lib.i64(nbins),
+              ctypes.c_uint64(bin_ticks), _lib.ptr(table) if nbins else None, ctypes.byref(unresolved))
+    if not full:
+        return out
+    return (out, rec, unresolved.value, table) if nbins else (out, rec, unresolved.value)
+
+
 def check_hand_nodata(nodata):
     """The nodata value of a HAND raster as a float32 (``adaptations.check_nodata``'s rule, and it must fit the raster's type;
     ``ValueError`` otherwise; nothing touches the library)."""

@@ -94,6 +94,15 @@ class BluespotTool(object):
     -1 on a flow cycle).  Every pour point then also carries ``wshed_lfp``, the length in metres of the longest flow path of the
     bluespot's local watershed, and ``lfp_row`` / ``lfp_col``, the cell that path starts at.  Without it the layer is unchanged.
 
+    ``output_traveltime_raster`` (no reference counterpart): a raster writer for ``traveltime.tif`` -- per cell the travel
+    time in seconds along the flow path to the bluespot it drains to, by the velocity method on the filled surface with the cell size
+    ``abs(transform[1])`` (nodata -1 on a flow cycle), streamed in row windows.  ``traveltime``: a dict of the parameters of
+    ``HydroPipeline.travel_time`` (``k_overland``, ``k_channel``, ``channel_threshold``, ``smin``, ``vmax``, ``tick``, ``bins``,
+    ``allow_saturated``).  Every pour point then also carries ``wshed_tc``, the time of concentration of the bluespot's local
+    watershed in seconds, ``tc_row`` / ``tc_col``, the cell it starts at, and with ``bins`` ``time_area``, the cells of the watershed
+    per travel-time bin.  A finite ``channel_threshold`` needs the accumulated flow: ``traveltime_run_accum`` as
+    ``flowpaths_run_accum``.  Without the writer the layer is unchanged.  A tool that reads its inputs itself needs ``input_dem``.
+
     ``output_labeled_vector`` / ``output_watersheds_vector``: vector writers for the outlines of the bluespots / of their local
     watersheds, written after the respective raster from the resident rasters: one ``Polygon`` per bluespot with
     the attribute ``bspot_id``, as the reference's (bluespots.py:176-178, 187-189).  Without them every output is what it was.
@@ -123,7 +132,8 @@ class BluespotTool(object):
                  input_accum=None, input_dem=None, output_labeled_vector=None, output_watersheds_vector=None,
                  pipeline=None, device=0, output_flowlength_raster=None, output_flowpaths=None, flowpaths_threshold=None,
                  flowpaths_stop_at_bluespots=True, flowpaths_run_accum=False, output_hand_raster=None, output_drain_distance_raster=None,
-                 hand_threshold=None, hand_run_accum=False, output_reach_catchments_raster=None, output_reach_catchments_vector=None):
+                 hand_threshold=None, hand_run_accum=False, output_reach_catchments_raster=None, output_reach_catchments_vector=None,
+                 output_traveltime_raster=None, traveltime=None, traveltime_run_accum=False):
         self.input_depths = input_depths
         self.input_flowdir = input_flowdir
         self.input_bluespot_filter_function = input_bluespot_filter_function
@@ -152,6 +162,16 @@ class BluespotTool(object):
         if self.want_hand:
             self.hand_threshold = check_threshold(hand_threshold)
             assert self.input_dem or pipeline, "The height above drainage needs input_dem"
+        self.output_traveltime_raster = output_traveltime_raster
+        self.traveltime_run_accum = traveltime_run_accum
+        if output_traveltime_raster is not None:
+            from .algorithms.flow import check_bins, check_traveltime_params
+            self.traveltime = dict(traveltime or {})
+            call = {k: self.traveltime[k] for k in self.traveltime if k not in ("bins", "allow_saturated")}
+            p = check_traveltime_params(**call)      # (the parameters are checked before anything runs)
+            check_bins(self.traveltime.get("bins"), float(p["tick"][0]))
+            self.traveltime_classes = bool(np.isfinite(p["channel_threshold"][0]))
+            assert self.input_dem or pipeline, "The travel time needs input_dem"
         assert self.input_accum or self.input_dem or pipeline, "Either input_dem or input_accum must be specified"
         self.logger = logging.getLogger(__name__)
 
@@ -172,8 +192,8 @@ class BluespotTool(object):
                 # DEM invalidates every raster derived from the previous one
                 pipe.upload("dem", self.input_dem.read())
                 pipe.run("noflat")
-            elif self.want_hand:
-                pipe.upload("dem", self.input_dem.read())      # (the filled surface the heights are measured on)
+            elif self.want_hand or self.output_traveltime_raster is not None:
+                pipe.upload("dem", self.input_dem.read())      # (the filled surface the heights and the slopes are measured on)
                 pipe.run("fill")
             pipe.upload("depths", depths)
             pipe.upload("flowdir", self.input_flowdir.read())
@@ -212,9 +232,26 @@ class BluespotTool(object):
                 pipe.download_flow_distance_to(self.output_flowlength_raster)
                 for feature, lfp in zip(pour_points, pipe.flow_distance_records()):
                     feature['properties'].update(wshed_lfp=float(lfp['value']), lfp_row=int(lfp['row']), lfp_col=int(lfp['col']))
+            accum_run = False
+            if self.output_traveltime_raster is not None:
+                if self.traveltime_classes and (self.traveltime_run_accum or (own and not self.input_accum)):
+                    self.logger.info("Calculating flow accumulation")      # (the pour points are taken: they stay where they are)
+                    pipe.run("accum")
+                    accum_run = True
+                self.logger.info("Calculating travel times")
+                unresolved = pipe.travel_time(cell_width, **self.traveltime)
+                if unresolved:
+                    self.logger.warning("{} cells lie on or drain into a flow cycle: no travel time".format(unresolved))
+                pipe.download_travel_time_to(self.output_traveltime_raster)
+                table = pipe.time_area() if self.traveltime.get("bins") is not None else None
+                for l, (feature, tc) in enumerate(zip(pour_points, pipe.travel_time_records())):
+                    feature['properties'].update(wshed_tc=float(tc['value']), tc_row=int(tc['row']), tc_col=int(tc['col']))
+                    if table is not None:
+                        feature['properties']['time_area'] = [int(v) for v in table[l]]
             self.output_pourpoints.write_geojson_features(dict(type="FeatureCollection", features=pour_points))
             # the accumulated flow for the flow paths and the heights above drainage, once, where the pipeline holds none yet
-            if (((self.output_flowpaths is not None or self.want_catchments) and (self.flowpaths_run_accum or (own and not self.input_accum))) or
+            if not accum_run and (
+                    ((self.output_flowpaths is not None or self.want_catchments) and (self.flowpaths_run_accum or (own and not self.input_accum))) or
                     (self.want_hand and (self.hand_run_accum or (own and not self.input_accum)))):
                 self.logger.info("Calculating flow accumulation")
                 pipe.run("accum")

@@ -90,7 +90,7 @@ def parse_filter(filter):
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
                 finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
                 flowpaths=None, flowpaths_stop_at_bluespots=True, hand=None, reach_catchments=False, inundation=None,
-                adaptations=None):
+                traveltime=False, adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -115,6 +115,12 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     ``flowlength``: also write ``flowlength.tif`` -- per cell the distance in metres along the flow path to the bluespot it drains to
     (nodata -1) -- and give every pour point ``wshed_lfp`` / ``lfp_row`` / ``lfp_col``, the longest flow path of its local watershed
     (``BluespotTool(output_flowlength_raster=...)``); the dict gains ``flowlength``.  Not on row bands yet.
+
+    ``traveltime`` (keyword only): ``True`` or a dict of the parameters of ``HydroPipeline.travel_time``.  Also writes
+    ``traveltime.tif`` -- per cell the travel time in seconds along the flow path to the bluespot it drains to, by the velocity method
+    of NRCS TR-55 on the filled surface (nodata -1) -- and gives every pour point ``wshed_tc`` / ``tc_row`` / ``tc_col``, the time of
+    concentration of its local watershed, and with ``bins=(nbins, seconds)`` ``time_area``, its cells per travel-time bin
+    (``BluespotTool(output_traveltime_raster=...)``); the dict gains ``traveltime``.  Not on row bands yet.
 
     ``adaptations``: the path of a GeoJSON file of culvert / dike lines (``adaptations.lines_from_features`` names the properties)
     that are burnt into the DEM before anything is computed; also writes ``dem_adapted.tif`` and the vector layer ``adaptations``:
@@ -177,6 +183,14 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         from .flowpaths import check_threshold
         flowpaths = check_threshold(flowpaths) if flowpaths is not None else None
         hand = check_threshold(hand) if hand is not None else None
+    if traveltime is True:
+        traveltime = {}      # (the defaults)
+    elif traveltime is False or traveltime is None:
+        traveltime = None
+    elif isinstance(traveltime, dict):
+        traveltime = dict(traveltime)
+    else:
+        raise ValueError("traveltime must be True or a dict of parameters, got %r" % (traveltime,))
     if (onset or not final_rasters) and not finalstate:
         raise ValueError("onset and final_rasters belong to the final state: pass finalstate=True")
     if comm is not None and comm.size > 1:
@@ -188,6 +202,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                                       "label), which is not built yet; run it on one context")
         if flowlength:
             raise NotImplementedError("flowlength on row bands: a flow path crosses the seams between the bands, and the walk over "
+                                      "them is not built yet; run it on one context")
+        if traveltime is not None:
+            raise NotImplementedError("traveltime on row bands: a flow path crosses the seams between the bands, and the walk over "
                                       "them is not built yet; run it on one context")
         if adaptations is not None:
             raise NotImplementedError("adaptations on row bands: a line crosses the seams between the bands, and its levels hang on "
@@ -238,6 +255,7 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         watershed_writer = io.RasterWriter(os.path.join(outdir, 'watersheds.tif'), tr, crs, 0)
         labeled_writer = io.RasterWriter(os.path.join(outdir, 'bluespots.tif'), tr, crs, 0)
         flowlength_path = os.path.join(outdir, 'flowlength.tif')
+        traveltime_path = os.path.join(outdir, 'traveltime.tif')
         labeled_vector_writer = io.VectorWriter('GeoJSON', outvector, 'bluespots', None, None, crs) if vector else None
         watershed_vector_writer = io.VectorWriter('GeoJSON', outvector, 'watersheds', None, None, crs) if vector else None
         flowpaths_writer = io.VectorWriter('GeoJSON', outvector, 'flowpaths', None, None, crs) if flowpaths is not None else None
@@ -255,7 +273,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                      output_drain_distance_raster=io.RasterWriter(hand_dist_path, tr, crs, -1) if hand is not None else None,
                      hand_threshold=hand, hand_run_accum=not accum,
                      output_reach_catchments_raster=io.RasterWriter(catch_path, tr, crs, 0) if reach_catchments else None,
-                     output_reach_catchments_vector=catch_vector_writer).process()
+                     output_reach_catchments_vector=catch_vector_writer,
+                     output_traveltime_raster=io.RasterWriter(traveltime_path, tr, crs, -1) if traveltime is not None else None,
+                     traveltime=traveltime, traveltime_run_accum=not accum).process()
         inundation_paths = {}
         if stages:
             # (the heights and the catchments are resident, made with one threshold at the bluespots: nothing has been written since)
@@ -302,6 +322,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
             res.update(bluespots_vector=labeled_vector_writer.filepath, watersheds_vector=watershed_vector_writer.filepath)
         if flowlength:
             res["flowlength"] = flowlength_path
+        if traveltime is not None:
+            res["traveltime"] = traveltime_path
         if flowpaths is not None:
             res["flowpaths"] = flowpaths_writer.filepath
         if hand is not None:

@@ -407,6 +407,46 @@ int mhip_flow_distance(const uint8_t *flowdir, const int32_t *labels, int64_t H,
     return download(out_dist, d_out, n * 4, s);
 }
 
+int mhip_step_cost(const uint8_t *flowdir, const float *z, const double *accum, int64_t H, int64_t W, double cellsize,
+                   const mhip_traveltime_params *params, uint32_t *cost, int64_t *saturated)
+{
+    MH_ARG(flowdir && z && cost && H >= 1 && W >= 1, "step_cost(flowdir, z, accum, H>=1, W>=1, cellsize, params, cost, saturated)");
+    MH_TRY(travel_time_check(cellsize, params));
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    const size_t n = (size_t)(H * W);
+    DevBuf d_fd, d_z, d_a, d_c;
+    MH_TRY(upload(d_fd, flowdir, n, s));
+    MH_TRY(upload(d_z, z, n * 4, s));
+    if (accum) MH_TRY(upload(d_a, accum, n * 8, s));
+    MH_TRY(d_c.alloc(n * 4));
+    MH_TRY(step_cost_dev(d_fd.as<uint8_t>(), d_z.as<float>(), accum ? d_a.as<double>() : nullptr, H, W, cellsize, *params, d_c.as<uint32_t>(), saturated, s));
+    return download(cost, d_c, n * 4, s);
+}
+
+int mhip_flow_cost_distance(const uint8_t *flowdir, const int32_t *labels, const uint32_t *cost, int64_t H, int64_t W, double tick, int64_t nlab,
+                            float *out, mhip_index_record *records, int64_t nbins, uint64_t bin_ticks, uint32_t *hist, int64_t *unresolved)
+{
+    MH_ARG(flowdir && cost && out && H >= 1 && W >= 1 && nlab >= 0,
+           "flow_cost_distance(flowdir, labels, cost, H>=1, W>=1, tick, nlab>=0, out, records, nbins, bin_ticks, hist, unresolved)");
+    MH_TRY(travel_time_walk_check(tick, nbins, bin_ticks, hist != nullptr));
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    const size_t n = (size_t)(H * W), nrec = (size_t)(nlab + 1), hbytes = 4 * nrec * (size_t)nbins;
+    DevBuf d_fd, d_l, d_c, d_out, d_rec, d_h;
+    MH_TRY(upload(d_fd, flowdir, n, s));
+    if (labels) MH_TRY(upload(d_l, labels, n * 4, s));
+    MH_TRY(upload(d_c, cost, n * 4, s));
+    MH_TRY(d_out.alloc(n * 4));
+    if (records) MH_TRY(d_rec.alloc(sizeof(mhip_index_record) * nrec));
+    if (hist) MH_TRY(d_h.alloc(hbytes));
+    MH_TRY(flow_cost_distance_dev(d_fd.as<uint8_t>(), labels ? d_l.as<int32_t>() : nullptr, d_c.as<uint32_t>(), H, W, tick, nlab, d_out.as<float>(),
+                                  records ? d_rec.as<mhip_index_record>() : nullptr, nbins, bin_ticks, hist ? d_h.as<uint32_t>() : nullptr, unresolved, s));
+    if (records) MH_HIP(hipMemcpyAsync(records, d_rec.p, sizeof(mhip_index_record) * nrec, hipMemcpyDeviceToHost, s));
+    if (hist) MH_HIP(hipMemcpyAsync(hist, d_h.p, hbytes, hipMemcpyDeviceToHost, s));
+    return download(out, d_out, n * 4, s);
+}
+
 int mhip_hand_f32(const uint8_t *flowdir, const double *accum, const float *elev, const int32_t *labels, int64_t H, int64_t W, double threshold,
                   double scale, float nodata, float *out_hand, float *out_dist, int64_t *undrained)
 {

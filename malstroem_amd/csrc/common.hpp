@@ -536,6 +536,18 @@ int flow_walk_dev(const uint8_t *d_fd, const double *d_acc, const int32_t *d_lab
                   hipStream_t s);
 // the count and the `bad` word of the final pass, once the stream is idle (the scratch and the nodes go back to the pool with `w`)
 int flow_walk_count(FlowWalk &w, int64_t *count, bool *bad, hipStream_t s);
+// traveltime.hip: travel time along the flow paths.  travel_time_check / travel_time_walk_check: the argument rules
+// of the two calls (MHIP_EINVAL; no device work) -- cellsize and every parameter finite and > 0 (channel_threshold may be +inf); tick
+// finite and > 0, and with a table nbins in [1, 256] and bin_ticks >= 1, without one nbins == 0.  step_cost_dev: the cost raster
+// (d_acc may be nullptr) and the cells clipped to the cap.  flow_cost_distance_dev: flow_distance_dev with the cost summed down the
+// path; d_rec (nlab + 1 records) and d_hist (uint32 [nlab + 1][nbins]) are optional.  MHIP_EINVAL: a cost above the cap; with d_rec
+// or d_hist, a label outside [0, nlab].  Both synchronise.
+int travel_time_check(double cellsize, const mhip_traveltime_params *p);
+int travel_time_walk_check(double tick, int64_t nbins, uint64_t bin_ticks, bool table);
+int step_cost_dev(const uint8_t *d_fd, const float *d_z, const double *d_acc, int64_t H, int64_t W, double cellsize, const mhip_traveltime_params &p,
+                  uint32_t *d_cost, int64_t *saturated, hipStream_t s);
+int flow_cost_distance_dev(const uint8_t *d_fd, const int32_t *d_lab, const uint32_t *d_cost, int64_t H, int64_t W, double tick, int64_t nlab, float *d_out,
+                           mhip_index_record *d_rec, int64_t nbins, uint64_t bin_ticks, uint32_t *d_hist, int64_t *unresolved, hipStream_t s);
 // hand.hip: height above the nearest drainage and the distance to it along the flow path.  A drainage cell:
 // d_acc >= threshold (float64; a NaN is none) or, with d_lab, a label != 0.  d_hand = elev[c] - elev[D(c)] (a NaN result is the
 // canonical quiet NaN), `nodata` for a cell whose walk ends without drainage; d_dist (optional) as flow_distance_dev's raster, -1

@@ -26,6 +26,20 @@ static void drop_flow_distance(mhip_ctx *c)
     c->fdist_rec.release();
 }
 
+// `which` was written: the result of mhip_ctx_travel_time goes with any of the four rasters it is made from (which < 0: a new call)
+static void drop_travel_time(mhip_ctx *c, int which)
+{
+    if (!(which < 0 || which == MHIP_R_FLOWDIR || which == MHIP_R_LABELS || which == MHIP_R_FILLED || which == MHIP_R_ACCUM)) return;
+    if (c->tt_unresolved < 0) return;      // (nothing held: the stages' writes take no lock for this)
+    std::lock_guard<std::mutex> lk(c->tt_mu);
+    c->tt_unresolved = -1;      // (the call that fills the buffers has synchronised: nothing on the device still uses them)
+    c->tt_saturated = -1;
+    c->tt_bins = 0;
+    c->tt_out.release();
+    c->tt_rec.release();
+    c->tt_hist.release();
+}
+
 // the depths of mhip_ctx_inundate go with either of the two results they were made from
 static void drop_inundation(mhip_ctx *c)
 {
@@ -64,6 +78,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
 {
     drop_hand(c, which);
     drop_reach_catchments(c, which);
+    drop_travel_time(c, which);
     switch (which) {
     case MHIP_R_DEM:    // a new DEM invalidates everything derived from the previous one
         c->noflat_pending = false;      // (a surface nobody has asked for goes with have[NOFLAT])
@@ -131,6 +146,7 @@ int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes)
         {c->rcatch_nreach >= 0, c->rcatch_out, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters"},
         {c->inund_held > 0, c->inund_out, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments"},
         {c->nzone >= 0, c->zones, "ctx_zones_rows needs mhip_ctx_rasterize_zones"},
+        {c->tt_unresolved >= 0, c->tt_out, "ctx_travel_time_rows needs mhip_ctx_travel_time on the resident rasters"},
     };
     MH_ARG(t[id].held && t[id].buf.p, t[id].needs);
     *ptr = t[id].buf.p;
@@ -500,7 +516,10 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
     else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels
     else if (k == "flow_distance_unresolved") *value = c->fdist_unresolved;   // -1: no result of mhip_ctx_flow_distance on the resident flow directions and labels
-    else if (k == "hand_undrained") *value = c->hand_undrained;      // -1: no result of mhip_ctx_hand on the resident rasters
+    else if (k == "travel_time_unresolved") *value = c->tt_unresolved;   // -1: no result of mhip_ctx_travel_time on the resident rasters
+    else if (k == "travel_time_saturated") *value = c->tt_unresolved >= 0 ? c->tt_saturated : -1;   // the cells whose cost was clipped to the cap
+    else if (k == "travel_time_bins") *value = c->tt_unresolved >= 0 ? c->tt_bins : -1;             // the bins of the table held, 0: no table
+    else if (k == "hand_undrained") *value = c->hand_undrained;     // -1: no result of mhip_ctx_hand on the resident rasters
     else if (k == "reach_catchments") *value = c->rcatch_nreach;     // -1: no result of mhip_ctx_reach_catchments on the resident rasters
     else if (k == "inundation") *value = c->inund_held;              // 1: a depth raster of mhip_ctx_inundate is held, -1: none
     else if (k == "zones") *value = c->nzone;                       // -1: no zone raster of mhip_ctx_rasterize_zones
@@ -707,6 +726,61 @@ int mhip_ctx_flow_distance_records(mhip_ctx *c, mhip_index_record *records)
     return ctx_fetch(c, c->fdist_rec, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
 }
 
+/* ---- travel time to the receiving bluespot, time of concentration and time-area table per watershed (traveltime.hip) ------------- */
+int mhip_ctx_travel_time(mhip_ctx *c, double cellsize, const mhip_traveltime_params *params, int64_t nbins, uint64_t bin_ticks, int64_t *unresolved)
+{
+    MH_ARG(c && unresolved, "ctx_travel_time(ctx, cellsize, params, nbins, bin_ticks, unresolved)");
+    MH_TRY(travel_time_check(cellsize, params));
+    MH_TRY(travel_time_walk_check(params->tick, nbins, bin_ticks, nbins != 0));
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "travel time on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_travel_time needs the FLOWDIR and LABELS rasters");
+    MH_ARG(c->have[MHIP_R_FILLED], "ctx_travel_time needs the FILLED raster");
+    const bool classes = params->channel_threshold <= 1.7976931348623157e308;      // (finite: two classes are live)
+    MH_ARG(!classes || c->have[MHIP_R_ACCUM], "ctx_travel_time with a finite channel_threshold needs the ACCUM raster");
+    MH_ARG(c->labels_filtered, "ctx_travel_time needs mhip_ctx_apply_keep after the LABEL run");
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    MH_TRY(ctx_label_max(c, s));
+    const int64_t nlab = c->nlabels, n = c->H * c->W;
+    drop_travel_time(c, -1);
+    DevBuf cost;      // (scratch of this call)
+    MH_TRY(cost.alloc(4 * (size_t)n));
+    int64_t sat = 0, u = 0;
+    MH_TRY(step_cost_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_FILLED].as<float>(), classes ? c->r[MHIP_R_ACCUM].as<double>() : nullptr, c->H, c->W,
+                         cellsize, *params, cost.as<uint32_t>(), &sat, s));
+    MH_TRY(c->tt_out.alloc(4 * (size_t)n));
+    MH_TRY(c->tt_rec.alloc(sizeof(mhip_index_record) * (size_t)(nlab + 1)));
+    if (nbins) MH_TRY(c->tt_hist.alloc(4 * (size_t)(nlab + 1) * (size_t)nbins));
+    MH_TRY(flow_cost_distance_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_LABELS].as<int32_t>(), cost.as<uint32_t>(), c->H, c->W, params->tick, nlab,
+                                  c->tt_out.as<float>(), c->tt_rec.as<mhip_index_record>(), nbins, bin_ticks, nbins ? c->tt_hist.as<uint32_t>() : nullptr, &u,
+                                  s));      // (synchronises)
+    c->tt_saturated = sat;
+    c->tt_bins = nbins;
+    c->tt_unresolved = u;
+    *unresolved = u;
+    return MHIP_OK;
+}
+
+int mhip_ctx_travel_time_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
+{
+    return held_rows(c, HELD_TRAVELTIME, row0, nrows, dst, "ctx_travel_time_rows(ctx, row0, nrows, dst)");
+}
+
+int mhip_ctx_travel_time_records(mhip_ctx *c, mhip_index_record *records)
+{
+    MH_ARG(c && records, "ctx_travel_time_records(ctx, records)");
+    MH_ARG(c->tt_unresolved >= 0 && c->tt_rec.p, "ctx_travel_time_records needs mhip_ctx_travel_time on the resident rasters");
+    return ctx_fetch(c, c->tt_rec, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
+}
+
+int mhip_ctx_travel_time_hist(mhip_ctx *c, int64_t nbins, uint32_t *hist)
+{
+    MH_ARG(c && hist, "ctx_travel_time_hist(ctx, nbins, hist)");
+    MH_ARG(c->tt_unresolved >= 0 && c->tt_bins > 0 && c->tt_hist.p, "ctx_travel_time_hist needs mhip_ctx_travel_time with a table on the resident rasters");
+    MH_ARG(nbins == c->tt_bins, "ctx_travel_time_hist: nbins is not the held table's");
+    return ctx_fetch(c, c->tt_hist, 4 * (size_t)(c->nlabels + 1) * (size_t)nbins, hist);
+}
+
 /* ---- height above the nearest drainage and the distance to it (hand.hip) ---------------------------------------------------------- */
 int mhip_ctx_hand(mhip_ctx *c, int32_t elev_source, double threshold, int32_t stop_at_labels, double scale, float nodata, int64_t *undrained)
 {
@@ -787,7 +861,7 @@ int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
     MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
     const bool member = source == MHIP_R_DEM || source == MHIP_R_FILLED || source == MHIP_R_DEPTHS || source == MHIP_R_FINALDEPTHS;
     const int id = source == MHIP_ZSRC_WETAT ? HELD_WETAT : source == MHIP_ZSRC_FLOWDIST ? HELD_FLOWDIST : source == MHIP_ZSRC_HAND ? HELD_HAND :
-                   source == MHIP_ZSRC_DRAINDIST ? HELD_DRAINDIST : source == MHIP_ZSRC_INUNDATION ? HELD_INUNDATION : -1;
+                   source == MHIP_ZSRC_DRAINDIST ? HELD_DRAINDIST : source == MHIP_ZSRC_INUNDATION ? HELD_INUNDATION : source == MHIP_ZSRC_TRAVELTIME ? HELD_TRAVELTIME : -1;
     MH_ARG(member || id >= 0, "ctx_zone_stats: the source is no float32 raster of the context");
     void *src = member ? c->r[source].p : nullptr;
     if (member) MH_ARG(c->have[source], "raster has not been computed or uploaded");

@@ -127,6 +127,13 @@ struct mhip_ctx {
     mh::DevBuf fdist_out, fdist_rec;
     std::atomic<int64_t> fdist_unresolved{-1};
     std::mutex fdist_mu;
+    // the raster (float32, H x W; no member of mhip_raster), the records and the time-area table (tt_bins bins a label; 0: none) of
+    // the last mhip_ctx_travel_time, its unresolved cells (-1: none) and the cells whose cost was clipped.  They live and die with
+    // FLOWDIR, LABELS, FILLED and ACCUM; handed back under the lock, as above
+    mh::DevBuf tt_out, tt_rec, tt_hist;
+    std::atomic<int64_t> tt_unresolved{-1};
+    int64_t tt_saturated = -1, tt_bins = 0;
+    std::mutex tt_mu;
     // the two rasters (float32, H x W; no members of mhip_raster) of the last mhip_ctx_hand and its number of undrained cells; -1:
     // none.  They live and die with FLOWDIR, ACCUM, the elevation raster `hand_src` and, where `hand_labels` says they were used,
     // LABELS; handed back under the lock, as above
@@ -256,10 +263,10 @@ inline int ctx_settle(mhip_ctx *c, int which, bool write)
 // checked the window against H_owned.  Every whole-raster and windowed transfer of ctx.hip is this call.
 int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, int64_t nrows, void *host, hipMemcpyKind kind);
 // ---- the rasters a context holds outside mhip_raster, wherever they are read (ctx.hip) ------------------------------------------
-// wet_at, flow distance, hand and the distance to the drainage, reach catchments, inundation depths, zones: each lives behind a
+// wet_at, flow distance, hand and the distance to the drainage, reach catchments, inundation depths, zones, travel time: each lives behind a
 // sentinel of its own, which the drop_* functions of ctx.hip clear.  ctx_held is the one test "is it held, and where": MHIP_EINVAL
 // with the message of that raster's mhip_ctx_*_rows getter, or the device pointer and (optional) the bytes of an element.
-enum HeldRaster { HELD_WETAT, HELD_FLOWDIST, HELD_HAND, HELD_DRAINDIST, HELD_REACHCATCH, HELD_INUNDATION, HELD_ZONES, HELD_COUNT_ };
+enum HeldRaster { HELD_WETAT, HELD_FLOWDIST, HELD_HAND, HELD_DRAINDIST, HELD_REACHCATCH, HELD_INUNDATION, HELD_ZONES, HELD_TRAVELTIME, HELD_COUNT_ };
 int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes = nullptr);
 // `bytes` of a record buffer to `host` on the main stream, synchronised: every record getter after its validity test
 int ctx_fetch(mhip_ctx *c, const DevBuf &buf, size_t bytes, void *host);

@@ -221,6 +221,62 @@ class HydroPipeline(CtxHandle):
         """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
         write_windows(writer, self.shape, np.float32, self.download_flow_distance_rows, max_rows)
 
+    # ---- travel time to the receiving bluespot, time of concentration and time-area table per watershed (DESIGN.md 18) -------
+    def travel_time(self, cellsize=1.0, bins=None, allow_saturated=False, **params):
+        """Travel time along the flow path from every cell to the bluespot (or raster edge, or sink) it drains to, in seconds, by the
+        velocity method on the resident flow directions, filled surface, (filtered or uploaded) labels and -- with a finite
+        ``channel_threshold`` -- accumulated flow; the parameters are ``algorithms.flow.check_traveltime_params``'s,
+        ``bins=(nbins, seconds)`` asks for the time-area table.  Returns the number of cells whose walk never ends (they hold -1).
+        ``ValueError`` naming ``tick`` when the cost of a step was clipped to ``2**20 - 1`` ticks, unless ``allow_saturated``.  The
+        raster, the records and the table stay on the device for ``download_travel_time`` / ``download_travel_time_to`` /
+        ``travel_time_records`` / ``time_area`` until one of the rasters they were made from is written again."""
+        from .algorithms.flow import check_bins, check_cellsize, check_traveltime_params
+        scale, p = check_cellsize(cellsize), check_traveltime_params(**params)
+        nbins, bin_ticks = check_bins(bins, float(p["tick"][0]))
+        unresolved = ctypes.c_int64(0)
+        _lib.call("mhip_ctx_travel_time", self._ctx, ctypes.c_double(scale), _lib.ptr(p), _lib.i64(nbins), ctypes.c_uint64(bin_ticks),
+                  ctypes.byref(unresolved))
+        saturated = self.get_int("travel_time_saturated")
+        if saturated > 0 and not allow_saturated:
+            raise ValueError("travel_time: the cost of %d cells exceeds %d ticks and was clipped; choose a coarser tick than %r "
+                             "(or allow_saturated=True)" % (saturated, _lib.TRAVELTIME_COST_MAX, float(p["tick"][0])))
+        return unresolved.value
+
+    def _travel_time_held(self):
+        if self.get_int("travel_time_unresolved") < 0:
+            raise ValueError("travel_time() has not been run on the resident rasters")
+
+    def travel_time_records(self):
+        """``records[l]`` (``nlabels + 1`` of ``_lib.INDEX_DTYPE``): the time of concentration of bluespot ``l``'s local watershed in
+        seconds and the cell it starts at (``l = 0``: of what drains to no bluespot); ``ValueError`` once a raster it was made from
+        is gone."""
+        self._travel_time_held()
+        rec = np.zeros(self.get_int("nlabels") + 1, dtype=INDEX_DTYPE)
+        _lib.call("mhip_ctx_travel_time_records", self._ctx, _lib.ptr(rec))
+        return rec
+
+    def time_area(self):
+        """The time-area table of the last ``travel_time(bins=...)``: uint32 ``[nlabels + 1, nbins]``, cells per watershed and
+        travel-time bin; ``ValueError`` when none is held."""
+        self._travel_time_held()
+        nbins = self.get_int("travel_time_bins")
+        if nbins <= 0:
+            raise ValueError("travel_time() has been run without bins")
+        table = np.zeros((self.get_int("nlabels") + 1, nbins), dtype=np.uint32)
+        _lib.call("mhip_ctx_travel_time_hist", self._ctx, _lib.i64(nbins), _lib.ptr(table))
+        return table
+
+    def download_travel_time_rows(self, row0, nrows):
+        return self._held_rows("mhip_ctx_travel_time_rows", np.float32, row0, nrows)
+
+    def download_travel_time(self):
+        """The raster of the last ``travel_time`` (float32 seconds); ``ValueError`` once a raster it was made from is gone."""
+        return self.download_travel_time_rows(0, self.shape[0])
+
+    def download_travel_time_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.float32, self.download_travel_time_rows, max_rows)
+
     # ---- height above the nearest drainage and the distance to it (DESIGN.md 16) ------------------------------
     HAND_SOURCES = {"filled": _lib.R_FILLED, "dem": _lib.R_DEM}
 
@@ -282,7 +338,7 @@ class HydroPipeline(CtxHandle):
     # ---- object exposure: polygons to a zone raster, a resident raster reduced per zone (objects.py) -----
     ZONE_SOURCES = {"dem": _lib.R_DEM, "filled": _lib.R_FILLED, "depths": _lib.R_DEPTHS, "finaldepths": _lib.R_FINALDEPTHS,
                     "wet_at": _lib.ZSRC_WETAT, "flow_distance": _lib.ZSRC_FLOWDIST, "hand": _lib.ZSRC_HAND,
-                    "drain_distance": _lib.ZSRC_DRAINDIST, "inundation": _lib.ZSRC_INUNDATION}
+                    "drain_distance": _lib.ZSRC_DRAINDIST, "inundation": _lib.ZSRC_INUNDATION, "travel_time": _lib.ZSRC_TRAVELTIME}
 
     def rasterize_zones(self, xy, ring_offsets, ring_zone, nzone, grow=0):
         """Rasterize polygons (``objects.rings_from_features``) at the pipeline's shape; the zone raster stays on the device for
@@ -295,7 +351,7 @@ class HydroPipeline(CtxHandle):
 
     def zone_stats(self, source):
         """``nzone + 1`` records (``_lib.ZONE_DTYPE``) of a resident float32 raster over the zones: ``source`` is ``"dem"``,
-        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"``, ``"flow_distance"``, ``"hand"``, ``"drain_distance"`` or ``"inundation"``.  ``ValueError`` without zones or when the
+        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"``, ``"flow_distance"``, ``"hand"``, ``"drain_distance"``, ``"inundation"`` or ``"travel_time"``.  ``ValueError`` without zones or when the
         source has not been computed.  (``"hand"``: ``vmin_pos`` is the lowest positive height above drainage of an object's cells.
         The negative nodata of its undrained cells is never the largest value of a zone that has one drained cell, and is never
         positive: it shows in ``vmax`` only where no cell of the zone is drained.)"""
