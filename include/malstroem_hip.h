@@ -556,7 +556,10 @@ int mhip_ctx_get_f64(mhip_ctx *ctx, const char *key, double *value);  /* "short"
 /* label filter between MHIP_STAGE_LABEL and MHIP_STAGE_WATERSHED (reference bluespots.py:165-172):
  * download raw stats (nlabels_raw+1 records), decide on host, upload keep flags.
  * The three record getters (and mhip_ctx_band_fetch / _gather / _foreign_counts) return the records of the RESIDENT rasters or
- * MHIP_EINVAL: a raster that was written again -- by a stage, an upload, a band call -- takes the records derived from it down. */
+ * MHIP_EINVAL: a raster that was written again -- by a stage, an upload, a band call -- takes the records derived from it down.
+ * raw_stats describes the depths the labelling read: MHIP_EINVAL once DEPTHS has been written since.  apply_keep(NULL) then takes
+ * the statistics of the resident depths instead of the labelling's (none resident: no statistics until mhip_ctx_hyps); apply_keep
+ * with a filter needs the DEPTHS raster and returns MHIP_EINVAL without it, the labels as they were. */
 int mhip_ctx_raw_stats(mhip_ctx *ctx, mhip_stat_record *records);
 int mhip_ctx_apply_keep(mhip_ctx *ctx, const uint8_t *keep);          /* NULL = keep all */
 int mhip_ctx_stats(mhip_ctx *ctx, mhip_stat_record *records);         /* nlabels+1, after apply_keep */

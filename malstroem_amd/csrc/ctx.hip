@@ -93,6 +93,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
         break;
     case MHIP_R_DEPTHS:
         c->stats_valid = false;
+        c->raw_stats_valid = false;      // (the labelling's statistics describe the depths it read)
         drop_hyps(c);
         break;
     case MHIP_R_NOFLAT:
@@ -112,6 +113,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
         c->nlabels = c->nlabels_raw = -1;
         c->labels_components = false;
         c->stats_valid = false;
+        c->raw_stats_valid = false;
         c->ws_counts_valid = false;
         c->pour_valid = false;
         drop_hyps(c);
@@ -210,13 +212,18 @@ int ctx_label_max(mhip_ctx *c, hipStream_t s)
 int ctx_apply_keep_on(mhip_ctx *c, const uint8_t *keep, hipStream_t s)
 {
     MH_ARG(c && c->have[MHIP_R_LABELS] && c->nlabels_raw >= 0 && !c->labels_filtered, "ctx_apply_keep needs a fresh LABEL run");
+    // (a filter's statistics are a pass over the depths: a raster whose last window has not arrived is none; refused with the labels as they were)
+    MH_ARG(!keep || c->have[MHIP_R_DEPTHS], "ctx_apply_keep with a filter needs the DEPTHS raster");
     const int64_t n = c->H * c->W;
-    // a write of LABELS that renumbers them: the raw count stays known, and kept components stay components
+    // a write of LABELS that renumbers them: the raw count stays known, kept components stay components, and the raw statistics
+    // still describe the resident depths if they did
     const int64_t nraw = c->nlabels_raw;
     const bool components = c->labels_components;
+    const bool raw_valid = c->raw_stats_valid;
     ctx_wrote(c, MHIP_R_LABELS);
     c->nlabels_raw = nraw;
     c->labels_components = components;
+    c->raw_stats_valid = raw_valid;
     if (keep) {
         std::vector<int32_t> lut;
         c->nlabels = build_rank_lut(keep, c->nlabels_raw, lut);
@@ -227,14 +234,22 @@ int ctx_apply_keep_on(mhip_ctx *c, const uint8_t *keep, hipStream_t s)
         MH_TRY(c->stats.alloc(sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1)));
         MH_TRY(label_stats_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->nlabels,
                                c->stats.as<mhip_stat_record>(), s, c->W, c->labels_components));   // (kept components stay components)
-    } else {
-        // keep everything (background excluded by construction): labels and stats are the raw ones
-        c->nlabels = c->nlabels_raw;
-        MH_TRY(c->stats.alloc(sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1)));
-        MH_HIP(hipMemcpyAsync(c->stats.p, c->raw_stats.p, sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1),
-                              hipMemcpyDeviceToDevice, s));
+        c->labels_filtered = true;
+        c->stats_valid = true;
+        return MHIP_OK;
     }
+    // keep everything (background excluded by construction): the labels are the raw ones, and so are the statistics while the depths
+    // are the ones the labelling read (the chain: a copy, no kernel).  Depths written since: a pass over the resident ones; none
+    // resident: the labels are final without statistics, and mhip_ctx_hyps computes them when it finds depths
+    c->nlabels = c->nlabels_raw;
     c->labels_filtered = true;
+    if (!raw_valid && !c->have[MHIP_R_DEPTHS]) return MHIP_OK;
+    MH_TRY(c->stats.alloc(sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1)));
+    if (raw_valid)
+        MH_HIP(hipMemcpyAsync(c->stats.p, c->raw_stats.p, sizeof(mhip_stat_record) * (size_t)(c->nlabels + 1), hipMemcpyDeviceToDevice, s));
+    else
+        MH_TRY(label_stats_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->nlabels, c->stats.as<mhip_stat_record>(), s,
+                               c->W, c->labels_components));
     c->stats_valid = true;
     return MHIP_OK;
 }
@@ -549,7 +564,7 @@ int mhip_ctx_get_f64(mhip_ctx *c, const char *key, double *value)
 
 int mhip_ctx_raw_stats(mhip_ctx *c, mhip_stat_record *records)
 {
-    MH_ARG(c && records && c->raw_stats.p && c->nlabels_raw >= 0, "ctx_raw_stats needs a LABEL run");
+    MH_ARG(c && records && c->raw_stats.p && c->nlabels_raw >= 0 && c->raw_stats_valid, "ctx_raw_stats needs a LABEL run on the resident depths");
     return ctx_fetch(c, c->raw_stats, sizeof(mhip_stat_record) * (size_t)(c->nlabels_raw + 1), records);
 }
 

@@ -112,6 +112,7 @@ struct mhip_ctx {
     // The three record sets describe the resident rasters they were computed from: set by the code that computes them, cleared by
     // ctx_wrote, tested by every reader.  (Atomic: both host threads of a request clear `pour_valid`, one for ACCUM, one for LABELS.)
     std::atomic<bool> stats_valid{false};       // `stats`: label_stats of DEPTHS by LABELS
+    std::atomic<bool> raw_stats_valid{false};   // `raw_stats`: label_stats of DEPTHS by the raw labels, set by the LABEL stage; a relabelling (mhip_ctx_apply_keep) keeps it
     std::atomic<bool> ws_counts_valid{false};   // `ws_counts`: label_count of WATERSHEDS
     std::atomic<bool> pour_valid{false};        // `pour`: arg-max of ACCUM (arg-min of NOFLAT) by LABELS
     // hypsometry of the resident labels (mhip_ctx_hyps): layout, table, and the records of the last mhip_ctx_final_depths

@@ -226,6 +226,7 @@ static int stage_label(mhip_ctx *c, hipStream_t s, const FillHandover *ho = null
     c->labels_components = true;
     c->labels_filtered = false;
     c->nlabels = c->nlabels_raw;
+    c->raw_stats_valid = true;      // (of the depths just read: a later write of DEPTHS clears it)
     return MHIP_OK;
 }
 

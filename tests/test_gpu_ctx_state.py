@@ -4,7 +4,8 @@ table describe the rasters they were computed from: a getter either returns the 
 whichever way the raster came in (a stage, a whole upload, a windowed upload, a band call).
 
 The DEMs are quantised to 1/64 m, so the depths are small multiples of 1/64 and every float64 sum of them is exact in any
-order: the records are compared with the oracle's bit for bit, the sums included."""
+order: the records are compared with the oracle's bit for bit, the sums included.
+Every held result of a context, under mixed sequences of calls, against a host shadow of it: tests/test_gpu_ctx_sequences.py."""
 import math
 
 import numpy as np
