@@ -616,7 +616,7 @@ int mhip_ctx_burn_lines(mhip_ctx *ctx, int64_t nseg, const mhip_burn_segment *se
  * of the context (no member of enum mhip_raster).  The zones come from outside: no write of a raster drops them, a new rasterize
  * replaces them.  zones_rows copies rows [row0, row0 + nrows) of the raster.  zone_stats: mhip_zone_stats_f32 of a resident
  * float32 raster over the zones, records[nzone + 1]; source: MHIP_R_DEM, MHIP_R_FILLED, MHIP_R_DEPTHS, MHIP_R_FINALDEPTHS,
- * MHIP_ZSRC_WETAT, MHIP_ZSRC_FLOWDIST, MHIP_ZSRC_HAND, MHIP_ZSRC_DRAINDIST, MHIP_ZSRC_INUNDATION or MHIP_ZSRC_TRAVELTIME; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
+ * MHIP_ZSRC_WETAT, MHIP_ZSRC_FLOWDIST, MHIP_ZSRC_HAND, MHIP_ZSRC_DRAINDIST, MHIP_ZSRC_INUNDATION, MHIP_ZSRC_TRAVELTIME, MHIP_ZSRC_SEALEVEL or MHIP_ZSRC_SEADEPTH; a source that is not valid is MHIP_EINVAL as from its own getter, and so is a context
  * without zones.  mhip_ctx_get_i64 "zones": nzone of the raster held, -1: none. */
 int mhip_ctx_rasterize_zones(mhip_ctx *ctx, int64_t nvert, const double *xy, int64_t nring, const int64_t *ring_offsets,
                              const int32_t *ring_zone, int64_t nzone, int32_t grow);
@@ -639,7 +639,8 @@ int mhip_ctx_zone_stats(mhip_ctx *ctx, int32_t source, mhip_zone_record *records
  * run, and holds 8 B a vertex + 12 B a ring of device memory until it is freed.  MHIP_EINVAL: a negative label; MHIP_ELIMIT: more than 2**32 - 1 edges.
  * An all-zero raster gives 0 rings and asks for no device.
  * On a context: source MHIP_R_LABELS (the filtered labels, as mhip_ctx_stats wants them) or MHIP_R_WATERSHEDS of an undivided context (a
- * row band is refused), or MHIP_PSRC_REACHCATCH (the catchment raster of the last mhip_ctx_reach_catchments, below); a source that is not valid is MHIP_EINVAL as from its own getter.  No raster leaves the device. */
+ * row band is refused), MHIP_PSRC_REACHCATCH (the catchment raster of the last mhip_ctx_reach_catchments, below) or MHIP_PSRC_SEACLASSES (the class raster of the
+ * last mhip_ctx_sea_classes, at the end of this file); a source that is not valid is MHIP_EINVAL as from its own getter.  No raster leaves the device. */
 typedef struct mhip_polygons mhip_polygons;
 int mhip_polygonize_i32(const int32_t *labels, int64_t H, int64_t W, mhip_polygons **out);
 int mhip_ctx_polygonize(mhip_ctx *ctx, int32_t source, mhip_polygons **out);
@@ -713,6 +714,47 @@ int mhip_ctx_reach_catchments(mhip_ctx *ctx, double threshold, int32_t stop_at_l
 int mhip_ctx_reach_catchments_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, int32_t *dst);
 int mhip_ctx_inundate(mhip_ctx *ctx, int64_t nreach, const float *stage, mhip_zone_record *records_or_NULL);
 int mhip_ctx_inundation_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, float *dst);
+
+/* Flooding from sources at a water level -- the sea in a surge, a lake, a breach (ours; the definition is tests/_seaflood.py,
+ * DESIGN.md 19).  dem[H][W] float32; a NaN cell, and a cell above max_level that is no source, reads as +inf (D').  stage[H][W]
+ * float32: the stage h_s of a source cell, NaN where the cell is none; a stage that is not finite is MHIP_EINVAL.  out_level is the
+ * greatest L with L[s] = h_s at the sources and L[c] = max(D'[c], min of L over the 8 neighbours inside the raster) elsewhere: the
+ * lowest level at the sources at which c is connected to one of them by water over 8-connected paths.  Raster border cells are
+ * ordinary cells.  Only min and max of input values occur: the result is the model's value for value.  A cell that no level up to
+ * max_level reaches holds nodata; reached (optional): the other cells.  max_level may be +inf; a NaN max_level or nodata is
+ * MHIP_EINVAL.  Every result is proven on the device (both equations at every cell) before it is returned; MHIP_ENOTCONV: the round
+ * cap of the relaxation.
+ * On an undivided context (a row band is refused): sea_flood on the resident MHIP_R_DEM with exactly one of the two source forms,
+ * anything else is MHIP_EINVAL: stage, a host raster of the owned rows as above, or zone_stage[nzone + 1] float32, a stage per zone of
+ * the zone raster held by mhip_ctx_rasterize_zones (entry 0 is ignored, NaN: the zone is no source; nzone must be the held count).
+ * The level raster stays in a buffer of the context (no member of enum mhip_raster), and so do the depth raster of the last
+ * sea_depths -- z - dem as one float32 subtraction where the level is no nodata and <= z and dem is no NaN, +0.0 elsewhere -- and
+ * the class raster of the last sea_classes, int32: k + 1 of the first level that wets the cell, 0 where none does.  All three go
+ * with any write of MHIP_R_DEM and with nothing else (the stages of the zones were taken at the call); a new sea_flood drops the
+ * depths and the classes.  sea_flood_rows copies rows of the level (which 0) or depth (which 1) raster, sea_classes_rows of the
+ * class raster; mhip_ctx_zone_stats takes the first two as MHIP_ZSRC_SEALEVEL and MHIP_ZSRC_SEADEPTH, mhip_ctx_polygonize the third
+ * as MHIP_PSRC_SEACLASSES.  sea_levels: K levels (1 to MHIP_SEA_MAX_LEVELS, finite, strictly increasing, none above the flood's
+ * max_level), one record a level, from one pass over the level raster and the DEM.  mhip_ctx_get_i64 "sea_flood": the cells reached,
+ * -1: none held; "sea_depths", "sea_classes": 1, -1: none; "seaflood_rounds", "seaflood_visits", "seaflood_rechecks": the launches
+ * that found work, the tile visits and the tiles the proof sent back (0 unless something is broken) of the last sea_flood. */
+#define MHIP_SEA_MAX_LEVELS 256
+/* one level of mhip_ctx_sea_levels: over the cells whose level is no nodata and <= the level -- the sum of their dem values that are
+ * no NaN, their number (wet_cells), the number of those dem values, the smallest of them (+inf without one).  wet_cells, dem_cells
+ * and dem_min are exact; dem_sum is a float64 sum in no fixed order.  numpy
+ * [('dem_sum','<f8'),('wet_cells','<i8'),('dem_cells','<i8'),('dem_min','<f4'),('pad','<i4')] */
+typedef struct { double dem_sum; int64_t wet_cells, dem_cells; float dem_min; int32_t pad; } mhip_sea_record;
+#define MHIP_ZSRC_SEALEVEL 106        /* mhip_ctx_zone_stats */
+#define MHIP_ZSRC_SEADEPTH 107        /* mhip_ctx_zone_stats */
+#define MHIP_PSRC_SEACLASSES 111      /* mhip_ctx_polygonize */
+int mhip_sea_flood_f32(const float *dem, const float *stage, int64_t H, int64_t W, float max_level, float nodata, float *out_level,
+                       int64_t *reached_or_NULL);
+int mhip_ctx_sea_flood(mhip_ctx *ctx, const float *stage_or_NULL, const float *zone_stage_or_NULL, int64_t nzone, float max_level, float nodata,
+                       int64_t *reached);
+int mhip_ctx_sea_flood_rows(mhip_ctx *ctx, int32_t which, int64_t row0, int64_t nrows, float *dst);
+int mhip_ctx_sea_levels(mhip_ctx *ctx, int32_t K, const float *levels, mhip_sea_record *records);
+int mhip_ctx_sea_depths(mhip_ctx *ctx, float z);
+int mhip_ctx_sea_classes(mhip_ctx *ctx, int32_t K, const float *levels);
+int mhip_ctx_sea_classes_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, int32_t *dst);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,12 @@ ZONE_DTYPE = np.dtype([("vmax", "<f8"), ("vmin_pos", "<f8"), ("cells", "<i8"), (
 ZSRC_WETAT, ZSRC_FLOWDIST, ZSRC_HAND, ZSRC_DRAINDIST, ZSRC_INUNDATION, ZSRC_TRAVELTIME = 100, 101, 102, 103, 104, 105
 PSRC_REACHCATCH = 110      # a source of mhip_ctx_polygonize that is no member of mhip_raster
 
+# flooding from sources at a water level (coastal.py): mhip_sea_record, the most levels of one call, the sources of
+# mhip_ctx_zone_stats and mhip_ctx_polygonize that the sea flood adds
+SEA_DTYPE = np.dtype([("dem_sum", "<f8"), ("wet_cells", "<i8"), ("dem_cells", "<i8"), ("dem_min", "<f4"), ("pad", "<i4")])
+SEA_MAX_LEVELS = 256
+ZSRC_SEALEVEL, ZSRC_SEADEPTH, PSRC_SEACLASSES = 106, 107, 111
+
 # flow paths (flowpaths.py): mhip_reach_record; the end kinds of a reach
 REACH_DTYPE = np.dtype([("first_cell", "<i8"), ("last_cell", "<i8"), ("end_cell", "<i8"), ("up_cells", "<f8"), ("down_cells", "<f8"),
                         ("n_orth", "<i4"), ("n_diag", "<i4"), ("end_kind", "<i4"), ("to_reach", "<i4"), ("to_label", "<i4"),
@@ -81,6 +87,8 @@ SYMBOLS = [
     "mhip_hand_f32", "mhip_ctx_hand", "mhip_ctx_hand_rows",
     "mhip_reach_catchments_i32", "mhip_inundate_f32", "mhip_ctx_reach_catchments", "mhip_ctx_reach_catchments_rows", "mhip_ctx_inundate",
     "mhip_ctx_inundation_rows",
+    "mhip_sea_flood_f32", "mhip_ctx_sea_flood", "mhip_ctx_sea_flood_rows", "mhip_ctx_sea_levels", "mhip_ctx_sea_depths", "mhip_ctx_sea_classes",
+    "mhip_ctx_sea_classes_rows",
     "mhip_burn_lines_f32", "mhip_ctx_burn_lines",
     "mhip_rasterize_zones_i32", "mhip_zone_stats_f32", "mhip_ctx_rasterize_zones", "mhip_ctx_zones_rows", "mhip_ctx_zone_stats",
     "mhip_polygonize_i32", "mhip_ctx_polygonize", "mhip_polygons_sizes", "mhip_polygons_fetch", "mhip_polygons_free",

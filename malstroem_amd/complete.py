@@ -90,7 +90,7 @@ def parse_filter(filter):
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
                 finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
                 flowpaths=None, flowpaths_stop_at_bluespots=True, hand=None, reach_catchments=False, inundation=None,
-                traveltime=False, adaptations=None):
+                traveltime=False, sea=None, adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -161,7 +161,43 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     ``reach_catchments=True``, ``hand == flowpaths`` and ``flowpaths_stop_at_bluespots=True``, so that the heights and the catchments
     speak of the same drainage cells.  Writes ``inundation_<cm>.tif`` per level (the level in whole centimetres): the depth
     ``level - hand`` in the cells that lie lower above their reach than the level, 0 elsewhere.  The dict gains ``inundation``, a dict
-    of the paths by centimetres.  Not on row bands yet."""
+    of the paths by centimetres.  Not on row bands yet.
+
+    ``sea`` (keyword only): a dict ``{"sources": ..., "levels": [...], "depths": [...]}`` -- flooding from a body of water at a level
+    (``coastal.SeaFloodTool``).  ``sources``: a float32 stage raster of the DEM's shape (``coastal.sources_from_mask``:
+    the level at a source cell, NaN elsewhere) or ``("nodata", level)``: the cells the DEM file marks as nodata at that level.
+    ``levels``: the sea levels in metres, strictly increasing; ``depths`` (optional): those of them that also get a depth raster.  It
+    runs on the DEM the chain ran on, after the ``adaptations`` are burnt, so a raised dike counts.  Writes ``sea_level.tif`` -- per
+    cell the lowest level at the sources at which water reaches it, nodata -9999 where none up to the highest level does --
+    ``sea_depth_<cm>.tif`` per depth level (the level in whole centimetres) and the vector layers ``sea_levels`` (one feature per
+    level: wet cells, area, volume, deepest) and ``sea_extents`` (the outlines of the flood extents with ``first_level``).  With
+    ``objects`` every object gets ``sea_level_min``, the lowest level that wets one of its cells (null: none does;
+    ``coastal.object_level_min`` says why it is ``vmin_pos``), which needs every stage > 0.  The dict gains ``sea_level``,
+    ``sea_depths``, ``sea_levels`` and ``sea_extents``.  Every other output is what it is without the argument.  Not on row bands
+    yet."""
+    sea_depth_levels = []
+    if sea is not None:
+        from .algorithms.fill import check_sea_levels
+        if not isinstance(sea, dict) or set(sea) - {"sources", "levels", "depths"} or "sources" not in sea or "levels" not in sea:
+            raise ValueError('sea must be a dict {"sources": ..., "levels": [...], "depths": [...]}, got %r' % (sea,))
+        sea_levels = check_sea_levels(sea["levels"])
+        for v in (sea.get("depths") or []):
+            z = check_sea_levels([v], sea_levels[-1])[0]
+            if z not in sea_levels:
+                raise ValueError("sea: the depth level %r is none of the levels" % (v,))
+            sea_depth_levels.append((int(round(float(z) * 100.0)), z))
+        if len({cm for cm, _ in sea_depth_levels}) != len(sea_depth_levels):
+            raise ValueError("sea: the depth levels must differ by whole centimetres, got %r" % (sea.get("depths"),))
+        src = sea["sources"]
+        if isinstance(src, tuple):
+            from .coastal import check_level
+            if len(src) != 2 or src[0] != "nodata":
+                raise ValueError('sea: sources must be a float32 stage raster or ("nodata", level), got %r' % (src,))
+            check_level(src[1])
+        if objects is not None:
+            st = np.asarray(src[1] if isinstance(src, tuple) else src, dtype=np.float64)
+            if (st[~np.isnan(st)] <= 0).any():
+                raise ValueError("sea with objects: sea_level_min needs every stage > 0 (zone_stats takes the lowest level over the values > 0)")
     if reach_catchments and flowpaths is None:
         raise ValueError("reach_catchments needs flowpaths: the threshold of the reaches whose catchments are wanted")
     stages = []
@@ -209,6 +245,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         if adaptations is not None:
             raise NotImplementedError("adaptations on row bands: a line crosses the seams between the bands, and its levels hang on "
                                       "both of its ends, which is not built yet; run it on one context")
+        if sea is not None:
+            raise NotImplementedError("sea on row bands: the water crosses the seams between the bands, and the wake-ups of the "
+                                      "relaxation over them are not built yet; run it on one context")
         if reach_catchments or inundation is not None:
             raise NotImplementedError("reach_catchments and inundation on row bands: a flow path crosses the seams between the bands, "
                                       "and the walk over them is not built yet; run it on one context")
@@ -310,6 +349,22 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                 for k, f in enumerate(object_features):
                     f["properties"].update(hand_min=float(zh["vmin_pos"][k + 1]) if zh["pos"][k + 1] else None,
                                            hand_dist_min=float(zd["vmin_pos"][k + 1]) if zd["pos"][k + 1] else None)
+        sea_res = {}
+        if sea is not None:
+            # Sea flood: on the resident DEM, adaptations burnt; the objects' zones are still resident
+            from .coastal import SeaFloodTool, sources_from_nodata
+            src = sea["sources"]
+            if isinstance(src, tuple):
+                src = sources_from_nodata(pipe.download("dem"), nodatasubst if nodatasubst is not None else np.nan, src[1])
+            sea_level_path = os.path.join(outdir, 'sea_level.tif')
+            sea_depth_paths = {cm: os.path.join(outdir, 'sea_depth_{}.tif'.format(cm)) for cm, _ in sea_depth_levels}
+            sea_levels_writer = io.VectorWriter('GeoJSON', outvector, 'sea_levels', None, None, crs)
+            sea_extents_writer = io.VectorWriter('GeoJSON', outvector, 'sea_extents', None, None, crs)
+            SeaFloodTool(dem_reader, src, sea_levels, output_level=io.RasterWriter(sea_level_path, tr, crs, -9999.0),
+                         output_depths={z: io.RasterWriter(sea_depth_paths[cm], tr, crs) for cm, z in sea_depth_levels},
+                         output_levels=sea_levels_writer, output_extents=sea_extents_writer, objects=object_features, pipeline=pipe).process()
+            sea_res = dict(sea_level=sea_level_path, sea_depths=sea_depth_paths, sea_levels=sea_levels_writer.filepath,
+                           sea_extents=sea_extents_writer.filepath)
         if not finalstate:
             pipe.close()
         # Process rain events
@@ -336,6 +391,7 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
             res["inundation"] = inundation_paths
         if adaptations is not None:
             res.update(dem_adapted=adapted_path, adaptations=report_writer.filepath)
+        res.update(sea_res)
         if finalstate:
             # Final state of every event: the depths and the filtered labels are still on the device
             from .finalstate import FinalStateTool

@@ -469,6 +469,21 @@ int mhip_hand_f32(const uint8_t *flowdir, const double *accum, const float *elev
     return download(out_hand, d_h, n * 4, s);
 }
 
+int mhip_sea_flood_f32(const float *dem, const float *stage, int64_t H, int64_t W, float max_level, float nodata, float *out_level, int64_t *reached)
+{
+    MH_ARG(dem && stage && out_level && H >= 1 && W >= 1, "sea_flood_f32(dem, stage, H>=1, W>=1, max_level, nodata, out_level, reached)");
+    MH_TRY(sea_flood_check(max_level, nodata));
+    MH_TRY(require_device());
+    hipStream_t s = 0;
+    const size_t n = (size_t)(H * W);
+    DevBuf d_dem, d_stage, d_out;
+    MH_TRY(upload(d_dem, dem, n * 4, s));
+    MH_TRY(upload(d_stage, stage, n * 4, s));
+    MH_TRY(d_out.alloc(n * 4));
+    MH_TRY(sea_flood_dev(d_dem.as<float>(), d_stage.as<float>(), nullptr, nullptr, 0, H, W, max_level, nodata, d_out.as<float>(), reached, nullptr, s));
+    return download(out_level, d_out, n * 4, s);
+}
+
 int mhip_burn_lines_f32(float *dem, int64_t H, int64_t W, int64_t nseg, const mhip_burn_segment *segments, int64_t nline,
                         const mhip_burn_line *lines, double nodata, mhip_burn_result *results)
 {

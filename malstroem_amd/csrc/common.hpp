@@ -566,6 +566,23 @@ int reach_catchments_dev(const uint8_t *d_fd, const double *d_acc, const int32_t
 // zone_stats_dev.  Synchronises.  MHIP_EINVAL: a catchment id outside [0, nreach].
 int inundate_dev(const float *d_hand, const int32_t *d_catch, int64_t n, int64_t W, int64_t nreach, const float *d_stage, float nodata, float *d_depth,
                  mhip_zone_record *d_rec, hipStream_t s);
+// seaflood.hip (tests/_seaflood.py): the lowest water level at the sources at which a cell is connected to them by water,
+// into d_out -- `nodata` where no level below max_level does it; *reached: the other cells.  The sources are d_stage (float32 raster,
+// NaN: no source) or, with d_stage == nullptr, the cells of the zones of d_zones whose entry of d_zone_stage (nzone + 1 float32 on the
+// device, entry 0 a NaN) is no NaN.  Every result is proven by a pass over both equations before it is returned.  Synchronises.
+// MHIP_EINVAL: a source stage that is not finite; MHIP_ENOTCONV: the round cap.  sea_flood_check / sea_levels_check: the argument
+// rules (MHIP_EINVAL; no device work).
+struct SeaStats {
+    int64_t rounds = 0, visits = 0, rechecks = 0;      // launches that found work, tile visits, tiles the proof sent back
+};
+int sea_flood_check(float max_level, float nodata);
+int sea_levels_check(int64_t K, const float *levels, float max_level);
+int sea_flood_dev(const float *d_dem, const float *d_stage, const int32_t *d_zones, const float *d_zone_stage, int64_t nzone, int64_t H, int64_t W,
+                  float max_level, float nodata, float *d_out, int64_t *reached, SeaStats *st, hipStream_t s);
+// ... and what follows from that raster for K checked levels (host array): the records (host), the depths of one level, the classes
+int sea_levels_dev(const float *d_level, const float *d_dem, int64_t n, float nodata, int K, const float *levels, mhip_sea_record *records, hipStream_t s);
+int sea_depths_dev(const float *d_level, const float *d_dem, int64_t n, float nodata, float z, float *d_out, hipStream_t s);
+int sea_classes_dev(const float *d_level, int64_t n, float nodata, int K, const float *levels, int32_t *d_out, hipStream_t s);
 // burn.hip: DEM adaptations.  burn_check: the argument rules of mhip_burn_lines_f32 on the host arrays (MHIP_EINVAL; no
 // device work).  burn_lines_dev: the checked lines into the float32 raster d_dem in place, the per-line records to `results` (host).
 // Synchronises.  nseg == 0 writes the records on the host and touches no device.

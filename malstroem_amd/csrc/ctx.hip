@@ -1,6 +1,7 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
 // getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, the flow paths, the reach catchments and their flood depths, and the one
 // rule for what a write of a resident raster invalidates (ctx_wrote) and the one test for a raster held outside mhip_raster (ctx_held).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
+#include <limits>
 #include <mutex>
 #include <new>
 #include <string>
@@ -74,6 +75,28 @@ static void drop_hand(mhip_ctx *c, int which)
     drop_inundation(c);
 }
 
+// the depths and the classes of the sea flood go with the level raster they were made from, and with a new call of their own
+static void drop_sea_depths(mhip_ctx *c)
+{
+    c->sea_depth_held = -1;      // (the call that fills the buffer has synchronised: nothing on the device still uses it)
+    c->sea_depth.release();
+}
+
+static void drop_sea_classes(mhip_ctx *c)
+{
+    c->sea_class_held = -1;
+    c->sea_class.release();
+}
+
+// the DEM was written, or a new mhip_ctx_sea_flood begins: the level raster of the last one goes, and what was made from it
+static void drop_sea_flood(mhip_ctx *c)
+{
+    c->sea_reached = -1;
+    c->sea_level.release();
+    drop_sea_depths(c);
+    drop_sea_classes(c);
+}
+
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
 {
     drop_hand(c, which);
@@ -82,6 +105,7 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
     switch (which) {
     case MHIP_R_DEM:    // a new DEM invalidates everything derived from the previous one
         c->noflat_pending = false;      // (a surface nobody has asked for goes with have[NOFLAT])
+        drop_sea_flood(c);
         for (int k = 0; k < MHIP_R_COUNT_; ++k) {
             if (k == MHIP_R_DEM) continue;
             c->have[k] = false;
@@ -149,6 +173,9 @@ int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes)
         {c->inund_held > 0, c->inund_out, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments"},
         {c->nzone >= 0, c->zones, "ctx_zones_rows needs mhip_ctx_rasterize_zones"},
         {c->tt_unresolved >= 0, c->tt_out, "ctx_travel_time_rows needs mhip_ctx_travel_time on the resident rasters"},
+        {c->sea_reached >= 0, c->sea_level, "ctx_sea_flood_rows needs mhip_ctx_sea_flood on the resident DEM"},
+        {c->sea_depth_held > 0, c->sea_depth, "ctx_sea_flood_rows needs mhip_ctx_sea_depths on the held sea levels"},
+        {c->sea_class_held > 0, c->sea_class, "ctx_sea_classes_rows needs mhip_ctx_sea_classes on the held sea levels"},
     };
     MH_ARG(t[id].held && t[id].buf.p, t[id].needs);
     *ptr = t[id].buf.p;
@@ -538,6 +565,12 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "reach_catchments") *value = c->rcatch_nreach;     // -1: no result of mhip_ctx_reach_catchments on the resident rasters
     else if (k == "inundation") *value = c->inund_held;              // 1: a depth raster of mhip_ctx_inundate is held, -1: none
     else if (k == "zones") *value = c->nzone;                       // -1: no zone raster of mhip_ctx_rasterize_zones
+    else if (k == "sea_flood") *value = c->sea_reached;              // the cells the last mhip_ctx_sea_flood reached, -1: no level raster is held
+    else if (k == "sea_depths") *value = c->sea_depth_held;          // 1: a depth raster of mhip_ctx_sea_depths is held, -1: none
+    else if (k == "sea_classes") *value = c->sea_class_held;         // 1: a class raster of mhip_ctx_sea_classes is held, -1: none
+    else if (k == "seaflood_rounds") *value = c->sea_st.rounds;      // of the last mhip_ctx_sea_flood: launches that found work,
+    else if (k == "seaflood_visits") *value = c->sea_st.visits;      // ... tile visits,
+    else if (k == "seaflood_rechecks") *value = c->sea_st.rechecks;  // ... tiles its proof sent back (0 unless something is broken)
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
     else {
@@ -876,7 +909,8 @@ int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
     MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
     const bool member = source == MHIP_R_DEM || source == MHIP_R_FILLED || source == MHIP_R_DEPTHS || source == MHIP_R_FINALDEPTHS;
     const int id = source == MHIP_ZSRC_WETAT ? HELD_WETAT : source == MHIP_ZSRC_FLOWDIST ? HELD_FLOWDIST : source == MHIP_ZSRC_HAND ? HELD_HAND :
-                   source == MHIP_ZSRC_DRAINDIST ? HELD_DRAINDIST : source == MHIP_ZSRC_INUNDATION ? HELD_INUNDATION : source == MHIP_ZSRC_TRAVELTIME ? HELD_TRAVELTIME : -1;
+                   source == MHIP_ZSRC_DRAINDIST ? HELD_DRAINDIST : source == MHIP_ZSRC_INUNDATION ? HELD_INUNDATION : source == MHIP_ZSRC_TRAVELTIME ? HELD_TRAVELTIME :
+                   source == MHIP_ZSRC_SEALEVEL ? HELD_SEALEVEL : source == MHIP_ZSRC_SEADEPTH ? HELD_SEADEPTH : -1;
     MH_ARG(member || id >= 0, "ctx_zone_stats: the source is no float32 raster of the context");
     void *src = member ? c->r[source].p : nullptr;
     if (member) MH_ARG(c->have[source], "raster has not been computed or uploaded");
@@ -893,11 +927,12 @@ int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
 int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
 {
     MH_ARG(c && out, "ctx_polygonize(ctx, source, out)");
-    MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS || source == MHIP_PSRC_REACHCATCH,
-           "ctx_polygonize: the source is MHIP_R_LABELS or MHIP_R_WATERSHEDS, or MHIP_PSRC_REACHCATCH for the reach catchments");
+    MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS || source == MHIP_PSRC_REACHCATCH || source == MHIP_PSRC_SEACLASSES,
+           "ctx_polygonize: the source is MHIP_R_LABELS or MHIP_R_WATERSHEDS, MHIP_PSRC_REACHCATCH for the reach catchments or MHIP_PSRC_SEACLASSES for the sea flood's classes");
     MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "outlines on a row band are not built (a ring crosses the seams: a later step); use an undivided context");
     void *held = nullptr;
     if (source == MHIP_PSRC_REACHCATCH) MH_TRY(ctx_held(c, HELD_REACHCATCH, &held));
+    else if (source == MHIP_PSRC_SEACLASSES) MH_TRY(ctx_held(c, HELD_SEACLASS, &held));
     else MH_ARG(c->have[source], "raster has not been computed or uploaded");
     if (source == MHIP_R_LABELS) MH_ARG(c->labels_filtered && !c->ccl_pending, "ctx_polygonize needs mhip_ctx_apply_keep after the LABEL run");
     MH_TRY(polygonize_check(c->H, c->W));
@@ -1021,6 +1056,96 @@ int mhip_ctx_inundate(mhip_ctx *c, int64_t nreach, const float *stage, mhip_zone
 int mhip_ctx_inundation_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *dst)
 {
     return held_rows(c, HELD_INUNDATION, row0, nrows, dst, "ctx_inundation_rows(ctx, row0, nrows, dst)");
+}
+
+/* ---- flooding from sources at a water level, and what follows from the level raster (seaflood.hip) --------------------------------- */
+int mhip_ctx_sea_flood(mhip_ctx *c, const float *stage, const float *zone_stage, int64_t nzone, float max_level, float nodata, int64_t *reached)
+{
+    MH_ARG(c && reached, "ctx_sea_flood(ctx, stage_or_NULL, zone_stage_or_NULL, nzone, max_level, nodata, reached)");
+    MH_ARG((stage != nullptr) != (zone_stage != nullptr), "ctx_sea_flood takes exactly one source form: a stage raster, or a stage per zone");
+    MH_TRY(sea_flood_check(max_level, nodata));
+    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "sea flooding on a row band is not built (the water crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_DEM], "ctx_sea_flood needs the DEM raster");
+    void *zones = nullptr;
+    if (zone_stage) {
+        MH_ARG(ctx_held(c, HELD_ZONES, &zones) == MHIP_OK, "ctx_sea_flood with a stage per zone needs mhip_ctx_rasterize_zones");
+        MH_ARG(nzone == c->nzone, "ctx_sea_flood: nzone is not the number of zones of the zone raster held");
+    }
+    MH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t n = c->H * c->W;
+    drop_sea_flood(c);
+    DevBuf d_stage;
+    if (stage) {
+        MH_TRY(upload(d_stage, stage, 4 * (size_t)n, s));
+    } else {      // (entry 0 is no zone: a NaN, whatever the caller left there)
+        std::vector<float> zs(zone_stage, zone_stage + nzone + 1);
+        zs[0] = std::numeric_limits<float>::quiet_NaN();
+        MH_TRY(upload(d_stage, zs.data(), 4 * zs.size(), s));
+        MH_HIP(stream_sync(s));      // (zs goes away)
+    }
+    MH_TRY(c->sea_level.alloc(4 * (size_t)n));
+    int64_t r = 0;
+    const int rc = sea_flood_dev(c->r[MHIP_R_DEM].as<float>(), stage ? d_stage.as<float>() : nullptr, (const int32_t *)zones, stage ? nullptr : d_stage.as<float>(),
+                                 stage ? 0 : nzone, c->H, c->W, max_level, nodata, c->sea_level.as<float>(), &r, &c->sea_st, s);      // (synchronises)
+    if (rc != MHIP_OK) {
+        MH_HIP(stream_sync(s));      // (an error may have left launches behind: the buffers go back to the pool)
+        c->sea_level.release();
+        return rc;
+    }
+    c->sea_max_level = max_level;
+    c->sea_nodata = nodata;
+    c->sea_reached = r;
+    *reached = r;
+    return MHIP_OK;
+}
+
+int mhip_ctx_sea_flood_rows(mhip_ctx *c, int32_t which, int64_t row0, int64_t nrows, float *dst)
+{
+    return held_rows(c, which == 0 ? HELD_SEALEVEL : which == 1 ? HELD_SEADEPTH : -1, row0, nrows, dst, "ctx_sea_flood_rows(ctx, which, row0, nrows, dst)");
+}
+
+int mhip_ctx_sea_levels(mhip_ctx *c, int32_t K, const float *levels, mhip_sea_record *records)
+{
+    MH_ARG(c && levels && records, "ctx_sea_levels(ctx, K, levels, records)");
+    void *lev = nullptr;
+    MH_ARG(ctx_held(c, HELD_SEALEVEL, &lev) == MHIP_OK, "ctx_sea_levels needs mhip_ctx_sea_flood on the resident DEM");
+    MH_TRY(sea_levels_check(K, levels, c->sea_max_level));
+    MH_HIP(hipSetDevice(c->device));
+    return sea_levels_dev((const float *)lev, c->r[MHIP_R_DEM].as<float>(), c->H * c->W, c->sea_nodata, K, levels, records, c->stream);
+}
+
+int mhip_ctx_sea_depths(mhip_ctx *c, float z)
+{
+    MH_ARG(c, "ctx_sea_depths(ctx, z)");
+    void *lev = nullptr;
+    MH_ARG(ctx_held(c, HELD_SEALEVEL, &lev) == MHIP_OK, "ctx_sea_depths needs mhip_ctx_sea_flood on the resident DEM");
+    MH_TRY(sea_levels_check(1, &z, c->sea_max_level));
+    MH_HIP(hipSetDevice(c->device));
+    drop_sea_depths(c);
+    MH_TRY(c->sea_depth.alloc(4 * (size_t)(c->H * c->W)));
+    MH_TRY(sea_depths_dev((const float *)lev, c->r[MHIP_R_DEM].as<float>(), c->H * c->W, c->sea_nodata, z, c->sea_depth.as<float>(), c->stream));
+    c->sea_depth_held = 1;
+    return MHIP_OK;
+}
+
+int mhip_ctx_sea_classes(mhip_ctx *c, int32_t K, const float *levels)
+{
+    MH_ARG(c && levels, "ctx_sea_classes(ctx, K, levels)");
+    void *lev = nullptr;
+    MH_ARG(ctx_held(c, HELD_SEALEVEL, &lev) == MHIP_OK, "ctx_sea_classes needs mhip_ctx_sea_flood on the resident DEM");
+    MH_TRY(sea_levels_check(K, levels, c->sea_max_level));
+    MH_HIP(hipSetDevice(c->device));
+    drop_sea_classes(c);
+    MH_TRY(c->sea_class.alloc(4 * (size_t)(c->H * c->W)));
+    MH_TRY(sea_classes_dev((const float *)lev, c->H * c->W, c->sea_nodata, K, levels, c->sea_class.as<int32_t>(), c->stream));
+    c->sea_class_held = 1;
+    return MHIP_OK;
+}
+
+int mhip_ctx_sea_classes_rows(mhip_ctx *c, int64_t row0, int64_t nrows, int32_t *dst)
+{
+    return held_rows(c, HELD_SEACLASS, row0, nrows, dst, "ctx_sea_classes_rows(ctx, row0, nrows, dst)");
 }
 
 }  // extern "C"

@@ -159,6 +159,14 @@ struct mhip_ctx {
     // none.  It comes from outside: no write of a raster drops it
     mh::DevBuf zones;
     int64_t nzone = -1;
+    // the level raster (float32, H x W; no member of mhip_raster) of the last mhip_ctx_sea_flood, the cells it reached (-1: none), and
+    // the max_level, the nodata and the counters of that call; the depth raster (float32) of the last mhip_ctx_sea_depths and the
+    // class raster (int32) of the last mhip_ctx_sea_classes.  All three live and die with the DEM; a new sea_flood drops the other two
+    mh::DevBuf sea_level, sea_depth, sea_class;
+    int64_t sea_reached = -1;
+    int sea_depth_held = -1, sea_class_held = -1;
+    float sea_max_level = 0, sea_nodata = 0;
+    mh::SeaStats sea_st;
     double sh = 0, dg = 0;
     int32_t fill_rounds = 0, noflat_rounds = 0;
     int64_t fill_handover_rechecks = 0;   // requests of this context whose fused visit failed the proof and went through the flood's own last pass
@@ -264,10 +272,12 @@ inline int ctx_settle(mhip_ctx *c, int which, bool write)
 // checked the window against H_owned.  Every whole-raster and windowed transfer of ctx.hip is this call.
 int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, int64_t nrows, void *host, hipMemcpyKind kind);
 // ---- the rasters a context holds outside mhip_raster, wherever they are read (ctx.hip) ------------------------------------------
-// wet_at, flow distance, hand and the distance to the drainage, reach catchments, inundation depths, zones, travel time: each lives behind a
+// wet_at, flow distance, hand and the distance to the drainage, reach catchments, inundation depths, zones, travel time, the sea flood's
+// levels, depths and classes: each lives behind a
 // sentinel of its own, which the drop_* functions of ctx.hip clear.  ctx_held is the one test "is it held, and where": MHIP_EINVAL
 // with the message of that raster's mhip_ctx_*_rows getter, or the device pointer and (optional) the bytes of an element.
-enum HeldRaster { HELD_WETAT, HELD_FLOWDIST, HELD_HAND, HELD_DRAINDIST, HELD_REACHCATCH, HELD_INUNDATION, HELD_ZONES, HELD_TRAVELTIME, HELD_COUNT_ };
+enum HeldRaster { HELD_WETAT, HELD_FLOWDIST, HELD_HAND, HELD_DRAINDIST, HELD_REACHCATCH, HELD_INUNDATION, HELD_ZONES, HELD_TRAVELTIME, HELD_SEALEVEL, HELD_SEADEPTH,
+                  HELD_SEACLASS, HELD_COUNT_ };
 int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes = nullptr);
 // `bytes` of a record buffer to `host` on the main stream, synchronised: every record getter after its validity test
 int ctx_fetch(mhip_ctx *c, const DevBuf &buf, size_t bytes, void *host);

@@ -338,7 +338,8 @@ class HydroPipeline(CtxHandle):
     # ---- object exposure: polygons to a zone raster, a resident raster reduced per zone (objects.py) -----
     ZONE_SOURCES = {"dem": _lib.R_DEM, "filled": _lib.R_FILLED, "depths": _lib.R_DEPTHS, "finaldepths": _lib.R_FINALDEPTHS,
                     "wet_at": _lib.ZSRC_WETAT, "flow_distance": _lib.ZSRC_FLOWDIST, "hand": _lib.ZSRC_HAND,
-                    "drain_distance": _lib.ZSRC_DRAINDIST, "inundation": _lib.ZSRC_INUNDATION, "travel_time": _lib.ZSRC_TRAVELTIME}
+                    "drain_distance": _lib.ZSRC_DRAINDIST, "inundation": _lib.ZSRC_INUNDATION, "travel_time": _lib.ZSRC_TRAVELTIME,
+                    "sea_level": _lib.ZSRC_SEALEVEL, "sea_depths": _lib.ZSRC_SEADEPTH}
 
     def rasterize_zones(self, xy, ring_offsets, ring_zone, nzone, grow=0):
         """Rasterize polygons (``objects.rings_from_features``) at the pipeline's shape; the zone raster stays on the device for
@@ -351,10 +352,12 @@ class HydroPipeline(CtxHandle):
 
     def zone_stats(self, source):
         """``nzone + 1`` records (``_lib.ZONE_DTYPE``) of a resident float32 raster over the zones: ``source`` is ``"dem"``,
-        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"``, ``"flow_distance"``, ``"hand"``, ``"drain_distance"``, ``"inundation"`` or ``"travel_time"``.  ``ValueError`` without zones or when the
+        ``"filled"``, ``"depths"``, ``"finaldepths"``, ``"wet_at"``, ``"flow_distance"``, ``"hand"``, ``"drain_distance"``, ``"inundation"``, ``"travel_time"``, ``"sea_level"`` or ``"sea_depths"``.  ``ValueError`` without zones or when the
         source has not been computed.  (``"hand"``: ``vmin_pos`` is the lowest positive height above drainage of an object's cells.
         The negative nodata of its undrained cells is never the largest value of a zone that has one drained cell, and is never
-        positive: it shows in ``vmax`` only where no cell of the zone is drained.)"""
+        positive: it shows in ``vmax`` only where no cell of the zone is drained.  ``"sea_level"``: ``vmin_pos`` is the lowest level
+        that wets a cell of an object where every stage is > 0 -- no level is below the lowest stage, and the negative nodata of
+        the cells no level reaches is never positive; ``vmax`` is the level at which the last of its reached cells is wet.)"""
         if source not in self.ZONE_SOURCES:
             raise ValueError("source must be one of %s, got %r" % (sorted(self.ZONE_SOURCES), source))
         nzone = self.get_int("zones")
@@ -376,11 +379,13 @@ class HydroPipeline(CtxHandle):
         write_windows(writer, self.shape, np.int32, self.download_zones_rows, max_rows)
 
     # ---- outlines of the resident labels / watersheds (vector.py) ----------------------------------------
-    POLYGON_SOURCES = {"labels": _lib.R_LABELS, "watersheds": _lib.R_WATERSHEDS, "reach_catchments": _lib.PSRC_REACHCATCH}
+    POLYGON_SOURCES = {"labels": _lib.R_LABELS, "watersheds": _lib.R_WATERSHEDS, "reach_catchments": _lib.PSRC_REACHCATCH,
+                       "sea_classes": _lib.PSRC_SEACLASSES}
 
     def polygonize(self, source="labels"):
         """``(xy, ring_offsets, ring_label)`` of the resident (filtered) labels, of the watersheds or of the catchments of the last
-        ``reach_catchments`` (``ring_label``: ``reach_id + 1``), as ``vector.polygonize`` gives them for the downloaded raster; no raster leaves the device.  The arrays are a snapshot: a later run does not change them."""
+        ``reach_catchments`` (``ring_label``: ``reach_id + 1``) or of the classes of the last ``sea_classes`` (``ring_label``: ``k + 1`` of
+        the first level that wets the region), as ``vector.polygonize`` gives them for the downloaded raster; no raster leaves the device.  The arrays are a snapshot: a later run does not change them."""
         from .vector import take_polygons
         if source not in self.POLYGON_SOURCES:
             raise ValueError("source must be one of %s, got %r" % (sorted(self.POLYGON_SOURCES), source))
@@ -449,3 +454,106 @@ class HydroPipeline(CtxHandle):
     def download_inundation_to(self, writer, max_rows=4096):
         """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
         write_windows(writer, self.shape, np.float32, self.download_inundation_rows, max_rows)
+
+    # ---- flooding from sources at a water level: the sea, a lake, a breach (coastal.py; DESIGN.md 19) ---------------------
+    def sea_flood(self, sources, max_level=np.inf, nodata=-9999.0):
+        """The lowest water level at the sources at which every cell of the resident DEM is connected to them by water
+        (``algorithms.fill.flood_from_sources``; the definition is ``tests/_seaflood.py``).  ``sources``: a float32 raster -- the stage
+        at a source cell, NaN elsewhere -- or ``("zones", stages)``, one stage per zone of the resident zone raster behind an ignored
+        entry 0, NaN where the zone is no source (as ``inundate`` takes its stage per reach): no raster crosses the bus.  Returns the
+        number of cells reached.  The level raster stays on the device for ``download_sea_level`` (and its ``_rows`` / ``_to`` forms),
+        ``sea_levels``, ``sea_depths``, ``sea_classes`` and ``zone_stats("sea_level")`` until the DEM is written again -- an upload,
+        a windowed upload or ``burn_lines``; nothing else drops it, later ``rasterize_zones`` included."""
+        from .algorithms.fill import check_sea_args, check_sea_stage
+        ml, nd = check_sea_args(max_level, nodata)
+        reached = ctypes.c_int64(0)
+        if isinstance(sources, tuple):
+            if len(sources) != 2 or sources[0] != "zones":
+                raise ValueError('sources must be a float32 stage raster or ("zones", stages), got %r' % (sources[:1],))
+            nzone = self.get_int("zones")
+            if nzone < 0:
+                raise ValueError("rasterize_zones() has not been run")
+            with np.errstate(over="ignore"):
+                zs = np.ascontiguousarray(np.asarray(sources[1], dtype=np.float64).astype(np.float32))
+            if zs.shape != (nzone + 1,):
+                raise ValueError("stages must have nzone + 1 = %d entries (entry 0 is ignored)" % (nzone + 1))
+            if np.isinf(zs[1:]).any():
+                raise ValueError("the stage of a source must be finite (NaN: the zone is no source)")
+            _lib.call("mhip_ctx_sea_flood", self._ctx, None, _lib.ptr(zs), _lib.i64(nzone), ctypes.c_float(ml), ctypes.c_float(nd), ctypes.byref(reached))
+        else:
+            st = check_sea_stage(sources, self.shape)
+            _lib.call("mhip_ctx_sea_flood", self._ctx, _lib.ptr(st), None, _lib.i64(0), ctypes.c_float(ml), ctypes.c_float(nd), ctypes.byref(reached))
+        self._sea_max_level = ml
+        return reached.value
+
+    def _sea_held(self):
+        if self.get_int("sea_flood") < 0:
+            raise ValueError("sea_flood() has not been run on the resident DEM")
+
+    def sea_levels(self, levels):
+        """One record per level (finite, strictly increasing, none above the flood's ``max_level``) from ONE pass over the held level
+        raster and the DEM: ``level``, ``wet_cells`` (cells the level wets), ``dem_cells`` / ``dem_sum`` / ``dem_min`` (number, sum
+        and smallest of their DEM values that are no NaN) and ``dmax``, the deepest depth ``float32(level) - dem_min`` (0 without a
+        cell).  The volume under a level is ``cellarea * (level * dem_cells - dem_sum)``."""
+        from .algorithms.fill import check_sea_levels
+        self._sea_held()
+        lev = check_sea_levels(levels, self._sea_max_level)
+        rec = np.zeros(lev.size, dtype=_lib.SEA_DTYPE)
+        _lib.call("mhip_ctx_sea_levels", self._ctx, ctypes.c_int32(lev.size), _lib.ptr(lev), _lib.ptr(rec))
+        out = np.zeros(lev.size, dtype=[("level", "<f4"), ("wet_cells", "<i8"), ("dem_min", "<f4"), ("dem_sum", "<f8"), ("dem_cells", "<i8"),
+                                        ("dmax", "<f4")])
+        out["level"] = lev
+        for f in ("wet_cells", "dem_min", "dem_sum", "dem_cells"):
+            out[f] = rec[f]
+        with np.errstate(invalid="ignore"):
+            out["dmax"] = np.where(rec["dem_cells"] > 0, lev - rec["dem_min"], np.float32(0.0))
+        return out
+
+    def sea_depths(self, level):
+        """The depth raster of one level on the held level raster: ``float32(level) - dem`` in the cells the level wets, 0 elsewhere.
+        It stays on the device for ``download_sea_depths`` (and its ``_rows`` / ``_to`` forms) and ``zone_stats("sea_depths")`` until
+        the DEM is written or ``sea_flood`` or ``sea_depths`` runs again."""
+        from .algorithms.fill import check_sea_levels
+        self._sea_held()
+        lev = check_sea_levels([level], self._sea_max_level)
+        _lib.call("mhip_ctx_sea_depths", self._ctx, ctypes.c_float(lev[0]))
+
+    def sea_classes(self, levels):
+        """The class raster of a series on the held level raster -- int32, ``k + 1`` of the first level that wets the cell, 0 where none
+        does -- for ``polygonize("sea_classes")`` and ``download_sea_classes``; it goes as the depths do."""
+        from .algorithms.fill import check_sea_levels
+        self._sea_held()
+        lev = check_sea_levels(levels, self._sea_max_level)
+        _lib.call("mhip_ctx_sea_classes", self._ctx, ctypes.c_int32(lev.size), _lib.ptr(lev))
+
+    def download_sea_level_rows(self, row0, nrows):
+        return self._held_rows("mhip_ctx_sea_flood_rows", np.float32, row0, nrows, lead=(ctypes.c_int32(0),), key="sea_flood",
+                               missing="sea_flood() has not been run on the resident DEM")
+
+    def download_sea_level(self):
+        """The level raster of the last ``sea_flood`` (float32); ``ValueError`` once the DEM it was made from is gone."""
+        return self.download_sea_level_rows(0, self.shape[0])
+
+    def download_sea_level_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.float32, self.download_sea_level_rows, max_rows)
+
+    def download_sea_depths_rows(self, row0, nrows):
+        return self._held_rows("mhip_ctx_sea_flood_rows", np.float32, row0, nrows, lead=(ctypes.c_int32(1),), key="sea_depths",
+                               missing="sea_depths() has not been run on the held sea levels")
+
+    def download_sea_depths(self):
+        """The depth raster of the last ``sea_depths`` (float32); ``ValueError`` once the levels it was made from are gone."""
+        return self.download_sea_depths_rows(0, self.shape[0])
+
+    def download_sea_depths_to(self, writer, max_rows=4096):
+        """Stream that raster into a writer in row windows, as ``download_to`` does for the rasters of ``RASTERS``."""
+        write_windows(writer, self.shape, np.float32, self.download_sea_depths_rows, max_rows)
+
+    def download_sea_classes_rows(self, row0, nrows):
+        return self._held_rows("mhip_ctx_sea_classes_rows", np.int32, row0, nrows, key="sea_classes",
+                               missing="sea_classes() has not been run on the held sea levels")
+
+    def download_sea_classes(self):
+        """The class raster of the last ``sea_classes`` (int32); ``ValueError`` once the levels it was made from are gone."""
+        return self.download_sea_classes_rows(0, self.shape[0])
