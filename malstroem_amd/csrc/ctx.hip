@@ -1,6 +1,9 @@
 // ctx.hip -- the device-resident context (ctx.hpp): create / destroy, the side-thread bracket, whole and windowed transfers, the
-// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the object zones, the outlines, the flow paths, the reach catchments and their flood depths, and the one
-// rule for what a write of a resident raster invalidates (ctx_wrote) and the one test for a raster held outside mhip_raster (ctx_held).  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
+// getters, the per-label records, the label filter, hypsometry and final depths, the DEM adaptations, the outlines, the flow paths, and
+// the held products -- wet_at, flow distance, travel time, hand, reach catchments and their flood depths, object zones, the sea flood --
+// with their one record each, one lock and one drop (held_begin / held_commit / held_drop; what each is made from is
+// held_rules.hpp).  The one rule for what a write of a resident raster invalidates (ctx_wrote) and the one test for a raster held
+// outside mhip_raster (ctx_held, over the HELD table) are here.  The stages are ctx_run.hip, the row-band protocol ctx_band.hip.
 #include <limits>
 #include <mutex>
 #include <new>
@@ -15,97 +18,51 @@ static void drop_hyps(mhip_ctx *c)
 {
     c->hyps_total = -1;
     c->have[MHIP_R_FINALDEPTHS] = false;
-    c->wetat_events = -1;      // (every call that fills the buffer has synchronised: nothing on the device still uses it)
-    c->wetat_out.release();
 }
 
-static void drop_flow_distance(mhip_ctx *c)
+// ---- the held products (held_rules.hpp) ---------------------------------------------------------------------------------------------
+// The one drop, with held_mu held: the product goes, its buffers go back to the pool (the call that filled them has synchronised:
+// nothing on the device still uses them), and so does every product that was made from it
+static void held_drop(mhip_ctx *c, int product)
 {
-    std::lock_guard<std::mutex> lk(c->fdist_mu);
-    c->fdist_unresolved = -1;      // (the call that fills the buffers has synchronised: nothing on the device still uses them)
-    c->fdist_out.release();
-    c->fdist_rec.release();
+    c->held[product].state = -1;
+    for (DevBuf &b : c->held[product].buf) b.release();
+    for (int p = 0; p < HP_COUNT_; ++p)
+        if (held_goes_with(p) & held_bit(product)) held_drop(c, p);
+    uint32_t live = 0;
+    for (const mhip_ctx::Held &h : c->held)
+        if (h.state >= 0) live |= h.made_from;
+    c->held_mask = live;
 }
 
-// `which` was written: the result of mhip_ctx_travel_time goes with any of the four rasters it is made from (which < 0: a new call)
-static void drop_travel_time(mhip_ctx *c, int which)
+// a making call begins: what its last call left goes, and what was made from that; the call fills the buffers of the record ...
+static mhip_ctx::Held &held_begin(mhip_ctx *c, int product)
 {
-    if (!(which < 0 || which == MHIP_R_FLOWDIR || which == MHIP_R_LABELS || which == MHIP_R_FILLED || which == MHIP_R_ACCUM)) return;
-    if (c->tt_unresolved < 0) return;      // (nothing held: the stages' writes take no lock for this)
-    std::lock_guard<std::mutex> lk(c->tt_mu);
-    c->tt_unresolved = -1;      // (the call that fills the buffers has synchronised: nothing on the device still uses them)
-    c->tt_saturated = -1;
-    c->tt_bins = 0;
-    c->tt_out.release();
-    c->tt_rec.release();
-    c->tt_hist.release();
+    std::lock_guard<std::mutex> lk(c->held_mu);
+    held_drop(c, product);
+    return c->held[product];
 }
 
-// the depths of mhip_ctx_inundate go with either of the two results they were made from
-static void drop_inundation(mhip_ctx *c)
+// ... and has succeeded: `state` (>= 0) is what mhip_ctx_get_i64 reports, `variant` what the rule of the product looks at
+static void held_commit(mhip_ctx *c, int product, int64_t state, int variant = 0)
 {
-    std::lock_guard<std::mutex> lk(c->rcatch_mu);
-    c->inund_held = -1;      // (the call that fills the buffer has synchronised: nothing on the device still uses it)
-    c->inund_out.release();
-}
-
-// `which` was written: the result of mhip_ctx_reach_catchments goes if it was made from that raster (which < 0: whatever it was made from)
-static void drop_reach_catchments(mhip_ctx *c, int which)
-{
-    if (c->rcatch_nreach < 0 && c->inund_held < 0) return;      // (nothing held: the stages' writes take no lock for this)
-    {
-        std::lock_guard<std::mutex> lk(c->rcatch_mu);
-        if (c->rcatch_nreach < 0) return;
-        if (!(which < 0 || which == MHIP_R_FLOWDIR || which == MHIP_R_ACCUM || (which == MHIP_R_LABELS && c->rcatch_labels))) return;
-        c->rcatch_nreach = -1;
-        c->rcatch_out.release();
-    }
-    drop_inundation(c);
-}
-
-// `which` was written: the result of mhip_ctx_hand goes if it was made from that raster (which < 0: whatever it was made from)
-static void drop_hand(mhip_ctx *c, int which)
-{
-    std::lock_guard<std::mutex> lk(c->hand_mu);
-    if (c->hand_undrained < 0) return;
-    if (!(which < 0 || which == MHIP_R_FLOWDIR || which == MHIP_R_ACCUM || which == c->hand_src || (which == MHIP_R_LABELS && c->hand_labels))) return;
-    c->hand_undrained = -1;      // (the call that fills the buffers has synchronised: nothing on the device still uses them)
-    c->hand_out.release();
-    c->hand_dist.release();
-    drop_inundation(c);
-}
-
-// the depths and the classes of the sea flood go with the level raster they were made from, and with a new call of their own
-static void drop_sea_depths(mhip_ctx *c)
-{
-    c->sea_depth_held = -1;      // (the call that fills the buffer has synchronised: nothing on the device still uses it)
-    c->sea_depth.release();
-}
-
-static void drop_sea_classes(mhip_ctx *c)
-{
-    c->sea_class_held = -1;
-    c->sea_class.release();
-}
-
-// the DEM was written, or a new mhip_ctx_sea_flood begins: the level raster of the last one goes, and what was made from it
-static void drop_sea_flood(mhip_ctx *c)
-{
-    c->sea_reached = -1;
-    c->sea_level.release();
-    drop_sea_depths(c);
-    drop_sea_classes(c);
+    std::lock_guard<std::mutex> lk(c->held_mu);
+    c->held[product].made_from = held_made_from(product, variant);
+    c->held[product].state = state;
+    c->held_mask |= c->held[product].made_from;
 }
 
 void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
 {
-    drop_hand(c, which);
-    drop_reach_catchments(c, which);
-    drop_travel_time(c, which);
+    // (with no product held that was made from `which` no lock is taken: all the stages' writes see of this)
+    if (const uint32_t w = held_write_mask(which); w & c->held_mask) {
+        std::lock_guard<std::mutex> lk(c->held_mu);
+        for (int p = 0; p < HP_COUNT_; ++p)
+            if (c->held[p].state >= 0 && (c->held[p].made_from & w)) held_drop(c, p);
+    }
     switch (which) {
     case MHIP_R_DEM:    // a new DEM invalidates everything derived from the previous one
         c->noflat_pending = false;      // (a surface nobody has asked for goes with have[NOFLAT])
-        drop_sea_flood(c);
         for (int k = 0; k < MHIP_R_COUNT_; ++k) {
             if (k == MHIP_R_DEM) continue;
             c->have[k] = false;
@@ -127,7 +84,6 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
         c->nodir_valid = false;
         c->flowdir_own = false;
         c->acc_keep.valid = false;
-        drop_flow_distance(c);
         break;
     case MHIP_R_ACCUM:
         c->acc_keep.valid = false;
@@ -141,7 +97,6 @@ void ctx_wrote(mhip_ctx *c, int which, bool uploaded)
         c->ws_counts_valid = false;
         c->pour_valid = false;
         drop_hyps(c);
-        drop_flow_distance(c);
         break;
     case MHIP_R_WATERSHEDS:
         c->ws_counts_valid = false;
@@ -162,23 +117,35 @@ int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, 
     return MHIP_OK;
 }
 
+// every raster held outside mhip_raster, in the order of HeldRaster: its product and which of the product's buffers it is (0: the
+// raster, 1: a second raster or the records, 2: the table); the key of mhip_ctx_get_i64 that reports the product's state (once per
+// product); what mhip_ctx_zone_stats / mhip_ctx_polygonize call it as a source (-1: no source of that call); the message of its getter
+static const struct HeldRow { int product, buf; const char *key; int zsrc, psrc; const char *needs; } HELD[HELD_COUNT_] = {
+    {HP_WETAT, 0, "wet_at_events", MHIP_ZSRC_WETAT, -1, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels"},
+    {HP_FLOWDIST, 0, "flow_distance_unresolved", MHIP_ZSRC_FLOWDIST, -1, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels"},
+    {HP_HAND, 0, "hand_undrained", MHIP_ZSRC_HAND, -1, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters"},
+    {HP_HAND, 1, nullptr, MHIP_ZSRC_DRAINDIST, -1, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters"},
+    {HP_REACHCATCH, 0, "reach_catchments", -1, MHIP_PSRC_REACHCATCH, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters"},
+    {HP_INUNDATION, 0, "inundation", MHIP_ZSRC_INUNDATION, -1, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments"},
+    {HP_ZONES, 0, "zones", -1, -1, "ctx_zones_rows needs mhip_ctx_rasterize_zones"},
+    {HP_TRAVELTIME, 0, "travel_time_unresolved", MHIP_ZSRC_TRAVELTIME, -1, "ctx_travel_time_rows needs mhip_ctx_travel_time on the resident rasters"},
+    {HP_SEALEVEL, 0, "sea_flood", MHIP_ZSRC_SEALEVEL, -1, "ctx_sea_flood_rows needs mhip_ctx_sea_flood on the resident DEM"},
+    {HP_SEADEPTH, 0, "sea_depths", MHIP_ZSRC_SEADEPTH, -1, "ctx_sea_flood_rows needs mhip_ctx_sea_depths on the held sea levels"},
+    {HP_SEACLASS, 0, "sea_classes", -1, MHIP_PSRC_SEACLASSES, "ctx_sea_classes_rows needs mhip_ctx_sea_classes on the held sea levels"},
+};
+
+static int held_source(int HeldRow::*column, int source)      // the raster that zone_stats (zsrc) / polygonize (psrc) calls `source`, or -1
+{
+    for (int id = 0; id < HELD_COUNT_; ++id)
+        if (source >= 0 && HELD[id].*column == source) return id;
+    return -1;
+}
+
 int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes)
 {
-    const struct { bool held; const DevBuf &buf; const char *needs; } t[HELD_COUNT_] = {      // (in the order of the enumeration)
-        {c->wetat_events > 0, c->wetat_out, "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels"},
-        {c->fdist_unresolved >= 0, c->fdist_out, "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels"},
-        {c->hand_undrained >= 0, c->hand_out, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters"},      // (the two are made and dropped
-        {c->hand_undrained >= 0, c->hand_dist, "ctx_hand_rows needs mhip_ctx_hand on the resident rasters"},     // together: one is there, both are)
-        {c->rcatch_nreach >= 0, c->rcatch_out, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters"},
-        {c->inund_held > 0, c->inund_out, "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments"},
-        {c->nzone >= 0, c->zones, "ctx_zones_rows needs mhip_ctx_rasterize_zones"},
-        {c->tt_unresolved >= 0, c->tt_out, "ctx_travel_time_rows needs mhip_ctx_travel_time on the resident rasters"},
-        {c->sea_reached >= 0, c->sea_level, "ctx_sea_flood_rows needs mhip_ctx_sea_flood on the resident DEM"},
-        {c->sea_depth_held > 0, c->sea_depth, "ctx_sea_flood_rows needs mhip_ctx_sea_depths on the held sea levels"},
-        {c->sea_class_held > 0, c->sea_class, "ctx_sea_classes_rows needs mhip_ctx_sea_classes on the held sea levels"},
-    };
-    MH_ARG(t[id].held && t[id].buf.p, t[id].needs);
-    *ptr = t[id].buf.p;
+    const mhip_ctx::Held &h = c->held[HELD[id].product];
+    MH_ARG(h.state >= 0 && h.buf[HELD[id].buf].p, HELD[id].needs);
+    *ptr = h.buf[HELD[id].buf].p;
     if (elem_bytes) *elem_bytes = 4;      // (float32 or int32, every one)
     return MHIP_OK;
 }
@@ -556,24 +523,19 @@ int mhip_ctx_get_i64(mhip_ctx *c, const char *key, int64_t *value)
     else if (k == "noflat_rows_stored") *value = c->noflat_st.rows_stored;  // ... and the rows of distances that came to
     else if (k == "hyps_bins") *value = c->hyps_total;               // -1: no table (mhip_ctx_hyps)
     else if (k == "hyps_lds_spills") *value = c->hyps_spills;        // runs that found no slot in their tile's LDS table
-    else if (k == "wet_at_events") *value = c->wetat_events;         // -1: no raster of mhip_ctx_wet_at on the resident depths and labels
-    else if (k == "flow_distance_unresolved") *value = c->fdist_unresolved;   // -1: no result of mhip_ctx_flow_distance on the resident flow directions and labels
-    else if (k == "travel_time_unresolved") *value = c->tt_unresolved;   // -1: no result of mhip_ctx_travel_time on the resident rasters
-    else if (k == "travel_time_saturated") *value = c->tt_unresolved >= 0 ? c->tt_saturated : -1;   // the cells whose cost was clipped to the cap
-    else if (k == "travel_time_bins") *value = c->tt_unresolved >= 0 ? c->tt_bins : -1;             // the bins of the table held, 0: no table
-    else if (k == "hand_undrained") *value = c->hand_undrained;     // -1: no result of mhip_ctx_hand on the resident rasters
-    else if (k == "reach_catchments") *value = c->rcatch_nreach;     // -1: no result of mhip_ctx_reach_catchments on the resident rasters
-    else if (k == "inundation") *value = c->inund_held;              // 1: a depth raster of mhip_ctx_inundate is held, -1: none
-    else if (k == "zones") *value = c->nzone;                       // -1: no zone raster of mhip_ctx_rasterize_zones
-    else if (k == "sea_flood") *value = c->sea_reached;              // the cells the last mhip_ctx_sea_flood reached, -1: no level raster is held
-    else if (k == "sea_depths") *value = c->sea_depth_held;          // 1: a depth raster of mhip_ctx_sea_depths is held, -1: none
-    else if (k == "sea_classes") *value = c->sea_class_held;         // 1: a class raster of mhip_ctx_sea_classes is held, -1: none
+    else if (k == "travel_time_saturated") *value = c->held[HP_TRAVELTIME].state >= 0 ? c->tt_saturated : -1;   // the cells whose cost was clipped to the cap
+    else if (k == "travel_time_bins") *value = c->held[HP_TRAVELTIME].state >= 0 ? c->tt_bins : -1;             // the bins of the table held, 0: no table
     else if (k == "seaflood_rounds") *value = c->sea_st.rounds;      // of the last mhip_ctx_sea_flood: launches that found work,
     else if (k == "seaflood_visits") *value = c->sea_st.visits;      // ... tile visits,
     else if (k == "seaflood_rechecks") *value = c->sea_st.rechecks;  // ... tiles its proof sent back (0 unless something is broken)
     else if (k == "H") *value = c->H;
     else if (k == "W") *value = c->W;
-    else {
+    else {      // the state of a held product (HELD: key), -1: none
+        for (const HeldRow &row : HELD)
+            if (row.key && k == row.key) {
+                *value = c->held[row.product].state;
+                return MHIP_OK;
+            }
         set_error("unknown key '%s'", key);
         return MHIP_EINVAL;
     }
@@ -630,7 +592,7 @@ int mhip_ctx_pourpoints(mhip_ctx *c, mhip_index_record *records)
 int mhip_ctx_hyps(mhip_ctx *c, double res, int64_t *total)
 {
     MH_ARG(c && total && hyps_res_ok(res), "ctx_hyps(ctx, 0 < res < inf, total)");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "hypsometry on a row band is not built (the tables of the bands add up: a later step); use an undivided context");
+    MH_ARG(undivided(c), "hypsometry on a row band is not built (the tables of the bands add up: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_DEPTHS] && c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_hyps needs the DEPTHS and LABELS rasters");
     MH_ARG(c->labels_filtered, "ctx_hyps needs mhip_ctx_apply_keep after the LABEL run");
     MH_HIP(hipSetDevice(c->device));
@@ -710,7 +672,7 @@ int mhip_ctx_wet_at(mhip_ctx *c, int32_t K, const double *q, const float *values
 {
     MH_ARG(c && q && values && records, "ctx_wet_at(ctx, K, q, values, records)");
     MH_ARG(wet_at_events_ok(K, values), "ctx_wet_at: 1 to 16 events whose values are finite, > 0 and strictly increasing");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "wet_at on a row band is not built (it needs the bands' hypsometry tables: a later step); use an undivided context");
+    MH_ARG(undivided(c), "wet_at on a row band is not built (it needs the bands' hypsometry tables: a later step); use an undivided context");
     MH_ARG(c->hyps_total >= 0 && c->stats_valid, "ctx_wet_at needs mhip_ctx_hyps on the resident depths and labels");
     MH_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -719,8 +681,8 @@ int mhip_ctx_wet_at(mhip_ctx *c, int32_t K, const double *q, const float *values
     DevBuf d_q, d_rec;
     MH_TRY(upload(d_q, q, 8 * nt, s));
     MH_TRY(d_rec.alloc(sizeof(mhip_final_record) * nt));
-    c->wetat_events = -1;
-    MH_TRY(c->wetat_out.alloc(4 * (size_t)n));
+    DevBuf &out = held_begin(c, HP_WETAT).buf[0];
+    MH_TRY(out.alloc(4 * (size_t)n));
     StageTimer *k;
     MH_TRY(ctx_timer(c, WETAT_KERNEL_SLOT, &k));
     for (int32_t e = 0; e < K; ++e)
@@ -728,9 +690,9 @@ int mhip_ctx_wet_at(mhip_ctx *c, int32_t K, const double *q, const float *values
                                d_q.as<double>() + (size_t)e * (size_t)(nlab + 1), d_rec.as<mhip_final_record>() + (size_t)e * (size_t)(nlab + 1), s));
     // the draw-downs out of the records' first field, the wet cells into their last (the levels left 0 there)
     MH_TRY(wet_at_dev(c->r[MHIP_R_DEPTHS].as<float>(), c->r[MHIP_R_LABELS].as<int32_t>(), n, c->W, nlab, K, d_rec.as<double>(), 4, values,
-                      c->wetat_out.as<float>(), d_rec.as<int64_t>() + 3, 4, s, k->a, k->b));      // (synchronises)
+                      out.as<float>(), d_rec.as<int64_t>() + 3, 4, s, k->a, k->b));      // (synchronises)
     k->valid = true;
-    c->wetat_events = K;
+    held_commit(c, HP_WETAT, K);
     return ctx_fetch(c, d_rec, sizeof(mhip_final_record) * nt, records);
 }
 
@@ -744,20 +706,21 @@ int mhip_ctx_flow_distance(mhip_ctx *c, double scale, int64_t *unresolved)
 {
     MH_ARG(c && unresolved, "ctx_flow_distance(ctx, scale, unresolved)");
     MH_ARG(flow_distance_scale_ok(scale), "ctx_flow_distance: the scale must be finite and > 0");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "flow distance on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "flow distance on a row band is not built (a path crosses the seams: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_flow_distance needs the FLOWDIR and LABELS rasters");
     MH_ARG(c->labels_filtered, "ctx_flow_distance needs mhip_ctx_apply_keep after the LABEL run");
     MH_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     MH_TRY(ctx_label_max(c, s));
     const int64_t nlab = c->nlabels, n = c->H * c->W;
-    drop_flow_distance(c);
-    MH_TRY(c->fdist_out.alloc(4 * (size_t)n));
-    MH_TRY(c->fdist_rec.alloc(sizeof(mhip_index_record) * (size_t)(nlab + 1)));
+    mhip_ctx::Held &h = held_begin(c, HP_FLOWDIST);
+    DevBuf &out = h.buf[0], &rec = h.buf[1];
+    MH_TRY(out.alloc(4 * (size_t)n));
+    MH_TRY(rec.alloc(sizeof(mhip_index_record) * (size_t)(nlab + 1)));
     int64_t u = 0;
-    MH_TRY(flow_distance_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_LABELS].as<int32_t>(), c->H, c->W, scale, nlab, c->fdist_out.as<float>(),
-                             c->fdist_rec.as<mhip_index_record>(), &u, s));      // (synchronises)
-    c->fdist_unresolved = u;
+    MH_TRY(flow_distance_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_LABELS].as<int32_t>(), c->H, c->W, scale, nlab, out.as<float>(),
+                             rec.as<mhip_index_record>(), &u, s));      // (synchronises)
+    held_commit(c, HP_FLOWDIST, u);
     *unresolved = u;
     return MHIP_OK;
 }
@@ -770,8 +733,9 @@ int mhip_ctx_flow_distance_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float 
 int mhip_ctx_flow_distance_records(mhip_ctx *c, mhip_index_record *records)
 {
     MH_ARG(c && records, "ctx_flow_distance_records(ctx, records)");
-    MH_ARG(c->fdist_unresolved >= 0 && c->fdist_rec.p, "ctx_flow_distance_records needs mhip_ctx_flow_distance on the resident flow directions and labels");
-    return ctx_fetch(c, c->fdist_rec, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
+    const mhip_ctx::Held &h = c->held[HP_FLOWDIST];
+    MH_ARG(h.state >= 0 && h.buf[1].p, "ctx_flow_distance_records needs mhip_ctx_flow_distance on the resident flow directions and labels");
+    return ctx_fetch(c, h.buf[1], sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
 }
 
 /* ---- travel time to the receiving bluespot, time of concentration and time-area table per watershed (traveltime.hip) ------------- */
@@ -780,7 +744,7 @@ int mhip_ctx_travel_time(mhip_ctx *c, double cellsize, const mhip_traveltime_par
     MH_ARG(c && unresolved, "ctx_travel_time(ctx, cellsize, params, nbins, bin_ticks, unresolved)");
     MH_TRY(travel_time_check(cellsize, params));
     MH_TRY(travel_time_walk_check(params->tick, nbins, bin_ticks, nbins != 0));
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "travel time on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "travel time on a row band is not built (a path crosses the seams: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_travel_time needs the FLOWDIR and LABELS rasters");
     MH_ARG(c->have[MHIP_R_FILLED], "ctx_travel_time needs the FILLED raster");
     const bool classes = params->channel_threshold <= 1.7976931348623157e308;      // (finite: two classes are live)
@@ -790,21 +754,21 @@ int mhip_ctx_travel_time(mhip_ctx *c, double cellsize, const mhip_traveltime_par
     hipStream_t s = c->stream;
     MH_TRY(ctx_label_max(c, s));
     const int64_t nlab = c->nlabels, n = c->H * c->W;
-    drop_travel_time(c, -1);
+    mhip_ctx::Held &h = held_begin(c, HP_TRAVELTIME);
+    DevBuf &out = h.buf[0], &rec = h.buf[1], &hist = h.buf[2];
     DevBuf cost;      // (scratch of this call)
     MH_TRY(cost.alloc(4 * (size_t)n));
     int64_t sat = 0, u = 0;
     MH_TRY(step_cost_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_FILLED].as<float>(), classes ? c->r[MHIP_R_ACCUM].as<double>() : nullptr, c->H, c->W,
                          cellsize, *params, cost.as<uint32_t>(), &sat, s));
-    MH_TRY(c->tt_out.alloc(4 * (size_t)n));
-    MH_TRY(c->tt_rec.alloc(sizeof(mhip_index_record) * (size_t)(nlab + 1)));
-    if (nbins) MH_TRY(c->tt_hist.alloc(4 * (size_t)(nlab + 1) * (size_t)nbins));
+    MH_TRY(out.alloc(4 * (size_t)n));
+    MH_TRY(rec.alloc(sizeof(mhip_index_record) * (size_t)(nlab + 1)));
+    if (nbins) MH_TRY(hist.alloc(4 * (size_t)(nlab + 1) * (size_t)nbins));
     MH_TRY(flow_cost_distance_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_LABELS].as<int32_t>(), cost.as<uint32_t>(), c->H, c->W, params->tick, nlab,
-                                  c->tt_out.as<float>(), c->tt_rec.as<mhip_index_record>(), nbins, bin_ticks, nbins ? c->tt_hist.as<uint32_t>() : nullptr, &u,
-                                  s));      // (synchronises)
+                                  out.as<float>(), rec.as<mhip_index_record>(), nbins, bin_ticks, nbins ? hist.as<uint32_t>() : nullptr, &u, s));      // (synchronises)
     c->tt_saturated = sat;
     c->tt_bins = nbins;
-    c->tt_unresolved = u;
+    held_commit(c, HP_TRAVELTIME, u);
     *unresolved = u;
     return MHIP_OK;
 }
@@ -817,16 +781,18 @@ int mhip_ctx_travel_time_rows(mhip_ctx *c, int64_t row0, int64_t nrows, float *d
 int mhip_ctx_travel_time_records(mhip_ctx *c, mhip_index_record *records)
 {
     MH_ARG(c && records, "ctx_travel_time_records(ctx, records)");
-    MH_ARG(c->tt_unresolved >= 0 && c->tt_rec.p, "ctx_travel_time_records needs mhip_ctx_travel_time on the resident rasters");
-    return ctx_fetch(c, c->tt_rec, sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
+    const mhip_ctx::Held &h = c->held[HP_TRAVELTIME];
+    MH_ARG(h.state >= 0 && h.buf[1].p, "ctx_travel_time_records needs mhip_ctx_travel_time on the resident rasters");
+    return ctx_fetch(c, h.buf[1], sizeof(mhip_index_record) * (size_t)(c->nlabels + 1), records);
 }
 
 int mhip_ctx_travel_time_hist(mhip_ctx *c, int64_t nbins, uint32_t *hist)
 {
     MH_ARG(c && hist, "ctx_travel_time_hist(ctx, nbins, hist)");
-    MH_ARG(c->tt_unresolved >= 0 && c->tt_bins > 0 && c->tt_hist.p, "ctx_travel_time_hist needs mhip_ctx_travel_time with a table on the resident rasters");
+    const mhip_ctx::Held &h = c->held[HP_TRAVELTIME];
+    MH_ARG(h.state >= 0 && c->tt_bins > 0 && h.buf[2].p, "ctx_travel_time_hist needs mhip_ctx_travel_time with a table on the resident rasters");
     MH_ARG(nbins == c->tt_bins, "ctx_travel_time_hist: nbins is not the held table's");
-    return ctx_fetch(c, c->tt_hist, 4 * (size_t)(c->nlabels + 1) * (size_t)nbins, hist);
+    return ctx_fetch(c, h.buf[2], 4 * (size_t)(c->nlabels + 1) * (size_t)nbins, hist);
 }
 
 /* ---- height above the nearest drainage and the distance to it (hand.hip) ---------------------------------------------------------- */
@@ -835,7 +801,7 @@ int mhip_ctx_hand(mhip_ctx *c, int32_t elev_source, double threshold, int32_t st
     MH_ARG(c && undrained, "ctx_hand(ctx, elev_source, threshold, stop_at_labels, scale, nodata, undrained)");
     MH_ARG(elev_source == MHIP_R_FILLED || elev_source == MHIP_R_DEM, "ctx_hand: the elevation source is MHIP_R_FILLED or MHIP_R_DEM");
     MH_TRY(hand_check(threshold, scale));
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "hand on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "hand on a row band is not built (a path crosses the seams: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_ACCUM] && c->have[elev_source], "ctx_hand needs the FLOWDIR and ACCUM rasters and the elevation source");
     if (stop_at_labels) {
         MH_ARG(c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_hand with stop_at_labels needs the LABELS raster");
@@ -843,18 +809,18 @@ int mhip_ctx_hand(mhip_ctx *c, int32_t elev_source, double threshold, int32_t st
     }
     MH_HIP(hipSetDevice(c->device));
     const int64_t n = c->H * c->W;
-    drop_hand(c, -1);
-    MH_TRY(c->hand_out.alloc(4 * (size_t)n));
-    MH_TRY(c->hand_dist.alloc(4 * (size_t)n));
+    mhip_ctx::Held &h = held_begin(c, HP_HAND);
+    DevBuf &out = h.buf[0], &dist = h.buf[1];      // (made and dropped together: one is there, both are)
+    MH_TRY(out.alloc(4 * (size_t)n));
+    MH_TRY(dist.alloc(4 * (size_t)n));
     int64_t u = 0;
     MH_TRY(hand_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_ACCUM].as<double>(), c->r[elev_source].as<float>(),
-                    stop_at_labels ? c->r[MHIP_R_LABELS].as<int32_t>() : nullptr, c->H, c->W, threshold, scale, nodata, c->hand_out.as<float>(),
-                    c->hand_dist.as<float>(), &u, c->stream));      // (synchronises)
-    c->hand_src = elev_source;
+                    stop_at_labels ? c->r[MHIP_R_LABELS].as<int32_t>() : nullptr, c->H, c->W, threshold, scale, nodata, out.as<float>(), dist.as<float>(), &u,
+                    c->stream));      // (synchronises)
     c->hand_labels = stop_at_labels != 0;
     c->hand_thr = threshold;
     c->hand_nodata = nodata;
-    c->hand_undrained = u;
+    held_commit(c, HP_HAND, u, held_variant(elev_source, c->hand_labels));
     *undrained = u;
     return MHIP_OK;
 }
@@ -869,7 +835,7 @@ int mhip_ctx_burn_lines(mhip_ctx *c, int64_t nseg, const mhip_burn_segment *segm
                         mhip_burn_result *results)
 {
     MH_ARG(c, "ctx_burn_lines(ctx, nseg, segments, nline, lines, nodata, results)");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "DEM adaptations on a row band are not built (a line crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "DEM adaptations on a row band are not built (a line crosses the seams: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_DEM], "ctx_burn_lines needs the DEM raster");
     MH_TRY(burn_check(nseg, segments, nline, lines, results));
     if (nseg == 0) return burn_lines_dev(nullptr, c->H, c->W, 0, segments, nline, lines, nodata, results, nullptr);      // (the records; the context stays as it is)
@@ -883,18 +849,18 @@ int mhip_ctx_rasterize_zones(mhip_ctx *c, int64_t nvert, const double *xy, int64
                              int64_t nzone, int32_t grow)
 {
     MH_ARG(c, "ctx_rasterize_zones(ctx, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow)");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
     MH_TRY(zones_check(c->H, c->W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow));
     MH_HIP(hipSetDevice(c->device));
-    c->nzone = -1;
-    MH_TRY(c->zones.alloc(4 * (size_t)(c->H * c->W)));
+    DevBuf &zones = held_begin(c, HP_ZONES).buf[0];
+    MH_TRY(zones.alloc(4 * (size_t)(c->H * c->W)));
     if (nring == 0) {
-        MH_HIP(hipMemsetAsync(c->zones.p, 0, 4 * (size_t)(c->H * c->W), c->stream));
+        MH_HIP(hipMemsetAsync(zones.p, 0, 4 * (size_t)(c->H * c->W), c->stream));
         MH_HIP(stream_sync(c->stream));
     } else {
-        MH_TRY(zones_rasterize_dev(c->zones.as<int32_t>(), c->H, c->W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow, c->stream));      // (synchronises)
+        MH_TRY(zones_rasterize_dev(zones.as<int32_t>(), c->H, c->W, nvert, xy, nring, ring_offsets, ring_zone, nzone, grow, c->stream));      // (synchronises)
     }
-    c->nzone = nzone;
+    held_commit(c, HP_ZONES, nzone);
     return MHIP_OK;
 }
 
@@ -906,33 +872,32 @@ int mhip_ctx_zones_rows(mhip_ctx *c, int64_t row0, int64_t nrows, int32_t *dst)
 int mhip_ctx_zone_stats(mhip_ctx *c, int32_t source, mhip_zone_record *records)
 {
     MH_ARG(c && records, "ctx_zone_stats(ctx, source, records)");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "zones on a row band are not built (an object crosses the seams: a later step); use an undivided context");
     const bool member = source == MHIP_R_DEM || source == MHIP_R_FILLED || source == MHIP_R_DEPTHS || source == MHIP_R_FINALDEPTHS;
-    const int id = source == MHIP_ZSRC_WETAT ? HELD_WETAT : source == MHIP_ZSRC_FLOWDIST ? HELD_FLOWDIST : source == MHIP_ZSRC_HAND ? HELD_HAND :
-                   source == MHIP_ZSRC_DRAINDIST ? HELD_DRAINDIST : source == MHIP_ZSRC_INUNDATION ? HELD_INUNDATION : source == MHIP_ZSRC_TRAVELTIME ? HELD_TRAVELTIME :
-                   source == MHIP_ZSRC_SEALEVEL ? HELD_SEALEVEL : source == MHIP_ZSRC_SEADEPTH ? HELD_SEADEPTH : -1;
+    const int id = held_source(&HeldRow::zsrc, source);
     MH_ARG(member || id >= 0, "ctx_zone_stats: the source is no float32 raster of the context");
-    void *src = member ? c->r[source].p : nullptr;
+    void *src = member ? c->r[source].p : nullptr, *zones = nullptr;
     if (member) MH_ARG(c->have[source], "raster has not been computed or uploaded");
     else MH_TRY(ctx_held(c, id, &src));
-    MH_ARG(c->nzone >= 0 && c->zones.p, "ctx_zone_stats needs mhip_ctx_rasterize_zones");
+    MH_ARG(ctx_held(c, HELD_ZONES, &zones) == MHIP_OK, "ctx_zone_stats needs mhip_ctx_rasterize_zones");
+    const int64_t nzone = c->held[HP_ZONES].state;
     MH_HIP(hipSetDevice(c->device));
     DevBuf d_rec;
-    MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(c->nzone + 1)));
-    MH_TRY(zone_stats_dev((const float *)src, c->zones.as<int32_t>(), c->H * c->W, c->W, c->nzone, d_rec.as<mhip_zone_record>(), c->stream));
-    return ctx_fetch(c, d_rec, sizeof(mhip_zone_record) * (size_t)(c->nzone + 1), records);
+    MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(nzone + 1)));
+    MH_TRY(zone_stats_dev((const float *)src, (const int32_t *)zones, c->H * c->W, c->W, nzone, d_rec.as<mhip_zone_record>(), c->stream));
+    return ctx_fetch(c, d_rec, sizeof(mhip_zone_record) * (size_t)(nzone + 1), records);
 }
 
 /* ---- the outlines of the resident labels or watersheds (polygonize.hip): a snapshot in buffers of the handle, no raster leaves the device */
 int mhip_ctx_polygonize(mhip_ctx *c, int32_t source, mhip_polygons **out)
 {
     MH_ARG(c && out, "ctx_polygonize(ctx, source, out)");
-    MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS || source == MHIP_PSRC_REACHCATCH || source == MHIP_PSRC_SEACLASSES,
+    const int id = held_source(&HeldRow::psrc, source);
+    MH_ARG(source == MHIP_R_LABELS || source == MHIP_R_WATERSHEDS || id >= 0,
            "ctx_polygonize: the source is MHIP_R_LABELS or MHIP_R_WATERSHEDS, MHIP_PSRC_REACHCATCH for the reach catchments or MHIP_PSRC_SEACLASSES for the sea flood's classes");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "outlines on a row band are not built (a ring crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "outlines on a row band are not built (a ring crosses the seams: a later step); use an undivided context");
     void *held = nullptr;
-    if (source == MHIP_PSRC_REACHCATCH) MH_TRY(ctx_held(c, HELD_REACHCATCH, &held));
-    else if (source == MHIP_PSRC_SEACLASSES) MH_TRY(ctx_held(c, HELD_SEACLASS, &held));
+    if (id >= 0) MH_TRY(ctx_held(c, id, &held));
     else MH_ARG(c->have[source], "raster has not been computed or uploaded");
     if (source == MHIP_R_LABELS) MH_ARG(c->labels_filtered && !c->ccl_pending, "ctx_polygonize needs mhip_ctx_apply_keep after the LABEL run");
     MH_TRY(polygonize_check(c->H, c->W));
@@ -958,7 +923,7 @@ int mhip_ctx_flowpaths(mhip_ctx *c, double threshold, int32_t stop_at_labels, mh
 {
     MH_ARG(c && out, "ctx_flowpaths(ctx, threshold, stop_at_labels, out)");
     MH_TRY(flowpaths_check(c->H, c->W, threshold));
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "flow paths on a row band are not built (a reach crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "flow paths on a row band are not built (a reach crosses the seams: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_ACCUM], "raster has not been computed or uploaded");
     if (stop_at_labels) {
         MH_ARG(c->have[MHIP_R_LABELS], "raster has not been computed or uploaded");
@@ -986,7 +951,7 @@ int mhip_ctx_reach_catchments(mhip_ctx *c, double threshold, int32_t stop_at_lab
 {
     MH_ARG(c && out && assigned, "ctx_reach_catchments(ctx, threshold, stop_at_labels, out_reaches, assigned)");
     MH_TRY(flowpaths_check(c->H, c->W, threshold));
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "reach catchments on a row band are not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "reach catchments on a row band are not built (a path crosses the seams: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_FLOWDIR] && c->have[MHIP_R_ACCUM], "ctx_reach_catchments needs the FLOWDIR and ACCUM rasters");
     if (stop_at_labels) {
         MH_ARG(c->have[MHIP_R_LABELS] && !c->ccl_pending, "ctx_reach_catchments with stop_at_labels needs the LABELS raster");
@@ -999,22 +964,21 @@ int mhip_ctx_reach_catchments(mhip_ctx *c, double threshold, int32_t stop_at_lab
         return MHIP_EHIP;
     }
     p->device = c->device;
-    drop_reach_catchments(c, -1);
-    drop_inundation(c);      // (a new call drops the depths, whether catchments were held or not)
+    DevBuf &catchments = held_begin(c, HP_REACHCATCH).buf[0];      // (the depths of mhip_ctx_inundate go with it)
     int64_t a = 0;
-    int rc = c->rcatch_out.alloc(4 * (size_t)(c->H * c->W));
+    int rc = catchments.alloc(4 * (size_t)(c->H * c->W));
     if (rc == MHIP_OK)
         rc = reach_catchments_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), c->r[MHIP_R_ACCUM].as<double>(),
-                                  stop_at_labels ? c->r[MHIP_R_LABELS].as<int32_t>() : nullptr, c->H, c->W, threshold, c->rcatch_out.as<int32_t>(), p, &a,
+                                  stop_at_labels ? c->r[MHIP_R_LABELS].as<int32_t>() : nullptr, c->H, c->W, threshold, catchments.as<int32_t>(), p, &a,
                                   c->stream);      // (synchronises)
     if (rc != MHIP_OK) {
         delete p;
-        c->rcatch_out.release();
+        catchments.release();
         return rc;
     }
     c->rcatch_thr = threshold;
     c->rcatch_labels = stop_at_labels != 0;
-    c->rcatch_nreach = p->nreach;
+    held_commit(c, HP_REACHCATCH, p->nreach, held_variant(0, c->rcatch_labels));
     *assigned = a;
     *out = p;
     return MHIP_OK;
@@ -1028,27 +992,27 @@ int mhip_ctx_reach_catchments_rows(mhip_ctx *c, int64_t row0, int64_t nrows, int
 int mhip_ctx_inundate(mhip_ctx *c, int64_t nreach, const float *stage, mhip_zone_record *records)
 {
     MH_ARG(c && stage, "ctx_inundate(ctx, nreach, stage, records)");
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "inundation on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "inundation on a row band is not built (a path crosses the seams: a later step); use an undivided context");
     void *hand = nullptr, *rcatch = nullptr;
     MH_ARG(ctx_held(c, HELD_HAND, &hand) == MHIP_OK, "ctx_inundate needs mhip_ctx_hand on the resident rasters");
     MH_ARG(ctx_held(c, HELD_REACHCATCH, &rcatch) == MHIP_OK, "ctx_inundate needs mhip_ctx_reach_catchments on the resident rasters");
     MH_ARG(c->hand_thr == c->rcatch_thr, "ctx_inundate: the hand and the reach catchments were made with different thresholds");
     MH_ARG(c->hand_labels == c->rcatch_labels, "ctx_inundate: the hand and the reach catchments were made with different stop_at_labels");
-    MH_ARG(nreach == c->rcatch_nreach, "ctx_inundate: nreach is not the number of reaches of the catchments held");
+    MH_ARG(nreach == c->held[HP_REACHCATCH].state, "ctx_inundate: nreach is not the number of reaches of the catchments held");
     MH_HIP(hipSetDevice(c->device));
-    drop_inundation(c);
+    DevBuf &out = held_begin(c, HP_INUNDATION).buf[0];
     const int64_t n = c->H * c->W;
     DevBuf d_stage, d_rec;
     MH_TRY(upload(d_stage, stage, 4 * ((size_t)nreach + 1), c->stream));
     if (records) MH_TRY(d_rec.alloc(sizeof(mhip_zone_record) * (size_t)(nreach + 1)));
-    MH_TRY(c->inund_out.alloc(4 * (size_t)n));
-    const int rc = inundate_dev((const float *)hand, (const int32_t *)rcatch, n, c->W, nreach, d_stage.as<float>(), c->hand_nodata,
-                                c->inund_out.as<float>(), records ? d_rec.as<mhip_zone_record>() : nullptr, c->stream);      // (synchronises)
+    MH_TRY(out.alloc(4 * (size_t)n));
+    const int rc = inundate_dev((const float *)hand, (const int32_t *)rcatch, n, c->W, nreach, d_stage.as<float>(), c->hand_nodata, out.as<float>(),
+                                records ? d_rec.as<mhip_zone_record>() : nullptr, c->stream);      // (synchronises)
     if (rc != MHIP_OK) {
-        c->inund_out.release();
+        out.release();
         return rc;
     }
-    c->inund_held = 1;
+    held_commit(c, HP_INUNDATION, 1);
     if (records) return ctx_fetch(c, d_rec, sizeof(mhip_zone_record) * (size_t)(nreach + 1), records);
     return MHIP_OK;
 }
@@ -1064,17 +1028,17 @@ int mhip_ctx_sea_flood(mhip_ctx *c, const float *stage, const float *zone_stage,
     MH_ARG(c && reached, "ctx_sea_flood(ctx, stage_or_NULL, zone_stage_or_NULL, nzone, max_level, nodata, reached)");
     MH_ARG((stage != nullptr) != (zone_stage != nullptr), "ctx_sea_flood takes exactly one source form: a stage raster, or a stage per zone");
     MH_TRY(sea_flood_check(max_level, nodata));
-    MH_ARG(!(c->nranks > 1 || c->ht || c->hb), "sea flooding on a row band is not built (the water crosses the seams: a later step); use an undivided context");
+    MH_ARG(undivided(c), "sea flooding on a row band is not built (the water crosses the seams: a later step); use an undivided context");
     MH_ARG(c->have[MHIP_R_DEM], "ctx_sea_flood needs the DEM raster");
     void *zones = nullptr;
     if (zone_stage) {
         MH_ARG(ctx_held(c, HELD_ZONES, &zones) == MHIP_OK, "ctx_sea_flood with a stage per zone needs mhip_ctx_rasterize_zones");
-        MH_ARG(nzone == c->nzone, "ctx_sea_flood: nzone is not the number of zones of the zone raster held");
+        MH_ARG(nzone == c->held[HP_ZONES].state, "ctx_sea_flood: nzone is not the number of zones of the zone raster held");
     }
     MH_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int64_t n = c->H * c->W;
-    drop_sea_flood(c);
+    DevBuf &level = held_begin(c, HP_SEALEVEL).buf[0];      // (the depths and the classes go with it)
     DevBuf d_stage;
     if (stage) {
         MH_TRY(upload(d_stage, stage, 4 * (size_t)n, s));
@@ -1084,18 +1048,18 @@ int mhip_ctx_sea_flood(mhip_ctx *c, const float *stage, const float *zone_stage,
         MH_TRY(upload(d_stage, zs.data(), 4 * zs.size(), s));
         MH_HIP(stream_sync(s));      // (zs goes away)
     }
-    MH_TRY(c->sea_level.alloc(4 * (size_t)n));
+    MH_TRY(level.alloc(4 * (size_t)n));
     int64_t r = 0;
     const int rc = sea_flood_dev(c->r[MHIP_R_DEM].as<float>(), stage ? d_stage.as<float>() : nullptr, (const int32_t *)zones, stage ? nullptr : d_stage.as<float>(),
-                                 stage ? 0 : nzone, c->H, c->W, max_level, nodata, c->sea_level.as<float>(), &r, &c->sea_st, s);      // (synchronises)
+                                 stage ? 0 : nzone, c->H, c->W, max_level, nodata, level.as<float>(), &r, &c->sea_st, s);      // (synchronises)
     if (rc != MHIP_OK) {
         MH_HIP(stream_sync(s));      // (an error may have left launches behind: the buffers go back to the pool)
-        c->sea_level.release();
+        level.release();
         return rc;
     }
     c->sea_max_level = max_level;
     c->sea_nodata = nodata;
-    c->sea_reached = r;
+    held_commit(c, HP_SEALEVEL, r);
     *reached = r;
     return MHIP_OK;
 }
@@ -1122,10 +1086,10 @@ int mhip_ctx_sea_depths(mhip_ctx *c, float z)
     MH_ARG(ctx_held(c, HELD_SEALEVEL, &lev) == MHIP_OK, "ctx_sea_depths needs mhip_ctx_sea_flood on the resident DEM");
     MH_TRY(sea_levels_check(1, &z, c->sea_max_level));
     MH_HIP(hipSetDevice(c->device));
-    drop_sea_depths(c);
-    MH_TRY(c->sea_depth.alloc(4 * (size_t)(c->H * c->W)));
-    MH_TRY(sea_depths_dev((const float *)lev, c->r[MHIP_R_DEM].as<float>(), c->H * c->W, c->sea_nodata, z, c->sea_depth.as<float>(), c->stream));
-    c->sea_depth_held = 1;
+    DevBuf &out = held_begin(c, HP_SEADEPTH).buf[0];
+    MH_TRY(out.alloc(4 * (size_t)(c->H * c->W)));
+    MH_TRY(sea_depths_dev((const float *)lev, c->r[MHIP_R_DEM].as<float>(), c->H * c->W, c->sea_nodata, z, out.as<float>(), c->stream));
+    held_commit(c, HP_SEADEPTH, 1);
     return MHIP_OK;
 }
 
@@ -1136,10 +1100,10 @@ int mhip_ctx_sea_classes(mhip_ctx *c, int32_t K, const float *levels)
     MH_ARG(ctx_held(c, HELD_SEALEVEL, &lev) == MHIP_OK, "ctx_sea_classes needs mhip_ctx_sea_flood on the resident DEM");
     MH_TRY(sea_levels_check(K, levels, c->sea_max_level));
     MH_HIP(hipSetDevice(c->device));
-    drop_sea_classes(c);
-    MH_TRY(c->sea_class.alloc(4 * (size_t)(c->H * c->W)));
-    MH_TRY(sea_classes_dev((const float *)lev, c->H * c->W, c->sea_nodata, K, levels, c->sea_class.as<int32_t>(), c->stream));
-    c->sea_class_held = 1;
+    DevBuf &out = held_begin(c, HP_SEACLASS).buf[0];
+    MH_TRY(out.alloc(4 * (size_t)(c->H * c->W)));
+    MH_TRY(sea_classes_dev((const float *)lev, c->H * c->W, c->sea_nodata, K, levels, out.as<int32_t>(), c->stream));
+    held_commit(c, HP_SEACLASS, 1);
     return MHIP_OK;
 }
 

@@ -3,6 +3,7 @@
 // mhip_ctx_run) and ctx_band.hip (the row-band protocol).
 //   ctx_wrote   ctx.hip   what a write of a resident raster invalidates: every writer calls it
 //   ctx_held    ctx.hip   whether a raster held outside mhip_raster is valid, and where it is: every reader calls it
+// What each held product is made from is held_rules.hpp; the context keeps one record per product, one lock and one drop (ctx.hip).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -11,6 +12,7 @@
 #include <thread>
 
 #include "common.hpp"
+#include "held_rules.hpp"
 
 namespace mh {
 
@@ -118,53 +120,26 @@ struct mhip_ctx {
     // hypsometry of the resident labels (mhip_ctx_hyps): layout, table, and the records of the last mhip_ctx_final_depths
     mh::DevBuf hyps_off, hyps_cnt, hyps_sum, hyps_rec;
     int64_t hyps_total = -1, hyps_spills = 0;     // -1: no table of the resident depths and labels
-    // the raster of the last mhip_ctx_wet_at (float32, H x W; not a member of mhip_raster) and its number of events; -1: none.  It
-    // lives and dies with the tables (drop_hyps)
-    mh::DevBuf wetat_out;
-    int wetat_events = -1;
-    // the raster (float32, H x W; not a member of mhip_raster) and the records of the last mhip_ctx_flow_distance, and its number of
-    // unresolved cells; -1: none.  They live and die with FLOWDIR and LABELS, which the two host threads of a request may write at
-    // the same time: the buffers are handed back under the lock
-    mh::DevBuf fdist_out, fdist_rec;
-    std::atomic<int64_t> fdist_unresolved{-1};
-    std::mutex fdist_mu;
-    // the raster (float32, H x W; no member of mhip_raster), the records and the time-area table (tt_bins bins a label; 0: none) of
-    // the last mhip_ctx_travel_time, its unresolved cells (-1: none) and the cells whose cost was clipped.  They live and die with
-    // FLOWDIR, LABELS, FILLED and ACCUM; handed back under the lock, as above
-    mh::DevBuf tt_out, tt_rec, tt_hist;
-    std::atomic<int64_t> tt_unresolved{-1};
+    // the held products (held_rules.hpp: what each is made from), indexed by mh::HeldProduct.  state: -1 none, >= 0 held -- the value
+    // mhip_ctx_get_i64 reports: the events of wet_at, the unresolved cells of the flow distance and the travel time, the undrained cells
+    // of hand, the reaches, the zones, the cells the sea reached, 1 for the inundation and the sea's depths and classes.  made_from: the
+    // rasters whose write drops it, set by the call that made it.  buf: its rasters (H x W, 4 bytes a cell; no members of
+    // mhip_raster), records and table, as ctx.hip's HELD table and the entry points name them.  The two host threads of a request may
+    // write rasters at the same time: every change of a state and every release happens under held_mu, and held_mask -- the union of
+    // the live products' made_from -- lets a write that meets none of them pass without the lock
+    struct Held {
+        std::atomic<int64_t> state{-1};
+        uint32_t made_from = 0;
+        mh::DevBuf buf[3];
+    } held[mh::HP_COUNT_];
+    std::mutex held_mu;
+    std::atomic<uint32_t> held_mask{0};
+    // what a later call needs from the one that made a product: the travel time's clipped cells and the bins of its table (0: no table);
+    // what mhip_ctx_inundate compares and uses of the hand and the reach catchments; the sea flood's max_level, nodata and counters
     int64_t tt_saturated = -1, tt_bins = 0;
-    std::mutex tt_mu;
-    // the two rasters (float32, H x W; no members of mhip_raster) of the last mhip_ctx_hand and its number of undrained cells; -1:
-    // none.  They live and die with FLOWDIR, ACCUM, the elevation raster `hand_src` and, where `hand_labels` says they were used,
-    // LABELS; handed back under the lock, as above
-    mh::DevBuf hand_out, hand_dist;
-    std::atomic<int64_t> hand_undrained{-1};
-    int hand_src = -1;
-    bool hand_labels = false;
-    double hand_thr = 0;          // the threshold and the nodata of that call: what mhip_ctx_inundate compares and uses
+    double hand_thr = 0, rcatch_thr = 0;
+    bool hand_labels = false, rcatch_labels = false;
     float hand_nodata = 0;
-    std::mutex hand_mu;
-    // the catchment raster (int32, H x W; no member of mhip_raster) of the last mhip_ctx_reach_catchments and its number of reaches;
-    // -1: none.  It lives and dies with FLOWDIR, ACCUM and, where `rcatch_labels` says they were used, LABELS.  The depth raster
-    // (float32, H x W) of the last mhip_ctx_inundate goes with the catchments, with the hand result, and with a new call of either;
-    // both are handed back under the lock, as above
-    mh::DevBuf rcatch_out, inund_out;
-    std::atomic<int64_t> rcatch_nreach{-1};
-    std::atomic<int> inund_held{-1};
-    double rcatch_thr = 0;
-    bool rcatch_labels = false;
-    std::mutex rcatch_mu;
-    // the zone raster (int32, H x W; not a member of mhip_raster) of the last mhip_ctx_rasterize_zones and its number of zones; -1:
-    // none.  It comes from outside: no write of a raster drops it
-    mh::DevBuf zones;
-    int64_t nzone = -1;
-    // the level raster (float32, H x W; no member of mhip_raster) of the last mhip_ctx_sea_flood, the cells it reached (-1: none), and
-    // the max_level, the nodata and the counters of that call; the depth raster (float32) of the last mhip_ctx_sea_depths and the
-    // class raster (int32) of the last mhip_ctx_sea_classes.  All three live and die with the DEM; a new sea_flood drops the other two
-    mh::DevBuf sea_level, sea_depth, sea_class;
-    int64_t sea_reached = -1;
-    int sea_depth_held = -1, sea_class_held = -1;
     float sea_max_level = 0, sea_nodata = 0;
     mh::SeaStats sea_st;
     double sh = 0, dg = 0;
@@ -185,6 +160,9 @@ struct mhip_ctx {
 };
 
 namespace mh {
+
+// no row band: no halo row, and not one of several ranks (a rank may own every row and still be one of several)
+inline bool undivided(const mhip_ctx *c) { return !(c->nranks > 1 || c->ht || c->hb); }
 
 inline size_t raster_elem(int which)
 {
@@ -273,9 +251,9 @@ inline int ctx_settle(mhip_ctx *c, int which, bool write)
 int ctx_copy_rows(mhip_ctx *c, void *dev_base, size_t elem_bytes, int64_t row0, int64_t nrows, void *host, hipMemcpyKind kind);
 // ---- the rasters a context holds outside mhip_raster, wherever they are read (ctx.hip) ------------------------------------------
 // wet_at, flow distance, hand and the distance to the drainage, reach catchments, inundation depths, zones, travel time, the sea flood's
-// levels, depths and classes: each lives behind a
-// sentinel of its own, which the drop_* functions of ctx.hip clear.  ctx_held is the one test "is it held, and where": MHIP_EINVAL
-// with the message of that raster's mhip_ctx_*_rows getter, or the device pointer and (optional) the bytes of an element.
+// levels, depths and classes: each is a buffer of a held product (mhip_ctx::held), valid while the product's state says so.  ctx_held
+// is the one test "is it held, and where": MHIP_EINVAL with the message of that raster's mhip_ctx_*_rows getter, or the device
+// pointer and (optional) the bytes of an element.
 enum HeldRaster { HELD_WETAT, HELD_FLOWDIST, HELD_HAND, HELD_DRAINDIST, HELD_REACHCATCH, HELD_INUNDATION, HELD_ZONES, HELD_TRAVELTIME, HELD_SEALEVEL, HELD_SEADEPTH,
                   HELD_SEACLASS, HELD_COUNT_ };
 int ctx_held(mhip_ctx *c, int id, void **ptr, size_t *elem_bytes = nullptr);

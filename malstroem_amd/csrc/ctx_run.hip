@@ -330,7 +330,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     MH_ARG(c, "ctx");
     MH_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (c->nranks > 1 || c->ht || c->hb) {
+    if (!undivided(c)) {
         // row-band mode: the fills run through mhip_ctx_fill_begin/batch (halo refreshes in between); stages whose
         // cross-band protocol is not built yet are refused instead of silently computing band-local results
         MH_ARG((mask & ~(MHIP_STAGE_FLOWDIR | MHIP_STAGE_ACCUM)) == 0,
@@ -347,7 +347,7 @@ extern "C" int mhip_ctx_run(mhip_ctx *c, int mask)
     // own last pass.
     FillHandover handover;
     FillHandover *const ho =
-        ((mask & MHIP_STAGE_FILL) && (mask & MHIP_STAGE_NOFLAT) && c->nranks == 1 && !c->ht && !c->hb && fill_handover_env()) ? &handover : nullptr;
+        ((mask & MHIP_STAGE_FILL) && (mask & MHIP_STAGE_NOFLAT) && undivided(c) && fill_handover_env()) ? &handover : nullptr;
     c->fill_handover = 0;
     // the wet bits of the hand-over (handover_addr.hpp): a buffer of this request -- from the pool, back with the request; the stages
     // that may read them run on this context, in this call, behind the visit that writes them

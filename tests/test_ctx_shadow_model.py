@@ -138,9 +138,9 @@ def test_two_contexts_take_the_same_sequence_at_the_second_shape():
 
 def test_a_context_that_lacks_a_rule_would_be_noticed(capsys):
     """two shadows side by side, one without one rule of the table: some sequence must see the difference, at the points where the
-    GPU test looks.  The two rules named here are the ones whose `drop_*` call a reviewer deletes from csrc/ctx.hip to see the GPU test
-    fail (ctx_wrote's FLOWDIR case: drop_flow_distance; drop_hand: drop_inundation): each is noticed by a directed and by a random
-    sequence."""
+    GPU test looks.  The two rules named here are the two table entries a reviewer deletes from csrc/held_rules.hpp to see the GPU
+    test fail (held_made_from: FLOWDIST's FLOWDIR bit; held_goes_with: INUNDATION goes with HAND): each is noticed by a directed and
+    by a random sequence."""
     random = [S.sequence(seed) for seed in S.SEEDS]
     short = [ops for name, (doc, ops) in sorted(DIRECTED.items()) if name[0] != "b"]
     full = [ops for name, (doc, ops) in sorted(DIRECTED.items()) if name[0] == "b"]

@@ -215,3 +215,57 @@ def test_stage_timers_start_out_unset(A):
         p.hypsometry(RES)
         ms, launches = p.kernel_ms("hyps_table")
         assert math.isfinite(ms) and ms >= 0 and launches == 1
+
+
+# every raster a context holds outside RASTERS: the key that reports it, its row getter, its name as a source of zone_stats (None: no
+# source), and what the getter and the source say while none is held -- the getters that ask the key first answer from Python
+# (pipeline.py), the others and every source with the message of the library's table (csrc/ctx.hip: HELD)
+HELD = (
+    ("wet_at_events", "download_wet_at_rows", "wet_at", "ctx_wet_at_rows needs mhip_ctx_wet_at on the resident depths and labels", None),
+    ("flow_distance_unresolved", "download_flow_distance_rows", "flow_distance",
+     "ctx_flow_distance_rows needs mhip_ctx_flow_distance on the resident flow directions and labels", None),
+    ("travel_time_unresolved", "download_travel_time_rows", "travel_time", "ctx_travel_time_rows needs mhip_ctx_travel_time on the resident rasters", None),
+    ("hand_undrained", "download_hand_rows", "hand", "ctx_hand_rows needs mhip_ctx_hand on the resident rasters", r"hand\(\) has not been run on the resident rasters"),
+    ("hand_undrained", "download_drain_distance_rows", "drain_distance", "ctx_hand_rows needs mhip_ctx_hand on the resident rasters",
+     r"hand\(\) has not been run on the resident rasters"),
+    ("reach_catchments", "download_reach_catchments_rows", None, "ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters",
+     r"reach_catchments\(\) has not been run on the resident rasters"),
+    ("inundation", "download_inundation_rows", "inundation", "ctx_inundation_rows needs mhip_ctx_inundate on the held hand and reach catchments",
+     r"inundate\(\) has not been run on the held hand and reach catchments"),
+    ("zones", "download_zones_rows", None, "ctx_zones_rows needs mhip_ctx_rasterize_zones", None),
+    ("sea_flood", "download_sea_level_rows", "sea_level", "ctx_sea_flood_rows needs mhip_ctx_sea_flood on the resident DEM",
+     r"sea_flood\(\) has not been run on the resident DEM"),
+    ("sea_depths", "download_sea_depths_rows", "sea_depths", "ctx_sea_flood_rows needs mhip_ctx_sea_depths on the held sea levels",
+     r"sea_depths\(\) has not been run on the held sea levels"),
+    ("sea_classes", "download_sea_classes_rows", None, "ctx_sea_classes_rows needs mhip_ctx_sea_classes on the held sea levels",
+     r"sea_classes\(\) has not been run on the held sea levels"),
+)
+
+
+def test_a_fresh_context_holds_nothing_and_every_reader_of_a_held_raster_says_so():
+    from malstroem_amd.pipeline import HydroPipeline
+    with HydroPipeline((16, 16)) as p:
+        p.upload("dem", fbm(16, 16, beta=2.0, seed=3))
+        for key in [h[0] for h in HELD] + ["travel_time_saturated", "travel_time_bins"]:
+            assert p.get_int(key) == -1, key
+        for key, getter, source, library, python in HELD:
+            with pytest.raises(ValueError, match=python or library):
+                getattr(p, getter)(0, 16)
+        assert {h[2] for h in HELD if h[2]} == set(p.ZONE_SOURCES) - {"dem", "filled", "depths", "finaldepths"}
+        for source in p.ZONE_SOURCES:
+            with pytest.raises(ValueError, match=r"rasterize_zones\(\) has not been run"):
+                p.zone_stats(source)
+        with pytest.raises(ValueError, match="ctx_reach_catchments_rows needs mhip_ctx_reach_catchments on the resident rasters"):
+            p.polygonize("reach_catchments")
+        with pytest.raises(ValueError, match="ctx_sea_classes_rows needs mhip_ctx_sea_classes on the held sea levels"):
+            p.polygonize("sea_classes")
+        # with (empty) zones every held source gets as far as the library's table, and none of the other products has appeared
+        p.rasterize_zones(np.zeros((0, 2)), [0], np.zeros(0, dtype=np.int32), 3)
+        assert p.get_int("zones") == 3 and not p.download_zones_rows(0, 16).any()
+        for key, getter, source, library, python in HELD:
+            if source:
+                with pytest.raises(ValueError, match=library):
+                    p.zone_stats(source)
+            if key != "zones":
+                assert p.get_int(key) == -1, key
+        assert p.zone_stats("dem").shape == (4,)
