@@ -756,6 +756,33 @@ int mhip_ctx_sea_depths(mhip_ctx *ctx, float z);
 int mhip_ctx_sea_classes(mhip_ctx *ctx, int32_t K, const float *levels);
 int mhip_ctx_sea_classes_rows(mhip_ctx *ctx, int64_t row0, int64_t nrows, int32_t *dst);
 
+/* Runoff-weighted flow accumulation (ours; the definition is tests/_wacc.py).  flowdir[H][W] uint8 AGNPS codes 0..7 (a
+ * code > 7: no direction), weight[H][W] uint32 (any value; 1000000 is a cell that sends all of its rain downstream).
+ * out[c] = weight[c] + the sum of out[n] over the neighbours n inside the raster whose direction points at c, in uint64: exact, the
+ * same bits in every summation order.  A cell without a direction receives and does not forward, a cell whose step leaves the raster
+ * keeps its sum.  A cell on a flow cycle has no answer: it holds MHIP_WACC_UNRESOLVED (0 is a legal sum), and *unresolved counts these
+ * cells -- the cells mhip_accum leaves 0.  With zones[H][W] int32 (values in [0, nzone], anything else is MHIP_EINVAL):
+ * zone_sums[l] = the sum of weight over the cells with zones == l, uint64 [nzone + 1]; it depends on neither the directions nor the
+ * resolution.  MHIP_EINVAL: H or W < 1; MHIP_ELIMIT: 2**31 cells or more (a resolved sum stays below 2**63).
+ * On a context: weight is a host raster of the context's shape, the directions are the resident MHIP_R_FLOWDIR of an undivided
+ * context (a row band is refused), with use_watersheds the zones are the resident MHIP_R_WATERSHEDS and nzone the context's number of
+ * labels; a raster that is not valid is MHIP_EINVAL.  The result is a snapshot behind an opaque handle, in device buffers of its own,
+ * as mhip_polygons: it is no held product of the context, never goes stale, outlives the context and every later run, and is freed on
+ * its own.  wacc_info: nzone is -1 for a result without zone sums.  wacc_rows_u64 copies rows [row0, row0 + nrows) as they are;
+ * wacc_rows_f64 gives (float64(sum) / div) * mul, each operation rounded on its own, and nodata where the cell is unresolved (div
+ * must not be 0 or NaN).  wacc_zone_sums copies the nzone + 1 sums (MHIP_EINVAL without them). */
+#define MHIP_WACC_UNRESOLVED 0xffffffffffffffffULL
+#define MHIP_WACC_UNIT 1000000u
+typedef struct mhip_wacc mhip_wacc;
+int mhip_weighted_accum_u32(const uint8_t *flowdir, const uint32_t *weight, const int32_t *zones_or_NULL, int64_t H, int64_t W, int64_t nzone,
+                            uint64_t *out, uint64_t *zone_sums_or_NULL, int64_t *unresolved);
+int mhip_ctx_weighted_accum(mhip_ctx *ctx, const uint32_t *weight, int32_t use_watersheds, mhip_wacc **out);
+int mhip_wacc_info(const mhip_wacc *h, int64_t *H, int64_t *W, int64_t *nzone, int64_t *unresolved);
+int mhip_wacc_rows_u64(const mhip_wacc *h, int64_t row0, int64_t nrows, uint64_t *dst);
+int mhip_wacc_rows_f64(const mhip_wacc *h, int64_t row0, int64_t nrows, double div, double mul, double nodata, double *dst);
+int mhip_wacc_zone_sums(const mhip_wacc *h, uint64_t *dst);
+void mhip_wacc_free(mhip_wacc *h);
+
 #ifdef __cplusplus
 }
 #endif

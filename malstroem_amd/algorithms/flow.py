@@ -280,6 +280,31 @@ def hand(flowdir, accum, elev, threshold, labelled=None, cellsize=1.0, nodata=-9
     return (out, dist, undrained.value) if distance else out
 
 
+WACC_UNRESOLVED = np.uint64(2 ** 64 - 1)     # MHIP_WACC_UNRESOLVED: a cell on a flow cycle
+
+
+def weighted_accumulation(flowdir, weight, labelled=None):
+    """The accumulation of ``weight`` (uint32; ``runoff.UNIT`` is a cell that sends all of its rain downstream) down the flow
+    directions, in exact uint64 sums: per cell its own weight plus that of every cell upstream.  A cell on a flow cycle -- where
+    ``accumulated_flow`` leaves its 0 -- holds ``WACC_UNRESOLVED``.  With ``labelled`` (int32, no negative value):
+    ``(wacc, sums)``, ``sums[l]`` the sum of ``weight`` over the cells with label ``l`` (uint64, ``labelled.max() + 1`` entries).
+    No reference counterpart (the definition is ``tests/_wacc.py``)."""
+    fd = _flowdir(flowdir)
+    w = _like("weight", weight, fd.shape, np.uint32)
+    lab = _like("labelled", labelled, fd.shape, np.int32) if labelled is not None else None
+    nzone = 0
+    if lab is not None:
+        if lab.size and int(lab.min()) < 0:
+            raise ValueError("labelled must not hold a negative value")
+        nzone = int(lab.max()) if lab.size else 0
+    out = np.empty(fd.shape, dtype=np.uint64)
+    sums = np.zeros(nzone + 1, dtype=np.uint64) if lab is not None else None
+    unresolved = ctypes.c_int64(0)
+    _lib.call("mhip_weighted_accum_u32", _lib.ptr(fd), _lib.ptr(w), _lib.ptr(lab) if lab is not None else None, _lib.i64(fd.shape[0]),
+              _lib.i64(fd.shape[1]), _lib.i64(nzone), _lib.ptr(out), _lib.ptr(sums) if lab is not None else None, ctypes.byref(unresolved))
+    return (out, sums) if lab is not None else out
+
+
 # ---- per-cell host helpers (reference flow.py:170-301), used by stream tracing and tests --------------
 
 def direction_to_delta(direction):

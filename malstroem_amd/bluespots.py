@@ -125,6 +125,12 @@ class BluespotTool(object):
     the ``reach_id`` that ``features_from_reaches`` gives its reach.  They use ``flowpaths_threshold`` and
     ``flowpaths_stop_at_bluespots``; when either is set, the ``flowpaths`` layer comes from the same call and its features gain
     ``local_cells`` / ``local_area``.  The catchments stay on the pipeline for ``HydroPipeline.inundate``.
+
+    ``runoff_weight`` (no reference counterpart): a uint32 raster of runoff weights (``runoff.weights``).  Every pour
+    point then also carries ``wshed_eff_area``, the runoff-weighted area of the bluespot's local watershed in square metres
+    (``runoff.effective_area`` of the weights' sum over it; with weights of ``runoff.UNIT`` it is ``wshed_area`` bit for bit), and
+    ``output_runoff_accum_raster``, a raster writer, receives the effective upstream area of every cell in square metres (float64,
+    -1 on a flow cycle), streamed in row windows.  Without the weights the layer is unchanged.
     """
 
     def __init__(self, input_depths, input_flowdir, input_bluespot_filter_function,
@@ -133,7 +139,8 @@ class BluespotTool(object):
                  pipeline=None, device=0, output_flowlength_raster=None, output_flowpaths=None, flowpaths_threshold=None,
                  flowpaths_stop_at_bluespots=True, flowpaths_run_accum=False, output_hand_raster=None, output_drain_distance_raster=None,
                  hand_threshold=None, hand_run_accum=False, output_reach_catchments_raster=None, output_reach_catchments_vector=None,
-                 output_traveltime_raster=None, traveltime=None, traveltime_run_accum=False):
+                 output_traveltime_raster=None, traveltime=None, traveltime_run_accum=False, runoff_weight=None,
+                 output_runoff_accum_raster=None):
         self.input_depths = input_depths
         self.input_flowdir = input_flowdir
         self.input_bluespot_filter_function = input_bluespot_filter_function
@@ -172,6 +179,10 @@ class BluespotTool(object):
             check_bins(self.traveltime.get("bins"), float(p["tick"][0]))
             self.traveltime_classes = bool(np.isfinite(p["channel_threshold"][0]))
             assert self.input_dem or pipeline, "The travel time needs input_dem"
+        self.runoff_weight = runoff_weight
+        self.output_runoff_accum_raster = output_runoff_accum_raster
+        if output_runoff_accum_raster is not None and runoff_weight is None:
+            raise ValueError("output_runoff_accum_raster needs runoff_weight")
         assert self.input_accum or self.input_dem or pipeline, "Either input_dem or input_accum must be specified"
         self.logger = logging.getLogger(__name__)
 
@@ -224,6 +235,16 @@ class BluespotTool(object):
             pp_pix = pipe.pourpoints()
             self.logger.info("Writing {} pour points".format(len(pp_pix)))
             pour_points = assemble_pourpoints(transform, pp_pix, bluespot_stats, watershed_stats)
+            if self.runoff_weight is not None:
+                from .runoff import UNIT, effective_area
+                self.logger.info("Calculating the runoff-weighted accumulation")
+                with pipe.weighted_accumulation(self.runoff_weight) as wacc:
+                    if wacc.unresolved:
+                        self.logger.warning("{} cells lie on a flow cycle: no weighted accumulation".format(wacc.unresolved))
+                    for feature, area in zip(pour_points, effective_area(wacc.sums(), cell_area)):
+                        feature['properties']['wshed_eff_area'] = float(area)
+                    if self.output_runoff_accum_raster is not None:
+                        wacc.download_to(self.output_runoff_accum_raster, div=UNIT, mul=cell_area, nodata=-1.0)
             if self.output_flowlength_raster:
                 self.logger.info("Calculating flow lengths")
                 unresolved = pipe.flow_distance(cell_width)

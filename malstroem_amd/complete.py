@@ -90,7 +90,7 @@ def parse_filter(filter):
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
                 finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
                 flowpaths=None, flowpaths_stop_at_bluespots=True, hand=None, reach_catchments=False, inundation=None,
-                traveltime=False, sea=None, adaptations=None):
+                traveltime=False, runoff=None, sea=None, adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -174,7 +174,24 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     ``objects`` every object gets ``sea_level_min``, the lowest level that wets one of its cells (null: none does;
     ``coastal.object_level_min`` says why it is ``vmin_pos``), which needs every stage > 0.  The dict gains ``sea_level``,
     ``sea_depths``, ``sea_levels`` and ``sea_extents``.  Every other output is what it is without the argument.  Not on row bands
-    yet."""
+    yet.
+
+    ``runoff`` (keyword only): a dict ``{"coefficient": ..., "pattern": ..., "raster": bool}`` -- rain that does not run off
+    everywhere alike (``runoff.py``; DESIGN.md 20).  ``coefficient``: the share of the rain a cell sheds (1: impermeable ground);
+    ``pattern``: the depth of the rain on a cell relative to the event's nominal millimetres.  Each is the path of a GeoTIFF on the
+    DEM's grid, an array of the DEM's shape (anything else is a ``ValueError``) or ``None`` for 1; a NaN or nodata cell sheds
+    nothing.  The pour points and the nodes then carry ``wshed_eff_area``, the runoff-weighted area of the local watershed in square
+    metres, and the rain events -- with everything derived from their volumes, ``finalstate`` and ``onset`` -- use it in place
+    of ``wshed_area``.  With ``raster`` also writes ``runoff_accum.tif`` (float64, nodata -1): the effective upstream area of every
+    cell in square metres; the dict gains ``runoff_accum``.  With a coefficient of 1 everywhere every other output is what it is
+    without the argument.  Not on row bands yet."""
+    runoff_weight = None
+    if runoff is not None:
+        if not isinstance(runoff, dict) or set(runoff) - {"coefficient", "pattern", "raster"}:
+            raise ValueError('runoff must be a dict {"coefficient": ..., "pattern": ..., "raster": bool}, got %r' % (runoff,))
+        if comm is not None and comm.size > 1:
+            raise NotImplementedError("runoff on row bands: a flow path crosses the seams between the bands, and the weighted "
+                                      "accumulation over them is not built yet; run it on one context")
     sea_depth_levels = []
     if sea is not None:
         from .algorithms.fill import check_sea_levels
@@ -269,6 +286,28 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     filter_function = parse_filter(filter)
     dem_reader = io.RasterReader(dem, nodatasubst=nodatasubst)
     tr, crs = dem_reader.transform, dem_reader.crs
+    if runoff is not None:
+        from .runoff import weights
+        parts = {}
+        for key in ("coefficient", "pattern"):
+            a, nodata = runoff.get(key), None
+            if isinstance(a, (str, bytes, os.PathLike)):
+                reader = io.RasterReader(a)
+                a, nodata = reader.read(), reader.nodata
+                reader.close()
+            if a is not None:
+                a = np.asarray(a, dtype=np.float64)
+                if a.shape != tuple(dem_reader.shape):
+                    dem_reader.close()
+                    raise ValueError("runoff: %s is %s, the DEM is %s" % (key, a.shape, tuple(dem_reader.shape)))
+                if nodata is not None:
+                    a = np.where(a == np.float64(nodata), np.nan, a)      # (each file has a nodata of its own)
+            parts[key] = a
+        try:
+            runoff_weight = np.broadcast_to(weights(parts["coefficient"], parts["pattern"]), dem_reader.shape).copy()
+        except ValueError:
+            dem_reader.close()
+            raise
     logger.info('Processing')
     logger.info('   dem: {}'.format(dem))
     logger.info('   outdir: {}'.format(outdir))
@@ -300,6 +339,7 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         flowpaths_writer = io.VectorWriter('GeoJSON', outvector, 'flowpaths', None, None, crs) if flowpaths is not None else None
         hand_path, hand_dist_path = os.path.join(outdir, 'hand.tif'), os.path.join(outdir, 'hand_dist.tif')
         catch_path = os.path.join(outdir, 'reach_catchments.tif')
+        runoff_accum_path, runoff_raster = os.path.join(outdir, 'runoff_accum.tif'), bool(runoff is not None and runoff.get("raster"))
         catch_vector_writer = io.VectorWriter('GeoJSON', outvector, 'reach_catchments', None, None, crs) if reach_catchments and vector else None
         BluespotTool(input_depths=dem_reader, input_flowdir=dem_reader, input_bluespot_filter_function=filter_function,
                      input_accum=None, input_dem=dem_reader, output_labeled_raster=labeled_writer, output_pourpoints=pourpoint_writer,
@@ -314,7 +354,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                      output_reach_catchments_raster=io.RasterWriter(catch_path, tr, crs, 0) if reach_catchments else None,
                      output_reach_catchments_vector=catch_vector_writer,
                      output_traveltime_raster=io.RasterWriter(traveltime_path, tr, crs, -1) if traveltime is not None else None,
-                     traveltime=traveltime, traveltime_run_accum=not accum).process()
+                     traveltime=traveltime, traveltime_run_accum=not accum, runoff_weight=runoff_weight,
+                     output_runoff_accum_raster=io.RasterWriter(runoff_accum_path, tr, crs, -1) if runoff_raster else None).process()
         inundation_paths = {}
         if stages:
             # (the heights and the catchments are resident, made with one threshold at the bluespots: nothing has been written since)
@@ -370,9 +411,11 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         # Process rain events
         nodes_reader = io.VectorReader(outvector, nodes_writer.layername)
         events_writer = io.VectorWriter('GeoJSON', outvector, 'events', None, None, crs)
-        RainTool(nodes_reader, events_writer, rain).process()
+        RainTool(nodes_reader, events_writer, rain, area_key="wshed_eff_area" if runoff is not None else "wshed_area").process()
         res = dict(outdir=outdir, vector=outvector, nlabels=nlabels, events=events_writer.filepath,
                    nodes=nodes_writer.filepath, streams=streams_writer.filepath, pourpoints=pourpoint_writer.filepath)
+        if runoff_raster:
+            res["runoff_accum"] = runoff_accum_path
         if vector:
             res.update(bluespots_vector=labeled_vector_writer.filepath, watersheds_vector=watershed_vector_writer.filepath)
         if flowlength:

@@ -691,4 +691,72 @@ int mhip_trace_downstream_i32(const uint8_t *flowdir, const int32_t *labels, int
                            offsets, out_cells, s);
 }
 
+/* ---- runoff-weighted flow accumulation (wacc.hip): the stand-alone call and the readers of a context's snapshot ------------------- */
+int mhip_weighted_accum_u32(const uint8_t *flowdir, const uint32_t *weight, const int32_t *zones, int64_t H, int64_t W, int64_t nzone, uint64_t *out,
+                            uint64_t *zone_sums, int64_t *unresolved)
+{
+    MH_ARG(flowdir && weight && out && unresolved && (zones != nullptr) == (zone_sums != nullptr),
+           "weighted_accum_u32(flowdir, weight, zones, H, W, nzone, out, zone_sums, unresolved): zones and zone_sums go together");
+    MH_TRY(wacc_check(H, W, nzone, zones != nullptr));
+    MH_TRY(require_device());
+    const size_t n = (size_t)(H * W);
+    hipStream_t s = 0;
+    DevBuf d_fd, d_w, d_z, d_out, d_sums;
+    MH_TRY(upload(d_fd, flowdir, n, s));
+    MH_TRY(upload(d_w, weight, 4 * n, s));
+    if (zones) {
+        MH_TRY(upload(d_z, zones, 4 * n, s));
+        MH_TRY(d_sums.alloc(8 * (size_t)(nzone + 1)));
+    }
+    MH_TRY(d_out.alloc(8 * n));
+    MH_TRY(wacc_dev(d_fd.as<uint8_t>(), d_w.as<uint32_t>(), zones ? d_z.as<int32_t>() : nullptr, H, W, nzone, d_out.as<unsigned long long>(),
+                    zones ? d_sums.as<unsigned long long>() : nullptr, unresolved, s));
+    if (zones) MH_HIP(hipMemcpyAsync(zone_sums, d_sums.p, 8 * (size_t)(nzone + 1), hipMemcpyDeviceToHost, s));
+    return download(out, d_out, 8 * n, s);
+}
+
+int mhip_wacc_info(const mhip_wacc *p, int64_t *H, int64_t *W, int64_t *nzone, int64_t *unresolved)
+{
+    MH_ARG(p && H && W && nzone && unresolved, "wacc_info(wacc, H, W, nzone, unresolved)");
+    *H = p->H;
+    *W = p->W;
+    *nzone = p->nzone;
+    *unresolved = p->unresolved;
+    return MHIP_OK;
+}
+
+int mhip_wacc_rows_u64(const mhip_wacc *p, int64_t row0, int64_t nrows, uint64_t *dst)
+{
+    MH_ARG(p && dst && row0 >= 0 && nrows >= 1 && row0 <= p->H - nrows, "wacc_rows_u64(wacc, row0, nrows, dst): rows inside the raster");
+    MH_HIP(hipSetDevice(p->device));
+    hipStream_t s = 0;      // (raw rows: a copy, no kernel)
+    MH_HIP(hipMemcpyAsync(dst, p->acc.as<uint64_t>() + row0 * p->W, 8 * (size_t)(nrows * p->W), hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
+int mhip_wacc_rows_f64(const mhip_wacc *p, int64_t row0, int64_t nrows, double div, double mul, double nodata, double *dst)
+{
+    MH_ARG(p && dst && row0 >= 0 && nrows >= 1 && row0 <= p->H - nrows, "wacc_rows_f64(wacc, row0, nrows, div, mul, nodata, dst): rows inside the raster");
+    MH_ARG(div != 0.0 && div == div, "wacc_rows_f64: div must not be 0 or NaN");
+    return wacc_rows_f64_dev(p, row0, nrows, div, mul, nodata, dst);
+}
+
+int mhip_wacc_zone_sums(const mhip_wacc *p, uint64_t *dst)
+{
+    MH_ARG(p && dst, "wacc_zone_sums(wacc, dst)");
+    MH_ARG(p->nzone >= 0, "wacc_zone_sums: the result was made without zones");
+    MH_HIP(hipSetDevice(p->device));
+    hipStream_t s = 0;
+    MH_HIP(hipMemcpyAsync(dst, p->sums.p, 8 * (size_t)(p->nzone + 1), hipMemcpyDeviceToHost, s));
+    MH_HIP(stream_sync(s));
+    return MHIP_OK;
+}
+
+void mhip_wacc_free(mhip_wacc *p)
+{
+    if (p && p->device >= 0) (void)hipSetDevice(p->device);
+    delete p;
+}
+
 }  // extern "C"

@@ -11,6 +11,7 @@
 
 struct mhip_polygons;
 struct mhip_flowpaths;
+struct mhip_wacc;
 
 namespace mh {
 
@@ -783,3 +784,21 @@ struct mhip_flowpaths {     // a result of mhip_flowpaths_f64 / mhip_ctx_flowpat
     int64_t nreach = 0, nvert = 0, unresolved = 0;
     int device = -1;
 };
+
+struct mhip_wacc {          // a result of mhip_ctx_weighted_accum: a snapshot in buffers of its own on `device`
+    mh::DevBuf acc, sums;                         // uint64 [H][W]; uint64 [nzone + 1] (none without zones: nzone == -1)
+    int64_t H = 0, W = 0, nzone = -1, unresolved = 0;
+    int device = -1;
+};
+
+namespace mh {
+// wacc.hip: the accumulation of a uint32 weight down the D8 forest in exact uint64 sums, and the weight's sums per label (DESIGN.md
+// 20; the definition is tests/_wacc.py).  wacc_check: the argument rules on the shape (MHIP_EINVAL, MHIP_ELIMIT; no device work).
+// wacc_dev: d_out (uint64, H x W) and the number of unresolved cells; with d_zones (labels in [0, nzone]) also d_sums (uint64,
+// nzone + 1).  Synchronises.  MHIP_EINVAL: a label outside [0, nzone].  wacc_rows_f64_dev: rows of a handle as
+// (float64(sum) / div) * mul, `nodata` where the cell is unresolved, into the caller's array.
+int wacc_check(int64_t H, int64_t W, int64_t nzone, bool zones);
+int wacc_dev(const uint8_t *d_fd, const uint32_t *d_w, const int32_t *d_zones, int64_t H, int64_t W, int64_t nzone, unsigned long long *d_out,
+             unsigned long long *d_sums, int64_t *unresolved, hipStream_t s);
+int wacc_rows_f64_dev(const mhip_wacc *p, int64_t row0, int64_t nrows, double div, double mul, double nodata, double *dst);
+}  // namespace mh

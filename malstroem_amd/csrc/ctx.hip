@@ -946,6 +946,43 @@ int mhip_ctx_flowpaths(mhip_ctx *c, double threshold, int32_t stop_at_labels, mh
     return MHIP_OK;
 }
 
+/* ---- runoff-weighted accumulation down the resident flow directions (wacc.hip): a snapshot in buffers of the handle, no held product */
+int mhip_ctx_weighted_accum(mhip_ctx *c, const uint32_t *weight, int32_t use_watersheds, mhip_wacc **out)
+{
+    MH_ARG(c && weight && out, "ctx_weighted_accum(ctx, weight, use_watersheds, out)");
+    MH_ARG(undivided(c), "weighted accumulation on a row band is not built (a path crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_FLOWDIR], "ctx_weighted_accum needs the FLOWDIR raster");
+    if (use_watersheds) MH_ARG(c->have[MHIP_R_WATERSHEDS] && c->nlabels >= 0, "ctx_weighted_accum with use_watersheds needs the WATERSHEDS raster and its labels");
+    MH_TRY(wacc_check(c->H, c->W, c->nlabels, use_watersheds != 0));
+    MH_HIP(hipSetDevice(c->device));
+    mhip_wacc *p = new (std::nothrow) mhip_wacc();
+    if (!p) {
+        set_error("ctx_weighted_accum: out of host memory");
+        return MHIP_EHIP;
+    }
+    p->device = c->device;
+    p->H = c->H;
+    p->W = c->W;
+    p->nzone = use_watersheds ? c->nlabels : -1;
+    const size_t n = (size_t)(c->H * c->W);
+    DevBuf d_w;
+    int rc = upload(d_w, weight, 4 * n, c->stream);
+    if (rc == MHIP_OK) rc = p->acc.alloc(8 * n);
+    if (rc == MHIP_OK && use_watersheds) rc = p->sums.alloc(8 * (size_t)(c->nlabels + 1));
+    if (rc == MHIP_OK)
+        rc = wacc_dev(c->r[MHIP_R_FLOWDIR].as<uint8_t>(), d_w.as<uint32_t>(), use_watersheds ? c->r[MHIP_R_WATERSHEDS].as<int32_t>() : nullptr, c->H, c->W,
+                      c->nlabels, p->acc.as<unsigned long long>(), use_watersheds ? p->sums.as<unsigned long long>() : nullptr, &p->unresolved,
+                      c->stream);      // (synchronises)
+    else
+        (void)stream_sync(c->stream);  // (the upload may still read the caller's array)
+    if (rc != MHIP_OK) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return MHIP_OK;
+}
+
 /* ---- reach catchments and flood depths from a stage per reach (hand.hip, flowpaths.hip, reachcatch.hip) ---------------------------- */
 int mhip_ctx_reach_catchments(mhip_ctx *c, double threshold, int32_t stop_at_labels, mhip_flowpaths **out, int64_t *assigned)
 {

@@ -33,9 +33,11 @@ class Network(object):
         if downstream_id is None:
             self.root_nodes.append(node_id)
 
-    def rain_events(self, events_mm):
+    def rain_events(self, events_mm, area_key="wshed_area"):
         """Every event of ``events_mm`` in one pass -> list (per event) of lists of event dicts
-        ``{nodeid, rainv, spillv, v, pctv}`` in the reference's order (network.py:115-129)."""
+        ``{nodeid, rainv, spillv, v, pctv}`` in the reference's order (network.py:115-129).  ``area_key``: the node property that
+        is the area the rain falls on -- ``wshed_eff_area`` for the runoff-weighted area of ``runoff.py``; the default is the
+        reference's."""
         events = np.ascontiguousarray(np.asarray(list(events_mm), dtype=np.float64))
         n = len(self.nodes)
         # the LAST node added under an id is the one the reference evaluates (nodes_index keeps the last), but every add
@@ -45,7 +47,7 @@ class Network(object):
         for i, node in enumerate(self.nodes):
             d = node['dstrnodeid']
             down[i] = -1 if d is None else pos.get(d, -2)
-        area = np.array([float(node['wshed_area']) for node in self.nodes], dtype=np.float64)
+        area = np.array([float(node[area_key]) for node in self.nodes], dtype=np.float64)
         vol = np.array([float(node['bspot_vol']) for node in self.nodes], dtype=np.float64)
         ne = len(events)
         out = [np.zeros((ne, n), dtype=np.float64) for _ in range(4)]
@@ -64,6 +66,6 @@ class Network(object):
             results.append(ev)
         return results
 
-    def rain_event(self, mmrain):
+    def rain_event(self, mmrain, area_key="wshed_area"):
         """All nodes below a root with the event's values added (network.py:115-129)."""
-        return self.rain_events([mmrain])[0]
+        return self.rain_events([mmrain], area_key)[0]

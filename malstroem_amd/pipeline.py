@@ -404,6 +404,18 @@ class HydroPipeline(CtxHandle):
         _lib.call("mhip_ctx_flowpaths", self._ctx, ctypes.c_double(thr), ctypes.c_int32(1 if stop_at_bluespots else 0), ctypes.byref(handle))
         return take_flowpaths(handle)
 
+    # ---- runoff-weighted accumulation down the resident flow directions (runoff.py) ------------------------
+    def weighted_accumulation(self, weight, by_watersheds=True):
+        """The accumulation of ``weight`` (uint32 raster of the pipeline's shape; ``runoff.weights``) down the resident flow
+        directions in exact uint64 sums, and with ``by_watersheds`` its sums over the resident watersheds, as a
+        ``runoff.WeightedAccum``: a snapshot on the device in buffers of its own, which no later upload or run changes and which
+        outlives the pipeline.  ``algorithms.flow.weighted_accumulation`` gives the same bits for the downloaded rasters."""
+        from .runoff import WeightedAccum, check_weight
+        w = check_weight(weight, self.shape)
+        handle = ctypes.c_void_p()
+        _lib.call("mhip_ctx_weighted_accum", self._ctx, _lib.ptr(w), ctypes.c_int32(1 if by_watersheds else 0), ctypes.byref(handle))
+        return WeightedAccum(handle)
+
     # ---- reach catchments and flood depths from a stage per reach (flowpaths.py; DESIGN.md 17) ---------------------------
     def reach_catchments(self, threshold, stop_at_bluespots=True):
         """``(xy, reach_offsets, records, unresolved, assigned)``: the reaches of ``flow_paths`` with the same arguments and, in a

@@ -10,8 +10,9 @@ from .network import Network
 
 
 class RainTool(object):
-    def __init__(self, input_nodes, output_eventdata, events_rainmm):
+    def __init__(self, input_nodes, output_eventdata, events_rainmm, area_key="wshed_area"):
         self.input_nodes = input_nodes
+        self.area_key = area_key      # the node property the rain falls on (``Network.rain_events``)
         self.output_eventdata = output_eventdata
         self.events_rainmm = list(events_rainmm)
         self.logger = logging.getLogger(__name__)
@@ -23,7 +24,7 @@ class RainTool(object):
         network = Network()
         network.add_nodes([f['properties'] for f in features.values()])
         self.logger.info("Calculating rain events")
-        for mmrain, eventvalues in zip(self.events_rainmm, network.rain_events(self.events_rainmm)):
+        for mmrain, eventvalues in zip(self.events_rainmm, network.rain_events(self.events_rainmm, self.area_key)):
             self.logger.info("  {}mm".format(mmrain))
             for e in eventvalues:
                 props = features[e['nodeid']]['properties']

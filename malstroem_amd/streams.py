@@ -45,6 +45,7 @@ def nodes_to_features(nodes, pourpoints, transform):
     """(node features, stream features) of the reference's StreamTool output (streams.py:77-124): a node carries the bluespot
     attributes of its pour point (defaults for a junction), a stream the path from the node to the next one downstream."""
     pp_index = {pp['properties']['bspot_id']: pp for pp in pourpoints}
+    weighted = any('wshed_eff_area' in pp['properties'] for pp in pourpoints)      # pour points of a run with runoff weights (runoff.py)
     geojson_nodes, streams = [], []
     for n in nodes:
         props = dict(nodeid=n['id'], dstrnodeid=n['downstream_id'], nodetype=n['nodetype'], cell_row=n['pix'][0], cell_col=n['pix'][1],
@@ -53,6 +54,8 @@ def nodes_to_features(nodes, pourpoints, transform):
         if ppoint:
             for key in ('bspot_id', 'bspot_area', 'bspot_vol', 'wshed_area'):
                 props[key] = ppoint['properties'][key]
+        if weighted:      # (a junction has no watershed of its own: 0, as its wshed_area)
+            props['wshed_eff_area'] = ppoint['properties']['wshed_eff_area'] if ppoint else 0.0
         coord = transform_cell_to_world(n['pix'], transform)
         geojson_nodes.append(dict(id=n['id'], geometry=dict(type='Point', coordinates=list(coord)), properties=props))
         if n.get('geometry'):
