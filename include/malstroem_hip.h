@@ -783,6 +783,34 @@ int mhip_wacc_rows_f64(const mhip_wacc *h, int64_t row0, int64_t nrows, double d
 int mhip_wacc_zone_sums(const mhip_wacc *h, uint64_t *dst);
 void mhip_wacc_free(mhip_wacc *h);
 
+/* Multiple-flow-direction accumulation (ours; the definition is tests/_mfd.py).  Two stateless functions that form a pair:
+ * anybody's fractions can be accumulated.
+ * mfd_fractions_f64: z[H][W] float64 -> out[H][W][8] uint16, the share of a cell's flow that goes to each neighbour (0 up, then clockwise)
+ * in units of 1 / MHIP_MFD_ONE.  Per interior cell with a finite z: the drops z - z_k, the diagonal ones times the constant of mhip_d8_f64;
+ * a drop that is not in (0, inf) -- a NaN or infinite neighbour, a neighbour that is not lower -- counts 0.  m is the first largest drop
+ * (the D8 choice), t_k = (drop_k / drop_m) multiplied by itself exponent - 1 times, T = ((t_0 + t_1) + ...) + t_7,
+ * q_k = floor(t_k / T * ONE), and q_m takes the remainder ONE - sum(q): the fractions sum to ONE.  Every float64 operation is rounded on
+ * its own.  A cell without a lower neighbour, a cell on the raster's border and a cell whose z is not finite has eight zeros.
+ * exponent in [1, 8] (MHIP_EINVAL otherwise): 1 spreads by slope, larger values approach D8.
+ * mfd_accum_u32: fractions[H][W][8] uint16 (a cell's eight must sum to 0 or to ONE: anything else is MHIP_EINVAL), weight[H][W] uint32
+ * -> out[H][W] uint64.  out[c] = weight[c] + what the neighbours send it.  A cell sends once, when every neighbour with a positive
+ * fraction towards it has sent: (out[c] * p_k) >> 15 to neighbour k for k != m, m the first largest p_k, and out[c] minus these to m, so
+ * nothing is lost to rounding; a share whose neighbour lies outside the raster leaves it.  A cell keeps its own sum (the flow through the
+ * cell).  The result is defined by that order alone and is the same bits on every schedule.  Cells that never send -- those on a cycle of
+ * caller-made fractions and everything downstream of one; fractions of a surface cannot form one -- hold MHIP_WACC_UNRESOLVED, and
+ * *unresolved counts them.  MHIP_ELIMIT: 2**31 cells or more.
+ * ctx_mfd_accum: on an undivided context with a valid MHIP_R_NOFLAT (MHIP_EINVAL otherwise): the fractions of the resident no-flats
+ * surface -- written first where it is still pending -- with `exponent`, and the accumulation of weight (a host raster of the context's
+ * shape, or NULL: MHIP_WACC_UNIT on every cell) down them.  The result is an mhip_wacc handle without zone sums (wacc_info: nzone == -1):
+ * a snapshot in buffers of its own, read with mhip_wacc_rows_u64 / _rows_f64 and freed with mhip_wacc_free.  wacc_work: what the tile
+ * schedule did for a result of ctx_mfd_accum -- its launches that had a list (rounds), the tile visits over all of them and the number of
+ * tiles; zeros for a result of ctx_weighted_accum. */
+#define MHIP_MFD_ONE 32768u
+int mhip_mfd_fractions_f64(const double *z, int64_t H, int64_t W, int32_t exponent, uint16_t *out);
+int mhip_mfd_accum_u32(const uint16_t *fractions, const uint32_t *weight, int64_t H, int64_t W, uint64_t *out, int64_t *unresolved);
+int mhip_ctx_mfd_accum(mhip_ctx *ctx, int32_t exponent, const uint32_t *weight_or_NULL, mhip_wacc **out);
+int mhip_wacc_work(const mhip_wacc *h, int64_t *rounds, int64_t *visits, int64_t *tiles);
+
 #ifdef __cplusplus
 }
 #endif

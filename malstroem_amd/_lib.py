@@ -94,7 +94,7 @@ SYMBOLS = [
     "mhip_polygonize_i32", "mhip_ctx_polygonize", "mhip_polygons_sizes", "mhip_polygons_fetch", "mhip_polygons_free",
     "mhip_flowpaths_f64", "mhip_ctx_flowpaths", "mhip_flowpaths_sizes", "mhip_flowpaths_fetch", "mhip_flowpaths_free",
     "mhip_weighted_accum_u32", "mhip_ctx_weighted_accum", "mhip_wacc_info", "mhip_wacc_rows_u64", "mhip_wacc_rows_f64", "mhip_wacc_zone_sums",
-    "mhip_wacc_free",
+    "mhip_wacc_free", "mhip_mfd_fractions_f64", "mhip_mfd_accum_u32", "mhip_ctx_mfd_accum", "mhip_wacc_work",
 ]
 
 _lib = None

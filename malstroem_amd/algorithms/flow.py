@@ -305,6 +305,43 @@ def weighted_accumulation(flowdir, weight, labelled=None):
     return (out, sums) if lab is not None else out
 
 
+def mfd_fractions(z, exponent=1):
+    """The multiple-flow-direction fractions of a surface (float64, as ``terrain_flowdirection`` takes it): ``uint16 [H, W, 8]`` in
+    units of ``1 / mfd.ONE``, per neighbour (0 up, then clockwise) the share of a cell's flow that goes there -- proportional to
+    ``slope ** exponent`` over the lower neighbours (``exponent`` an integer in 1..8: 1 spreads by slope, 8 is nearly D8), the
+    largest on the D8 direction, which also takes what the rounding leaves, so a cell's eight sum to ``mfd.ONE``.  A cell without a
+    lower neighbour, on the border, or with a ``z`` that is not finite has eight zeros.  No reference counterpart (the
+    definition is ``tests/_mfd.py``)."""
+    from ..mfd import check_exponent
+    e = check_exponent(exponent)
+    g = np.asarray(z)
+    if g.ndim != 2:
+        raise ValueError("Buffer has wrong number of dimensions (expected 2, got %d)" % g.ndim)
+    if g.dtype != DTYPE_FILLNOFLAT:
+        raise ValueError("Buffer dtype mismatch, expected 'float64' but got '%s'" % g.dtype)
+    g = np.ascontiguousarray(g)
+    out = np.empty(g.shape + (8,), dtype=np.uint16)
+    _lib.call("mhip_mfd_fractions_f64", _lib.ptr(g), _lib.i64(g.shape[0]), _lib.i64(g.shape[1]), ctypes.c_int32(e), _lib.ptr(out))
+    return out
+
+
+def mfd_accumulation(fractions, weight=None):
+    """The accumulation of ``weight`` (uint32; default ``runoff.UNIT`` on every cell) down ``fractions`` (uint16 ``[H, W, 8]``, a
+    cell's eight summing to 0 or ``mfd.ONE``; anything else is a ``ValueError`` from the device), in exact uint64: the flow through
+    every cell, its own weight included.  A cell sends once all of its inflows are complete: ``(sum * p) >> 15`` to each neighbour
+    but the one with the largest fraction, which gets the rest.  Cells on a cycle of the caller's fractions, and everything
+    downstream of one, hold ``WACC_UNRESOLVED``.  Returns ``(sums, unresolved)``.  No reference counterpart."""
+    from ..mfd import check_fractions
+    from ..runoff import UNIT, check_weight
+    fr = check_fractions(fractions)
+    shape = fr.shape[:2]
+    w = np.full(shape, UNIT, dtype=np.uint32) if weight is None else check_weight(weight, shape)
+    out = np.empty(shape, dtype=np.uint64)
+    unresolved = ctypes.c_int64(0)
+    _lib.call("mhip_mfd_accum_u32", _lib.ptr(fr), _lib.ptr(w), _lib.i64(shape[0]), _lib.i64(shape[1]), _lib.ptr(out), ctypes.byref(unresolved))
+    return out, unresolved.value
+
+
 # ---- per-cell host helpers (reference flow.py:170-301), used by stream tracing and tests --------------
 
 def direction_to_delta(direction):

@@ -90,7 +90,7 @@ def parse_filter(filter):
 def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, device=0, nodatasubst=-999, comm=None, backend_factory=None,
                 finalstate=False, hyps_resolution=0.05, onset=False, final_rasters=True, flowlength=False, *, objects=None, objects_grow=1,
                 flowpaths=None, flowpaths_stop_at_bluespots=True, hand=None, reach_catchments=False, inundation=None,
-                traveltime=False, runoff=None, sea=None, adaptations=None):
+                traveltime=False, runoff=None, mfd=None, sea=None, adaptations=None):
     """Quick option to run all processes (scripts/complete.py:37-117) on one MI355X -- or, with ``comm`` (a
     ``malstroem_amd.distributed.Comm`` of more than one rank; every rank calls this function), on the row bands of one DEM, one band per
     rank: see ``_process_all_bands``.
@@ -184,7 +184,24 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
     metres, and the rain events -- with everything derived from their volumes, ``finalstate`` and ``onset`` -- use it in place
     of ``wshed_area``.  With ``raster`` also writes ``runoff_accum.tif`` (float64, nodata -1): the effective upstream area of every
     cell in square metres; the dict gains ``runoff_accum``.  With a coefficient of 1 everywhere every other output is what it is
-    without the argument.  Not on row bands yet."""
+    without the argument.  Not on row bands yet.
+
+    ``mfd`` (keyword only): ``True`` or ``{"exponent": n}`` -- the multiple-flow-direction accumulation (``mfd.py``):
+    the flow of every cell spread over all of its lower neighbours of the no-flats surface by ``slope ** exponent`` (an integer in
+    1..8, default 1) instead of sent down the steepest one.  Writes ``accum_mfd.tif`` (float64, nodata -1): the upstream area of every
+    cell in cells, its own included; the dict gains ``accum_mfd``.  Every other output is what it is without the argument.  Not on
+    row bands yet."""
+    mfd_exponent = None
+    if mfd is not None and mfd is not False:
+        from .mfd import check_exponent
+        if mfd is True:
+            mfd = {}
+        if not isinstance(mfd, dict) or set(mfd) - {"exponent"}:
+            raise ValueError('mfd must be True or a dict {"exponent": n}, got %r' % (mfd,))
+        mfd_exponent = check_exponent(mfd.get("exponent", 1))
+        if comm is not None and comm.size > 1:
+            raise NotImplementedError("mfd on row bands: the flow crosses the seams between the bands, and the accumulation over "
+                                      "them is not built yet; run it on one context")
     runoff_weight = None
     if runoff is not None:
         if not isinstance(runoff, dict) or set(runoff) - {"coefficient", "pattern", "raster"}:
@@ -326,6 +343,9 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
         report_writer = io.VectorWriter('GeoJSON', outvector, 'adaptations', None, None, crs)
         adapt = dict(input_adaptations=io.VectorReader(adaptations), output_adapted=io.RasterWriter(adapted_path, tr, crs, nodatasubst),
                      output_adaptation_report=report_writer)
+    accum_mfd_path = os.path.join(outdir, 'accum_mfd.tif')
+    if mfd_exponent is not None:
+        adapt.update(output_accum_mfd=io.RasterWriter(accum_mfd_path, tr, crs, -1), mfd_exponent=mfd_exponent)
     pipe = DemTool(dem_reader, filled_writer, flowdir_writer, depths_writer, accum_writer, device=device, **adapt).process(keep_pipeline=True)
     try:
         # Process bluespots
@@ -416,6 +436,8 @@ def process_all(dem, outdir, rain, accum=False, filter=None, vector=False, devic
                    nodes=nodes_writer.filepath, streams=streams_writer.filepath, pourpoints=pourpoint_writer.filepath)
         if runoff_raster:
             res["runoff_accum"] = runoff_accum_path
+        if mfd_exponent is not None:
+            res["accum_mfd"] = accum_mfd_path
         if vector:
             res.update(bluespots_vector=labeled_vector_writer.filepath, watersheds_vector=watershed_vector_writer.filepath)
         if flowlength:

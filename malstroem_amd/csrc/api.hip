@@ -753,10 +753,54 @@ int mhip_wacc_zone_sums(const mhip_wacc *p, uint64_t *dst)
     return MHIP_OK;
 }
 
+int mhip_wacc_work(const mhip_wacc *p, int64_t *rounds, int64_t *visits, int64_t *tiles)
+{
+    MH_ARG(p && rounds && visits && tiles, "wacc_work(wacc, rounds, visits, tiles)");
+    *rounds = p->rounds;
+    *visits = p->visits;
+    *tiles = p->tiles;
+    return MHIP_OK;
+}
+
 void mhip_wacc_free(mhip_wacc *p)
 {
     if (p && p->device >= 0) (void)hipSetDevice(p->device);
     delete p;
+}
+
+/* ---- multiple-flow-direction accumulation (mfd.hip): the two stand-alone calls --------------------------------------------------- */
+int mhip_mfd_fractions_f64(const double *z, int64_t H, int64_t W, int32_t exponent, uint16_t *out)
+{
+    MH_ARG(z && out, "mfd_fractions_f64(z, H, W, exponent, out)");
+    MH_ARG(exponent >= 1 && exponent <= 8, "mfd_fractions_f64: exponent in [1, 8]");
+    MH_TRY(mfd_check(H, W));
+    MH_TRY(require_device());
+    const size_t n = (size_t)(H * W);
+    hipStream_t s = 0;
+    DevBuf d_z, d_out;
+    MH_TRY(upload(d_z, z, 8 * n, s));
+    MH_TRY(d_out.alloc(16 * n));
+    MH_TRY(mfd_fractions_dev(d_z.as<double>(), H, W, exponent, d_out.as<uint16_t>(), s));
+    return download(out, d_out, 16 * n, s);
+}
+
+int mhip_mfd_accum_u32(const uint16_t *fractions, const uint32_t *weight, int64_t H, int64_t W, uint64_t *out, int64_t *unresolved)
+{
+    MH_ARG(fractions && weight && out && unresolved, "mfd_accum_u32(fractions, weight, H, W, out, unresolved)");
+    MH_TRY(mfd_check(H, W));
+    MH_TRY(require_device());
+    const size_t n = (size_t)(H * W);
+    hipStream_t s = 0;
+    DevBuf d_fr, d_w, d_out;
+    MH_TRY(upload(d_fr, fractions, 16 * n, s));
+    MH_TRY(upload(d_w, weight, 4 * n, s));
+    MH_TRY(d_out.alloc(8 * n));
+    const int rc = mfd_accum_dev(d_fr.as<uint16_t>(), d_w.as<uint32_t>(), 0u, H, W, d_out.as<unsigned long long>(), unresolved, nullptr, s);
+    if (rc != MHIP_OK) {
+        (void)stream_sync(s);      // (the uploads may still read the caller's arrays)
+        return rc;
+    }
+    return download(out, d_out, 8 * n, s);
 }
 
 }  // extern "C"

@@ -788,6 +788,7 @@ struct mhip_flowpaths {     // a result of mhip_flowpaths_f64 / mhip_ctx_flowpat
 struct mhip_wacc {          // a result of mhip_ctx_weighted_accum: a snapshot in buffers of its own on `device`
     mh::DevBuf acc, sums;                         // uint64 [H][W]; uint64 [nzone + 1] (none without zones: nzone == -1)
     int64_t H = 0, W = 0, nzone = -1, unresolved = 0;
+    int64_t rounds = 0, visits = 0, tiles = 0;    // of mhip_ctx_mfd_accum: launches of the tile schedule, tile visits, tiles (else 0)
     int device = -1;
 };
 
@@ -801,4 +802,16 @@ int wacc_check(int64_t H, int64_t W, int64_t nzone, bool zones);
 int wacc_dev(const uint8_t *d_fd, const uint32_t *d_w, const int32_t *d_zones, int64_t H, int64_t W, int64_t nzone, unsigned long long *d_out,
              unsigned long long *d_sums, int64_t *unresolved, hipStream_t s);
 int wacc_rows_f64_dev(const mhip_wacc *p, int64_t row0, int64_t nrows, double div, double mul, double nodata, double *dst);
+
+// mfd.hip: multiple-flow-direction accumulation (the definition is tests/_mfd.py).  mfd_check: the argument rules on the
+// shape (MHIP_EINVAL, MHIP_ELIMIT; no device work).  mfd_fractions_dev: the uint16 fractions [H][W][8] of a float64 surface; queues one
+// launch and does not synchronise.  mfd_accum_dev: the sums of d_w -- or, with d_w null, of `wconst` on every cell -- down the fractions
+// into d_out (uint64, H x W) and the number of unresolved cells.  Synchronises.  MHIP_EINVAL: fractions that sum to neither 0 nor ONE.
+struct MfdStats {
+    int64_t rounds = 0, visits = 0, tiles = 0;
+};
+int mfd_check(int64_t H, int64_t W);
+int mfd_fractions_dev(const double *d_z, int64_t H, int64_t W, int exponent, uint16_t *d_out, hipStream_t s);
+int mfd_accum_dev(const uint16_t *d_fr, const uint32_t *d_w, uint32_t wconst, int64_t H, int64_t W, unsigned long long *d_out, int64_t *unresolved,
+                  MfdStats *stats, hipStream_t s);
 }  // namespace mh

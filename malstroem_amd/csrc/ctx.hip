@@ -983,6 +983,48 @@ int mhip_ctx_weighted_accum(mhip_ctx *c, const uint32_t *weight, int32_t use_wat
     return MHIP_OK;
 }
 
+/* ---- multiple-flow-direction accumulation down the resident no-flats surface (mfd.hip): a snapshot in an mhip_wacc handle ------------ */
+int mhip_ctx_mfd_accum(mhip_ctx *c, int32_t exponent, const uint32_t *weight, mhip_wacc **out)
+{
+    MH_ARG(c && out, "ctx_mfd_accum(ctx, exponent, weight_or_NULL, out)");
+    MH_ARG(undivided(c), "mfd accumulation on a row band is not built (the flow crosses the seams: a later step); use an undivided context");
+    MH_ARG(c->have[MHIP_R_NOFLAT], "ctx_mfd_accum needs the NOFLAT raster");
+    MH_ARG(exponent >= 1 && exponent <= 8, "ctx_mfd_accum: exponent in [1, 8]");
+    MH_TRY(mfd_check(c->H, c->W));
+    MH_HIP(hipSetDevice(c->device));
+    double *g = nullptr;
+    MH_TRY(ctx_noflat(c, &g));      // (a pending surface is written first, as for every other reader)
+    mhip_wacc *p = new (std::nothrow) mhip_wacc();
+    if (!p) {
+        set_error("ctx_mfd_accum: out of host memory");
+        return MHIP_EHIP;
+    }
+    p->device = c->device;
+    p->H = c->H;
+    p->W = c->W;
+    p->nzone = -1;
+    const size_t n = (size_t)(c->H * c->W);
+    DevBuf d_w, d_fr;
+    int rc = weight ? upload(d_w, weight, 4 * n, c->stream) : MHIP_OK;
+    if (rc == MHIP_OK) rc = d_fr.alloc(16 * n);
+    if (rc == MHIP_OK) rc = p->acc.alloc(8 * n);
+    if (rc == MHIP_OK) rc = mfd_fractions_dev(g, c->H, c->W, exponent, d_fr.as<uint16_t>(), c->stream);
+    MfdStats st;
+    if (rc == MHIP_OK)
+        rc = mfd_accum_dev(d_fr.as<uint16_t>(), weight ? d_w.as<uint32_t>() : nullptr, MHIP_WACC_UNIT, c->H, c->W, p->acc.as<unsigned long long>(), &p->unresolved,
+                           &st, c->stream);      // (synchronises)
+    p->rounds = st.rounds;
+    p->visits = st.visits;
+    p->tiles = st.tiles;
+    if (rc != MHIP_OK) {
+        (void)stream_sync(c->stream);      // (the upload may still read the caller's array)
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return MHIP_OK;
+}
+
 /* ---- reach catchments and flood depths from a stage per reach (hand.hip, flowpaths.hip, reachcatch.hip) ---------------------------- */
 int mhip_ctx_reach_catchments(mhip_ctx *c, double threshold, int32_t stop_at_labels, mhip_flowpaths **out, int64_t *assigned)
 {

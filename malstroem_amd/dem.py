@@ -7,6 +7,7 @@ computed in one device-resident pass; nothing is recomputed and nothing goes thr
 import logging
 
 from .algorithms import dtypes, speedups
+from .mfd import check_exponent
 from .pipeline import HydroPipeline
 
 
@@ -17,8 +18,8 @@ class DemTool(object):
     ``write(array)``.  Input x, y, z must be in meters and cells must be square.
     """
 
-    def __init__(self, input_dem, output_filled, output_flowdir, output_depths, output_accum=None, device=0, input_adaptations=None,
-                 output_adapted=None, output_adaptation_report=None):
+    def __init__(self, input_dem, output_filled, output_flowdir, output_depths, output_accum=None, device=0, output_accum_mfd=None,
+                 mfd_exponent=1, input_adaptations=None, output_adapted=None, output_adaptation_report=None):
         self.input_dem = input_dem
         self.output_filled = output_filled
         self.output_flowdir = output_flowdir
@@ -30,6 +31,10 @@ class DemTool(object):
         self.input_adaptations = input_adaptations
         self.output_adapted = output_adapted
         self.output_adaptation_report = output_adaptation_report
+        # multiple-flow-direction accumulation (mfd.py): a raster writer for the upstream area in cells (float64, -1 where a cell has
+        # no answer) and the exponent of the slopes
+        self.output_accum_mfd = output_accum_mfd
+        self.mfd_exponent = check_exponent(mfd_exponent)
         self.logger = logging.getLogger(__name__)
 
     def _adapt(self, pipe, transform):
@@ -74,6 +79,10 @@ class DemTool(object):
                 self.logger.info("Calculating flow accumulation")
                 pipe.run("accum")
                 pipe.download_to("accum", self.output_accum)
+            if self.output_accum_mfd is not None:
+                self.logger.info("Calculating multiple-flow-direction accumulation")
+                with pipe.mfd_accumulation(self.mfd_exponent) as acc:
+                    acc.download_to(self.output_accum_mfd)      # (div = UNIT, mul = 1: cells)
             self.logger.info("Done")
         except Exception:
             pipe.close()

@@ -416,6 +416,21 @@ class HydroPipeline(CtxHandle):
         _lib.call("mhip_ctx_weighted_accum", self._ctx, _lib.ptr(w), ctypes.c_int32(1 if by_watersheds else 0), ctypes.byref(handle))
         return WeightedAccum(handle)
 
+    # ---- multiple-flow-direction accumulation down the resident no-flats surface (mfd.py) ----------------------
+    def mfd_accumulation(self, exponent=1, weight=None):
+        """The multiple-flow-direction accumulation of ``weight`` (uint32 raster of the pipeline's shape; default ``runoff.UNIT``
+        on every cell, and then nothing crosses the bus) down the fractions of the resident no-flats surface with ``exponent`` (an
+        integer in 1..8), in exact uint64 sums, as a ``runoff.WeightedAccum`` without sums per watershed: a snapshot on the device
+        that no later upload or run changes and that outlives the pipeline.  ``algorithms.flow.mfd_fractions`` and
+        ``.mfd_accumulation`` on the downloaded surface give the same bits."""
+        from .mfd import check_exponent
+        from .runoff import WeightedAccum, check_weight
+        e = check_exponent(exponent)
+        w = check_weight(weight, self.shape) if weight is not None else None
+        handle = ctypes.c_void_p()
+        _lib.call("mhip_ctx_mfd_accum", self._ctx, ctypes.c_int32(e), _lib.ptr(w) if w is not None else None, ctypes.byref(handle))
+        return WeightedAccum(handle)
+
     # ---- reach catchments and flood depths from a stage per reach (flowpaths.py; DESIGN.md 17) ---------------------------
     def reach_catchments(self, threshold, stop_at_bluespots=True):
         """``(xy, reach_offsets, records, unresolved, assigned)``: the reaches of ``flow_paths`` with the same arguments and, in a

@@ -131,6 +131,14 @@ class WeightedAccum(object):
         from .pipeline import write_windows
         write_windows(writer, self.shape, np.float64, lambda row0, n: self.download_rows(row0, n, div, mul, nodata), max_rows)
 
+    def work(self):
+        """``{"rounds", "visits", "tiles"}``: what the tile schedule did for a result of ``HydroPipeline.mfd_accumulation`` (DESIGN.md
+        21) -- launches that had a list, tile visits over all of them, tiles; zeros for a weighted accumulation."""
+        self._open()
+        r, v, t = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.call("mhip_wacc_work", self._h, ctypes.byref(r), ctypes.byref(v), ctypes.byref(t))
+        return {"rounds": r.value, "visits": v.value, "tiles": t.value}
+
     def sums(self):
         """The sum of the weights per watershed (uint64, ``nlabels + 1`` entries); ``ValueError`` when the result was made without
         the watersheds."""
